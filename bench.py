@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """FOTO hot-path benchmark: Benamou-Brenier outer iterations/s on the 640x480x32 grid.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--cg-mode 0|1|2|3]
-                    [--no-cpu-baseline] [--no-gn] [--no-stencil] [--no-batch] [--no-c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--cg-mode 0|1|2|3] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-gn] [--no-stencil] [--no-kernel-timing]
+                            [--no-batch] [--no-c4]]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value,
+ms_per_step, the CG counts of the timed steps); --dump-outputs DIR also writes what the last
+timed step left (dump_outputs below).  Everything else this file measures -- the per-launch
+kernel timing pass with its rooflines and stream probes, the literal stencil CG, GN, the CPU
+baselines, and for N > 1 config 4 and the batch -- runs only with --full, as described below.
 
 A "step" is one outer iteration of benamou_brenier.solve (benamou_brenier.py:204-258:
 RHS + CG Poisson solve + stepB/stepC + criterion) over the synthetic 640x480x32
@@ -10,16 +17,17 @@ translating-Gaussian pair (SURVEY.md §8(d) S-metric; r = 1, eps = 1e-2, run.sh:
 parameters), with every input and all solver state resident in HBM.  The stop rules are
 disabled so exactly K steps run.
 
-N = 1: the single-GPU solve; the line also carries a "gn" object (the GN baseline, classical.py,
-SURVEY.md config 3, at 640x480 and 320x240 with the oracle's SuperLU solve beside it), the
-literal stencil-CG rate and the CPU baseline (the oracle on one host core).
+N = 1: the single-GPU solve; with --full the line also carries a "gn" object (the GN baseline,
+classical.py, SURVEY.md config 3, at 640x480 and 320x240 with the oracle's SuperLU solve beside
+it), the literal stencil-CG rate and the CPU baseline (the oracle on one host core).
 
 N > 1 (torch.distributed.run, one process per GPU): the headline is north_star's decomposition --
 ONE 640x480x32 solve time-sharded over the N GPUs (N time slabs; the slab <-> row-box all-to-alls,
 the phi / w_t halos and the histogram all-gather over RCCL), "scaling": "strong",
 value = its outer iterations per second on the slowest rank's clock.  It runs in a child process
 per rank under a watchdog (FOTO_BENCH_SHARD_TIMEOUT, 180 s): if RCCL fails or hangs on any rank,
-value is null and the line says why -- it is never replaced by another number.  Side objects:
+value is null and the line says why -- it is never replaced by another number.  Side objects
+(--full):
   * "c4": BASELINE config 4, the 1024x1024x64 pair time-sharded over the same N GPUs (its own
     child per rank, its own communicator);
   * "batch": N independent 640x480x32 solves, one per GPU (config 5's shape: run.py streams
@@ -60,6 +68,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cg-mode", type=int, default=int(os.environ.get("FOTO_CG_MODE", "3")),
                     help="0 stencil CG, 1 spectral CG (one GPU), 2 spectral s-step CG, 3 Gauss-compressed spectral CG (default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (per-launch kernel timing and rooflines, literal stencil CG, "
+                         "GN, CPU baselines; N > 1: config 4 and the data-parallel batch); the --no-* options below "
+                         "then leave single ones out.  Without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (flow, criterion, CG counts, samples of "
+                         "phi / mu / q) to DIR/<name>.npy (one GPU)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gn", action="store_true", help="skip the GN (classical.py, config 3) side measurement")
     ap.add_argument("--no-stencil", action="store_true", help="skip the literal stencil-CG side measurement")
@@ -73,7 +88,11 @@ def parse():
     ap.add_argument("--c4-warmup", type=int, default=2)
     ap.add_argument("--shard-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--grid", type=int, nargs=3, default=[NX, NY, NT], help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:   # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_gn = args.no_stencil = args.no_kernel_timing = True
+        args.no_batch = args.no_c4 = True
+    return args
 
 
 CPU_K = 2   # outer iterations the CPU baseline runs (BASELINE.md / SURVEY.md §8(d): K = 2 on CPU)
@@ -603,6 +622,8 @@ def run_shard_side(args, rdv, rank, world, local_rank, grid, steps, warmup, tag)
         env.setdefault("NCCL_SOCKET_IFNAME", "lo")
         cmd = [sys.executable, os.path.abspath(__file__), "--shard-child", "--gpus", str(world), "--steps", str(steps),
                "--warmup", str(warmup), "--cg-mode", str(args.cg_mode), "--grid", *[str(v) for v in grid]]
+        if args.full:
+            cmd.append("--full")
         if args.no_kernel_timing:
             cmd.append("--no-kernel-timing")
         proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
@@ -631,6 +652,30 @@ def run_shard_side(args, rdv, rank, world, local_rank, grid, steps, warmup, tag)
 
 # ----------------------------------------------------------------------- the solve on this GPU
 
+DUMP_SAMPLE, DUMP_SEED = 1 << 19, 20240611   # voxels of each full-grid field written by --dump-outputs
+
+
+def dump_outputs(out_dir, s, first):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64
+    DIR/<name>.npy -- the flow (u, v, m: whole Nx x Ny fields), crit and cg_its of the timed
+    steps (from index `first`), and phi and the three components of mu and q at DUMP_SAMPLE
+    voxels drawn once from a fixed seed (the whole grids are 550 MB; these files 41 MB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = dict(zip(("u", "v", "m"), s.flow()))
+    out["crit"] = np.asarray(s.crit[first:], dtype=np.float64)
+    out["cg_its"] = np.asarray(s.cg_its[first:], dtype=np.float64)
+    n = s.Nt * s.Nx * s.Ny
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    out["sample_index"] = idx.astype(np.float64)
+    out["phi_sample"] = s.phi()[idx]
+    mu, q = s.state()
+    for name, a in (("mu", mu), ("q", q)):
+        for c in range(3):
+            out[f"{name}{c}_sample"] = a[c * n:(c + 1) * n][idx]
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def measure_local(args, device, rdv):
     """This GPU's own 640x480x32 solve (N = 1: the headline; N > 1: one of the batch's
     independent solves): warmup, barrier, K timed steps (max over ranks), then K more with a HIP
@@ -658,6 +703,8 @@ def measure_local(args, device, rdv):
         rdv.barrier()
     cg_steps = s.cg_its[its_before:]
     st_timed = s.stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, s, its_before)
 
     roof, kern, phase_ms = None, {}, None
     if not args.no_kernel_timing:
@@ -779,6 +826,8 @@ def main():
         local_rank = visible_device(local_rank)
     if world != args.gpus and world > 1:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    if world > 1 and args.dump_outputs:
+        raise SystemExit("--dump-outputs writes the single-GPU solve's results: run it with --gpus 1")
 
     if world > 1:
         rdv = FileRendezvous(rank, world)

@@ -90,6 +90,18 @@ def test_n2_line_without_a_device_reports_null_value(tmp_path):
     assert d["batch"] is None and d["c4"] is None
 
 
+def test_plain_run_measures_the_headline_only(bench, monkeypatch):
+    """Without --full every side measurement is off; with it the --no-* options pick."""
+    side = ("no_cpu_baseline", "no_gn", "no_stencil", "no_kernel_timing", "no_batch", "no_c4")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert all(getattr(a, k) for k in side)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-gn", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and [k for k in side if getattr(a, k)] == ["no_gn"]
+
+
 def test_visible_device(bench, monkeypatch):
     for k in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
         monkeypatch.delenv(k, raising=False)

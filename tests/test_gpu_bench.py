@@ -1,7 +1,8 @@
 """The bench line the driver parses (README "bench.py contract"): one JSON line on stdout with
 the metric of BASELINE.json, whole-job throughput, the roofline object of the dominant kernel
-and the whole-step object.  A short run (3 timed outer iterations, no CPU baseline, no side
-measurements) on the GPU."""
+and the whole-step object.  A short run (3 timed outer iterations; --full for the kernel-timing
+pass behind the roofline, without the CPU baseline and the side measurements) on the GPU, and a
+plain run with --dump-outputs."""
 import json
 import os
 import subprocess
@@ -20,7 +21,7 @@ def test_bench_json_line():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--full",
                           "--no-cpu-baseline", "--no-gn", "--no-stencil"], cwd=REPO, env=env,
                          capture_output=True, text=True, timeout=180)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -46,6 +47,57 @@ def test_bench_json_line():
     assert "cpu_baseline" not in d or d["cpu_baseline"] is None
 
 
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run (no --full) measures the headline alone -- the same keys, no kernel-timing
+    pass or side object -- and --dump-outputs writes what its timed steps left: float64 .npy
+    files of at most 64 MB, crit and cg_its of exactly --steps steps, and the flow of warmup +
+    steps outer iterations, compared with the same solve made here (same library, same inputs;
+    atol 1e-7 is smoke()'s bound against the oracle, so it bounds two runs of one build)."""
+    import numpy as np
+    from foto.bb import BBSolver
+    from foto.synthetic import translating_gaussian
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(dump)], cwd=REPO, env=env, capture_output=True, text=True, timeout=180)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == bench.METRIC and d["unit"] == "iters/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 0.01
+    assert 150 <= d["cg_iters_per_step"] <= 210
+    assert d["roofline"] is None and d["kernels"] == {} and d["phase_ms"] is None
+    for key in ("literal_stencil", "gn", "cpu_baseline", "speedup_vs_cpu"):
+        assert key not in d, key
+    arrs = {f[:-4]: np.load(dump / f, allow_pickle=False) for f in sorted(os.listdir(dump))}
+    assert set(arrs) == {"u", "v", "m", "crit", "cg_its", "sample_index", "phi_sample"} | {
+        f"{a}{c}_sample" for a in ("mu", "q") for c in range(3)}
+    assert all(a.dtype == np.float64 for a in arrs.values())
+    assert sum(os.path.getsize(dump / f) for f in os.listdir(dump)) <= 64 << 20
+    assert arrs["crit"].shape == arrs["cg_its"].shape == (2,)
+    assert abs(arrs["cg_its"].mean() - d["cg_iters_per_step"]) <= 0.005
+    idx = arrs["sample_index"].astype(np.int64)
+    assert idx.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(idx) > 0) and idx[-1] < 640 * 480 * 32
+    rho0, rhoT = translating_gaussian(640, 480)
+    with BBSolver(rho0, rhoT, 32, 640, 480, r=bench.R, reg_epsilon=bench.EPS, device=0) as s:
+        for k in (1, 2):   # warmup, then the timed steps, as measure_local calls them
+            s.iterate(k, 0.0, stop_rules=False)
+            s.sync()
+        u, v, m = s.flow()
+        phi, (mu, q), crit, its = s.phi(), s.state(), s.crit[1:], s.cg_its[1:]
+    assert list(arrs["cg_its"]) == its
+    np.testing.assert_allclose(arrs["crit"], crit, rtol=1e-7)
+    for name, ref in (("u", u), ("v", v), ("m", m), ("phi_sample", phi[idx]),
+                      ("mu0_sample", mu[idx]), ("q2_sample", q[2 * 640 * 480 * 32 + idx])):
+        print(name, "max |diff|", np.abs(arrs[name] - ref).max(), "max |ref|", np.abs(ref).max())
+        np.testing.assert_allclose(arrs[name], ref, rtol=0, atol=1e-7, err_msg=name)
+        assert np.abs(ref).max() > 0, name
+
+
 def _ranks(n, port, extra_env=None, args=()):
     """bench.py --gpus n as the driver launches it (torch.distributed.run: one process per rank,
     RANK / WORLD_SIZE / LOCAL_RANK / MASTER_PORT set, children of one process) without its torch
@@ -58,7 +110,7 @@ def _ranks(n, port, extra_env=None, args=()):
                    LOCAL_RANK=str(g), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    FOTO_BENCH_SHARD_TIMEOUT="150", **(extra_env or {}))
         cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
-               "--no-cpu-baseline", "--no-gn", "--no-stencil", *args]
+               "--full", "--no-cpu-baseline", "--no-gn", "--no-stencil", *args]
         procs.append(subprocess.Popen(cmd, cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                                       text=True))
     outs = [p.communicate(timeout=280) for p in procs]

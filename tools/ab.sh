@@ -9,7 +9,7 @@
 # Run from the repo root on the GPU box.
 set -o pipefail
 tag=$1; shift
-reps=2; tests=""; bargs="--no-cpu-baseline --no-gn --no-stencil --steps 100"
+reps=2; tests=""; bargs="--full --no-cpu-baseline --no-gn --no-stencil --steps 100"
 while getopts "r:t:b:" o; do
   case $o in r) reps=$OPTARG ;; t) tests=$OPTARG ;; b) bargs=$OPTARG ;; *) exit 2 ;; esac
 done

@@ -9,6 +9,6 @@ echo "tests rc=$rc"; tail -3 $O/tests_$tag.log; grep -E "^FAILED|^ERROR" $O/test
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke_$tag.log 2>&1 || exit 3
 tail -1 $O/smoke_$tag.log
-timeout -k 10 300 python bench.py --no-cpu-baseline --no-gn --no-stencil > $O/bench_$tag.json 2> $O/bench_$tag.err || exit 4
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-gn --no-stencil > $O/bench_$tag.json 2> $O/bench_$tag.err || exit 4
 python tools/show_bench.py $O/bench_$tag.json 2>/dev/null || tail -c 600 $O/bench_$tag.json
 exit $rc
