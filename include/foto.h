@@ -7,6 +7,7 @@
  * [t-part; x-part; y-part]) and returns 0 on success, < 0 on error
  * (foto_last_error() has the message).  Each declaration cites the reference
  * interface it replaces (paths relative to the reference repository root).
+ * The *_dev entries at the end of this header are the same calls on DEVICE memory.
  *
  * The reference is pure Python (numpy/scipy); its "FFI" for this path is the
  * Python call surface.  The binding a maintainer adds is the ctypes layer in
@@ -297,6 +298,78 @@ int foto_flow_errors(const double* u, const double* v, const double* uGT, const 
                      double* out4);
 /* utils.IE (utils.py:340-354): RMS of 255 I - 255 IGT.                              */
 int foto_intensity_error(const double* I, const double* IGT, int w, int h, double* ie);
+
+/* ------------------------------------------------------------------ device buffers
+ * The same solvers and metrics for a caller whose frames are already in HBM (a decoder, a
+ * PyTorch-ROCm tensor, the output of an earlier foto_*_dev call): frames in, flow out, without
+ * the round trip through host float64 arrays.  Additive: every entry above is unchanged.
+ *
+ * Stream contract, identical for every *_dev call: `stream` is the caller's hipStream_t (NULL:
+ * the legacy null stream).  libfoto's own streams are non-blocking, so each call makes its
+ * stream wait for what `stream` has enqueued before it first reads an input or writes an output,
+ * and makes `stream` wait for its last write before it returns.  On return the inputs may be
+ * overwritten and the outputs consumed by work queued on `stream`, with no host synchronisation
+ * by the caller.  Every device pointer is checked with hipPointerGetAttributes to be device
+ * memory of the context's / plan's / current device before anything is enqueued (host memory
+ * or another GPU's: FOTO_ERR_ARG, never dereferenced).                                      */
+#define FOTO_U8 0
+#define FOTO_F32 1
+#define FOTO_F64 2
+/* One grey-scale frame as a strided view: what utils.openGrayscaleImage (utils.py:39-42) returns
+ * -- np.float64(PIL 'L' image) / 255 -- is {u8 pixels, FOTO_U8, pitch, 1, 255.0}; a row-padded
+ * frame, one channel of an interleaved [H][W][C] array and a transposed view are strides.   */
+typedef struct {
+    const void* data;      /* DEVICE pointer to pixel (row 0, column 0)                    */
+    int dtype;             /* FOTO_U8 / FOTO_F32 / FOTO_F64                                */
+    int64_t stride_y, stride_x;   /* in ELEMENTS, both > 0                                 */
+    double divisor;        /* value = (double)pixel / divisor (255 for 8-bit images, 1 otherwise) */
+} foto_image;
+
+/* Host-only validation of a descriptor for a w x h frame (no HIP call): FOTO_ERR_ARG for null
+ * data, a dtype outside 0..2, a stride <= 0, a divisor that is 0 or not finite, data not aligned
+ * to its element size, or rows (columns, for a transposed view) that overlap.  Every entry
+ * below calls it first (utils.openGrayscaleImage, utils.py:39-42, has no such view to check). */
+int foto_image_check(const foto_image* im, int w, int h);
+
+/* foto_bb_create / foto_bb_reset from device frames (w = Nx, h = Ny): the context is left in
+ * exactly the state the host entries leave for rho = (double)pixel / divisor, so the solve that
+ * follows is bit-identical.  normalize = 1 divides each frame by its own sum (main.py:71-74:
+ * f0 / np.sum(f0)), a fixed-order device reduction, reported in sums2_or_null[0..1] ({1, 1}
+ * with normalize = 0).  world == 1 only (virtual_ranks > 1 included); an RCCL context returns
+ * FOTO_ERR_STATE.  An argument error leaves an existing context untouched.               */
+int foto_bb_create_dev(const foto_image* f0, const foto_image* f1, int normalize, void* stream, int Nt, int Nx,
+                       int Ny, double r, double reg_epsilon, const foto_bb_opts* opts, double* sums2_or_null,
+                       foto_bb_ctx** out);
+int foto_bb_reset_dev(foto_bb_ctx* c, const foto_image* f0, const foto_image* f1, int normalize, void* stream,
+                      double* sums2_or_null);
+/* foto_bb_flow into device memory `out` of dtype FOTO_F32 | FOTO_F64: layout 0 is planar
+ * [3][Ny][Nx] = u, v, m; layout 1 is interleaved [Ny][Nx][2] = (u, v), the payload
+ * utils.saveFlo (utils.py:273-292) writes after its 12-byte header.  (float)x rounds to nearest
+ * even, as np.float32(x).  Same callback and in-flight rules as foto_bb_flow.            */
+int foto_bb_flow_dev(foto_bb_ctx* c, void* out, int dtype, int layout, void* stream);
+
+/* foto_gn_plan_solve (classical.py:68-130) on device frames, the solution exported to `out` as
+ * foto_bb_flow_dev does (planar: u, v, m).  Same PCG launches, prediction, result and return
+ * codes as foto_gn_plan_solve; it neither makes nor touches the plan's pinned host staging.  */
+int foto_gn_plan_solve_dev(foto_gn_plan* p, const foto_image* f1, const foto_image* f2, void* out, int dtype,
+                           int layout, void* stream, int* iterations);
+
+/* foto_warp / foto_flow_errors / foto_intensity_error (utils.py:186-248, 294-354) on contiguous
+ * float64 DEVICE arrays of w * h elements: the same kernels and reduction order without the
+ * uploads.  `out` of the warp is a device array (not aliasing an input); the metrics return
+ * host scalars (the call waits for them).                                                 */
+int foto_warp_dev(const double* f1, const double* u, const double* v, const double* m, int w, int h, double* out,
+                  void* stream);
+int foto_flow_errors_dev(const double* u, const double* v, const double* uGT, const double* vGT, int w, int h,
+                         double* out4, void* stream);
+int foto_intensity_error_dev(const double* I, const double* IGT, int w, int h, double* ie, void* stream);
+
+/* Device memory of the current device for callers without another GPU library (the ctypes
+ * binding, the tests): hipMalloc / hipFree / a blocking hipMemcpy on the null stream.
+ * kind: 0 host -> device, 1 device -> host, 2 device -> device.                          */
+int foto_dev_malloc(size_t bytes, void** out);
+int foto_dev_free(void* p);
+int foto_dev_memcpy(void* dst, const void* src, size_t bytes, int kind);
 
 #ifdef __cplusplus
 }

@@ -222,6 +222,11 @@ struct foto_bb_ctx {
     bool hcrit = false;            // single shard, fused prox: the kernel writes crit to hgath itself
     bool phase_force = false;      // FOTO_PHASE_EV=1: phase events even without kernel timing
     int hpar = 0;                  // slot of the last head
+    // device-buffer entries (foto_bb_*_dev): the events that order the caller's stream with s,
+    // and the scratch of normalize = 1 ({S0, ST, block partials}, made on first use)
+    StreamLink link;
+    double* nrm = nullptr;
+    double hsum[2] = {0, 0};
     ~foto_bb_ctx() {
         if (sc) (void)hipStreamSynchronize(sc);
         if (s) (void)hipStreamSynchronize(s);   // (before the shards free their buffers)
@@ -338,7 +343,51 @@ static int halo(foto_bb_ctx* c, Pick pick) {
 
 // ----------------------------------------------------------------------------- context setup
 
-static int ctx_init(foto_bb_ctx* c, const double* rho0, const double* rhoT) {
+// Where a context's two densities come from: the caller's host arrays (foto_bb_create / reset),
+// or two device images (foto_bb_create_dev / reset_dev).  The two uploads are the only
+// difference between the entries: everything around load_rho is shared, so the state it leaves
+// is the one the host entries leave for rho = (double)pixel / divisor.
+struct RhoSrc {
+    const double* h0 = nullptr;
+    const double* hT = nullptr;
+    const foto_image* i0 = nullptr;
+    const foto_image* iT = nullptr;
+    int normalize = 0;
+    hipStream_t user = nullptr;
+};
+
+static int load_rho(foto_bb_ctx* c, Shard& s, const RhoSrc& src) {
+    const int64_t nxy = (int64_t)c->Nx * c->Ny;
+    if (!src.i0) {
+        FOTO_HIP_CHECK(hipMemcpyAsync(s.rho0, src.h0, nxy * sizeof(double), hipMemcpyHostToDevice, c->s));
+        FOTO_HIP_CHECK(hipMemcpyAsync(s.rhoT, src.hT, nxy * sizeof(double), hipMemcpyHostToDevice, c->s));
+        return 0;
+    }
+    if (!c->sh.empty() && c->sh[0].get() != &s) {   // (virtual ranks: every further shard gets its copy)
+        FOTO_HIP_CHECK(hipMemcpyAsync(s.rho0, c->sh[0]->rho0, nxy * sizeof(double), hipMemcpyDeviceToDevice, c->s));
+        FOTO_HIP_CHECK(hipMemcpyAsync(s.rhoT, c->sh[0]->rhoT, nxy * sizeof(double), hipMemcpyDeviceToDevice, c->s));
+        return 0;
+    }
+    FOTO_TRY(c->link.enter(src.user, c->s));   // (before the first read of an input)
+    FOTO_HIP_CHECK(launch_ingest(*src.i0, c->Nx, c->Ny, s.rho0, c->s));
+    FOTO_HIP_CHECK(launch_ingest(*src.iT, c->Nx, c->Ny, s.rhoT, c->s));
+    if (src.normalize) {   // each frame over its own sum (main.py:71-74), the sum in a fixed order
+        if (!c->nrm) {
+            void* b = nullptr;
+            FOTO_TRY(s.alloc(sizeof(double) * (2 + (size_t)sum_blocks(nxy)), &b));
+            c->nrm = (double*)b;
+        }
+        double* const rho[2] = {s.rho0, s.rhoT};
+        for (int k = 0; k < 2; ++k) {
+            FOTO_HIP_CHECK(launch_sum(nxy, rho[k], c->nrm + 2, c->nrm + k, c->s));
+            FOTO_HIP_CHECK(launch_div_scalar(nxy, rho[k], c->nrm + k, c->s));
+        }
+        FOTO_HIP_CHECK(hipMemcpyAsync(c->hsum, c->nrm, 2 * sizeof(double), hipMemcpyDeviceToHost, c->s));
+    }
+    return 0;
+}
+
+static int ctx_init(foto_bb_ctx* c, const RhoSrc& src) {
     const int64_t nxy = (int64_t)c->Nx * c->Ny;
     if (c->o.device >= 0) FOTO_HIP_CHECK(hipSetDevice(c->o.device));
     FOTO_TRY(stream_acquire(&c->s));
@@ -432,8 +481,7 @@ static int ctx_init(foto_bb_ctx* c, const double* rho0, const double* rhoT) {
         FOTO_TRY(s.alloc(sizeof(double) * 4 * W, &b)); s.gath = (double*)b;
         FOTO_HIP_CHECK(hipMemsetAsync(s.gath, 0, sizeof(double) * 4 * W, c->s));
         FOTO_TRY(s.alloc(sizeof(CGScal), &b)); s.S = (CGScal*)b;
-        FOTO_HIP_CHECK(hipMemcpyAsync(s.rho0, rho0, nxy * sizeof(double), hipMemcpyHostToDevice, c->s));
-        FOTO_HIP_CHECK(hipMemcpyAsync(s.rhoT, rhoT, nxy * sizeof(double), hipMemcpyHostToDevice, c->s));
+        FOTO_TRY(load_rho(c, s, src));
         FOTO_HIP_CHECK(launch_init_mu(s.g, s.rho0, s.rhoT, s.mu[0], s.mu[1], s.mu[2], s.q[0], s.q[1], s.q[2], c->s));
         if (c->o.cg_mode >= 1 && c->o.cg_mode <= 3) {
             s.spec.reset(new SpectralPlan());
@@ -1095,7 +1143,14 @@ static int outer_complete(foto_bb_ctx* c, double* crit, int* cg_iters, int* cg_i
     return 0;
 }
 
-static int flow(foto_bb_ctx* c, double* u, double* v, double* m) {
+// foto_bb_flow_dev's target: (u, v, m) leave through one export kernel instead of three downloads
+struct FlowDev {
+    void* out;
+    int dtype, layout;
+    hipStream_t user;
+};
+
+static int flow(foto_bb_ctx* c, double* u, double* v, double* m, const FlowDev* dv = nullptr) {
     if (!c->have_phi) {
         set_error("foto_bb_flow: no outer iteration has run yet (reference: UnboundLocalError for max_it=0)");
         return FOTO_ERR_STATE;
@@ -1134,6 +1189,10 @@ static int flow(foto_bb_ctx* c, double* u, double* v, double* m) {
             FOTO_HIP_CHECK(hipMemcpyAsync(u, s0->fu, nxy * sizeof(double), hipMemcpyDeviceToHost, c->s));
             FOTO_HIP_CHECK(hipMemcpyAsync(v, s0->fv, nxy * sizeof(double), hipMemcpyDeviceToHost, c->s));
             FOTO_HIP_CHECK(hipMemcpyAsync(m, s0->fm, nxy * sizeof(double), hipMemcpyDeviceToHost, c->s));
+        }
+        if (dv) {   // (the caller's earlier work on `out` first; the trajectories above did not touch it)
+            FOTO_TRY(c->link.enter(dv->user, c->s));
+            FOTO_HIP_CHECK(launch_export(nxy, s0->fu, s0->fv, s0->fm, dv->out, dv->dtype, dv->layout, c->s));
         }
     }
     FOTO_HIP_CHECK(hipEventRecord(c->fl[1], c->s));
@@ -1230,12 +1289,23 @@ static int check_grid(int Nt, int Nx, int Ny) {
     return 0;
 }
 
-int foto_bb_create(const double* rho0, const double* rhoT, int Nt, int Nx, int Ny, double r, double reg_epsilon,
-                   const foto_bb_opts* opts, foto_bb_ctx** out) {
-    if (!rho0 || !rhoT || !out) { set_error("null argument"); return FOTO_ERR_ARG; }
+// foto_bb_create and foto_bb_create_dev: the same context from either source of the densities
+static int bb_create(const RhoSrc& src, int Nt, int Nx, int Ny, double r, double reg_epsilon, const foto_bb_opts* opts,
+                     foto_bb_ctx** out) {
     FOTO_TRY(check_grid(Nt, Nx, Ny));
     foto_bb_opts o;
     if (opts) o = *opts; else foto_bb_opts_default(&o);
+    if (src.i0) {
+        if (o.world > 1) {
+            set_error("foto_bb_create_dev: device buffers are not supported on RCCL-sharded contexts (world = %d)", o.world);
+            return FOTO_ERR_STATE;
+        }
+        // the images must be device memory of the context's device -- before anything is enqueued
+        int dev = o.device;
+        if (dev < 0) FOTO_HIP_CHECK(hipGetDevice(&dev));
+        FOTO_TRY(image_dev_check(src.i0, Nx, Ny, dev, "foto_bb_create_dev (f0)"));
+        FOTO_TRY(image_dev_check(src.iT, Nx, Ny, dev, "foto_bb_create_dev (f1)"));
+    }
     if (o.world < 1 || o.rank < 0 || o.rank >= o.world) { set_error("bad rank/world"); return FOTO_ERR_ARG; }
     if (o.world > 1 && o.virtual_ranks > 1) { set_error("virtual_ranks requires world == 1"); return FOTO_ERR_ARG; }
     if (o.world > 1 && !o.nccl_id) { set_error("world > 1 needs nccl_id"); return FOTO_ERR_ARG; }
@@ -1259,9 +1329,40 @@ int foto_bb_create(const double* rho0, const double* rhoT, int Nt, int Nx, int N
     c->rccl = o.world > 1;
     c->W = c->rccl ? o.world : std::max(1, o.virtual_ranks);
     c->kt.on = o.timing != 0;
-    int rc = ctx_init(c.get(), rho0, rhoT);
+    int rc = ctx_init(c.get(), src);
     if (rc < 0) return rc;
     *out = c.release();
+    return 0;
+}
+
+int foto_bb_create(const double* rho0, const double* rhoT, int Nt, int Nx, int Ny, double r, double reg_epsilon,
+                   const foto_bb_opts* opts, foto_bb_ctx** out) {
+    if (!rho0 || !rhoT || !out) { set_error("null argument"); return FOTO_ERR_ARG; }
+    RhoSrc src;
+    src.h0 = rho0;
+    src.hT = rhoT;
+    return bb_create(src, Nt, Nx, Ny, r, reg_epsilon, opts, out);
+}
+
+int foto_bb_create_dev(const foto_image* f0, const foto_image* f1, int normalize, void* stream, int Nt, int Nx, int Ny,
+                       double r, double reg_epsilon, const foto_bb_opts* opts, double* sums2_or_null,
+                       foto_bb_ctx** out) {
+    if (!f0 || !f1 || !out) { set_error("foto_bb_create_dev: null argument"); return FOTO_ERR_ARG; }
+    RhoSrc src;
+    src.i0 = f0;
+    src.iT = f1;
+    src.normalize = normalize != 0;
+    src.user = (hipStream_t)stream;
+    foto_bb_ctx* c = nullptr;
+    FOTO_TRY(bb_create(src, Nt, Nx, Ny, r, reg_epsilon, opts, &c));
+    std::unique_ptr<foto_bb_ctx> guard(c);
+    // (ctx_init ends with a stream synchronise: the inputs are read, the sums are on the host)
+    FOTO_TRY(c->link.leave(c->s, src.user));
+    if (sums2_or_null) {
+        sums2_or_null[0] = src.normalize ? c->hsum[0] : 1.0;
+        sums2_or_null[1] = src.normalize ? c->hsum[1] : 1.0;
+    }
+    *out = guard.release();
     return 0;
 }
 
@@ -1361,8 +1462,8 @@ static int iterate_loop(foto_bb_ctx* c, int max_iters, double tol, int use_stop_
 
 extern "C" {
 
-int foto_bb_reset(foto_bb_ctx* c, const double* rho0, const double* rhoT) {
-    if (!c || !rho0 || !rhoT) { set_error("null argument"); return FOTO_ERR_ARG; }
+// foto_bb_reset and foto_bb_reset_dev: the same reset from either source of the densities
+static int bb_reset(foto_bb_ctx* c, const RhoSrc& src) {
     if (c->in_iterate) {   // (from the iteration callback: the loop still owns the in-flight state)
         set_error("foto_bb_reset: called from foto_bb_iterate's callback");
         return FOTO_ERR_STATE;
@@ -1385,8 +1486,7 @@ int foto_bb_reset(foto_bb_ctx* c, const double* rho0, const double* rhoT) {
         FOTO_HIP_CHECK(hipMemsetAsync(s.gath, 0, sizeof(double) * 4 * c->W, c->s));
         FOTO_HIP_CHECK(hipMemsetAsync(s.rb.ticket, 0, sizeof(unsigned) * 64, c->s));
         FOTO_HIP_CHECK(hipMemsetAsync(s.S, 0, sizeof(CGScal), c->s));
-        FOTO_HIP_CHECK(hipMemcpyAsync(s.rho0, rho0, nxy * sizeof(double), hipMemcpyHostToDevice, c->s));
-        FOTO_HIP_CHECK(hipMemcpyAsync(s.rhoT, rhoT, nxy * sizeof(double), hipMemcpyHostToDevice, c->s));
+        FOTO_TRY(load_rho(c, s, src));
         FOTO_HIP_CHECK(launch_init_mu(s.g, s.rho0, s.rhoT, s.mu[0], s.mu[1], s.mu[2], s.q[0], s.q[1], s.q[2], c->s));
         if (s.spec) FOTO_TRY(s.spec->reset(c->s));
     }
@@ -1403,6 +1503,63 @@ int foto_bb_reset(foto_bb_ctx* c, const double* rho0, const double* rhoT) {
     c->hpar = 0;
     FOTO_HIP_CHECK(hipStreamSynchronize(c->s));
     return 0;
+}
+
+int foto_bb_reset(foto_bb_ctx* c, const double* rho0, const double* rhoT) {
+    if (!c || !rho0 || !rhoT) { set_error("null argument"); return FOTO_ERR_ARG; }
+    RhoSrc src;
+    src.h0 = rho0;
+    src.hT = rhoT;
+    return bb_reset(c, src);
+}
+
+int foto_bb_reset_dev(foto_bb_ctx* c, const foto_image* f0, const foto_image* f1, int normalize, void* stream,
+                      double* sums2_or_null) {
+    if (!c || !f0 || !f1) { set_error("foto_bb_reset_dev: null argument"); return FOTO_ERR_ARG; }
+    if (c->rccl) {
+        set_error("foto_bb_reset_dev: device buffers are not supported on RCCL-sharded contexts");
+        return FOTO_ERR_STATE;
+    }
+    // (argument errors leave the context as it was: nothing is drained, reset or enqueued yet)
+    const int dev = stream_device(c->s);
+    FOTO_TRY(image_dev_check(f0, c->Nx, c->Ny, dev, "foto_bb_reset_dev (f0)"));
+    FOTO_TRY(image_dev_check(f1, c->Nx, c->Ny, dev, "foto_bb_reset_dev (f1)"));
+    RhoSrc src;
+    src.i0 = f0;
+    src.iT = f1;
+    src.normalize = normalize != 0;
+    src.user = (hipStream_t)stream;
+    FOTO_TRY(bb_reset(c, src));
+    FOTO_TRY(c->link.leave(c->s, src.user));
+    if (sums2_or_null) {
+        sums2_or_null[0] = src.normalize ? c->hsum[0] : 1.0;
+        sums2_or_null[1] = src.normalize ? c->hsum[1] : 1.0;
+    }
+    return 0;
+}
+
+int foto_bb_flow_dev(foto_bb_ctx* c, void* out, int dtype, int layout, void* stream) {
+    if (!c) { set_error("null ctx"); return FOTO_ERR_ARG; }
+    if (c->rccl) {
+        set_error("foto_bb_flow_dev: device buffers are not supported on RCCL-sharded contexts");
+        return FOTO_ERR_STATE;
+    }
+    if (c->broken) { set_error("foto_bb_flow_dev: a failed foto_bb_iterate left the context inconsistent; foto_bb_reset it"); return FOTO_ERR_STATE; }
+    if (!c->have_phi) {   // (before the output is looked at: the reference's UnboundLocalError)
+        set_error("foto_bb_flow_dev: no outer iteration has run yet");
+        return FOTO_ERR_STATE;
+    }
+    FOTO_TRY(export_check(out, dtype, layout, (int64_t)c->Nx * c->Ny, stream_device(c->s), "foto_bb_flow_dev"));
+    Completed k;
+    FOTO_TRY(completed_state(c, "foto_bb_flow_dev", &k));
+    Shard& s0 = *c->sh[0];
+    double* keep = s0.phi;
+    s0.phi = k.phi;
+    const FlowDev dv{out, dtype, layout, (hipStream_t)stream};
+    int rc = flow(c, nullptr, nullptr, nullptr, &dv);
+    s0.phi = keep;
+    if (rc >= 0) rc = c->link.leave(c->s, dv.user);
+    return rc;
 }
 
 int foto_bb_flow(foto_bb_ctx* c, double* u, double* v, double* m) {

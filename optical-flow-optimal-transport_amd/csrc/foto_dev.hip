@@ -1,0 +1,315 @@
+// Device-buffer interface (include/foto.h, "device buffers"): the strided image descriptor's
+// validation, the ingest kernels (uint8 / float32 / float64 strided image -> the solvers'
+// contiguous float64 frame), the export kernels (float64 fields -> float32 / float64, planar or
+// interleaved), the fixed-order frame sum of normalize = 1, and the small device-memory
+// utilities.  The entries that need a context's or plan's internals (foto_bb_*_dev,
+// foto_gn_plan_solve_dev, the evaluation *_dev calls) live next to their host twins and call the
+// launchers below.
+//
+// Built with -ffp-contract=off like every other unit: value = (double)pixel / divisor is one
+// IEEE division (numpy's img.astype(np.float64) / 255), never a multiply by a reciprocal, and
+// (float)x rounds to nearest even as np.float32(x) does.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "foto_internal.h"
+
+namespace foto {
+
+namespace {
+
+constexpr int SUM_MAX_BLOCKS = 2048;
+
+template <class T> struct Vec16;   // the 16-byte load of the vector path
+template <> struct Vec16<unsigned char> { typedef unsigned int type __attribute__((ext_vector_type(4))); };
+template <> struct Vec16<float> { typedef float type __attribute__((ext_vector_type(4))); };
+template <> struct Vec16<double> { typedef double type __attribute__((ext_vector_type(2))); };
+
+// One work item = one chunk of VE = 16 / sizeof(T) pixels of a row (cpr chunks per row).  VEC: the
+// rows are unit-stride and every row start is 16-byte aligned -- a full chunk is one 16-byte
+// load (read once: non-temporal); the row tail, and every chunk of the scalar kernel, go pixel
+// by pixel through the strides.  Consecutive lanes take consecutive chunks of a row, so both
+// the loads and the float64 stores of a wave cover one contiguous span.
+template <class T, bool VEC>
+__global__ __launch_bounds__(NT) void k_ingest(const T* __restrict__ src, int64_t sy, int64_t sx, int w, int h,
+                                               int cpr, double divisor, double* __restrict__ dst) {
+    constexpr int VE = 16 / (int)sizeof(T);
+    const int64_t nchunk = (int64_t)h * cpr;
+    for (int64_t t = (int64_t)blockIdx.x * NT + threadIdx.x; t < nchunk; t += (int64_t)gridDim.x * NT) {
+        const int row = (int)(t / cpr);
+        const int c0 = (int)(t - (int64_t)row * cpr) * VE;
+        const T* rp = src + (int64_t)row * sy;
+        double* out = dst + (int64_t)row * w + c0;
+        if (VEC && c0 + VE <= w) {
+            typedef typename Vec16<T>::type V;
+            const V q = __builtin_nontemporal_load((const V*)(rp + c0));
+            T e[VE];
+            __builtin_memcpy(e, &q, 16);
+#pragma unroll
+            for (int k = 0; k < VE; ++k) out[k] = (double)e[k] / divisor;
+        } else {
+            const int ce = c0 + VE < w ? c0 + VE : w;
+            for (int c = c0; c < ce; ++c) out[c - c0] = (double)rp[(int64_t)c * sx] / divisor;
+        }
+    }
+}
+
+// fixed-order sum: a grid that depends on n only, per-thread strided partial sums, the block
+// tree of ev_block_sum (foto_eval.hip), then one block over the block partials
+__device__ __forceinline__ double block_sum(double v, double* sh /* NT */) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int st = NT / 2; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+__global__ __launch_bounds__(NT) void k_sum_partial(int64_t n, const double* __restrict__ x,
+                                                    double* __restrict__ part) {
+    __shared__ double sh[NT];
+    double acc = 0.0;
+    for (int64_t p = (int64_t)blockIdx.x * NT + threadIdx.x; p < n; p += (int64_t)gridDim.x * NT) acc += x[p];
+    const double s = block_sum(acc, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(NT) void k_sum_final(int nb, const double* __restrict__ part, double* __restrict__ tot) {
+    __shared__ double sh[NT];
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < nb; b += NT) acc += part[b];
+    const double s = block_sum(acc, sh);
+    if (threadIdx.x == 0) tot[0] = s;
+}
+
+__global__ __launch_bounds__(NT) void k_div_scalar(int64_t n, double* __restrict__ x, const double* __restrict__ S) {
+    const double d = S[0];
+    for (int64_t p = (int64_t)blockIdx.x * NT + threadIdx.x; p < n; p += (int64_t)gridDim.x * NT) x[p] = x[p] / d;
+}
+
+// LAYOUT 0: planar [3][n] = a, b, c; 1: interleaved [n][2] = (a, b)
+template <class T, int LAYOUT>
+__global__ __launch_bounds__(NT) void k_export(int64_t n, const double* __restrict__ a, const double* __restrict__ b,
+                                               const double* __restrict__ c, T* __restrict__ out) {
+    for (int64_t p = (int64_t)blockIdx.x * NT + threadIdx.x; p < n; p += (int64_t)gridDim.x * NT) {
+        if (LAYOUT == 0) {
+            out[p] = (T)a[p];
+            out[n + p] = (T)b[p];
+            out[2 * n + p] = (T)c[p];
+        } else {
+            out[2 * p] = (T)a[p];
+            out[2 * p + 1] = (T)b[p];
+        }
+    }
+}
+
+int stream_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(flat_blocks(n), 1 << 16)); }
+
+size_t dtype_size(int dtype) { return dtype == FOTO_U8 ? 1 : dtype == FOTO_F32 ? 4 : 8; }
+
+template <class T>
+hipError_t ingest_t(const foto_image& im, int w, int h, double* dst, hipStream_t s) {
+    constexpr int VE = 16 / (int)sizeof(T);
+    const int cpr = (w + VE - 1) / VE;
+    const T* src = (const T*)im.data;
+    const bool vec = im.stride_x == 1 && ((uintptr_t)im.data % 16) == 0 &&
+                     (((uint64_t)im.stride_y * sizeof(T)) % 16) == 0;
+    const int nb = stream_blocks((int64_t)h * cpr);
+    if (vec) k_ingest<T, true><<<nb, NT, 0, s>>>(src, im.stride_y, im.stride_x, w, h, cpr, im.divisor, dst);
+    else k_ingest<T, false><<<nb, NT, 0, s>>>(src, im.stride_y, im.stride_x, w, h, cpr, im.divisor, dst);
+    return hipGetLastError();
+}
+
+template <class T>
+hipError_t export_t(int64_t n, const double* a, const double* b, const double* c, void* out, int layout,
+                    hipStream_t s) {
+    const int nb = stream_blocks(n);
+    if (layout == 0) k_export<T, 0><<<nb, NT, 0, s>>>(n, a, b, c, (T*)out);
+    else k_export<T, 1><<<nb, NT, 0, s>>>(n, a, b, c, (T*)out);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+// ----------------------------------------------------------------------------- validation
+
+int image_check(const foto_image* im, int w, int h, const char* who) {
+    if (!im) { set_error("%s: null image descriptor", who); return FOTO_ERR_ARG; }
+    if (w < 1 || h < 1) { set_error("%s: w = %d, h = %d: both must be >= 1", who, w, h); return FOTO_ERR_ARG; }
+    if (!im->data) { set_error("%s: image data is null", who); return FOTO_ERR_ARG; }
+    if (im->dtype < FOTO_U8 || im->dtype > FOTO_F64) {
+        set_error("%s: dtype %d is not FOTO_U8 / FOTO_F32 / FOTO_F64", who, im->dtype);
+        return FOTO_ERR_ARG;
+    }
+    if (im->stride_x <= 0 || im->stride_y <= 0) {
+        set_error("%s: strides (%lld, %lld) must both be > 0 (in elements)", who, (long long)im->stride_y,
+                  (long long)im->stride_x);
+        return FOTO_ERR_ARG;
+    }
+    if (!(im->divisor != 0.0) || !std::isfinite(im->divisor)) {
+        set_error("%s: divisor %g must be finite and non-zero", who, im->divisor);
+        return FOTO_ERR_ARG;
+    }
+    if ((uintptr_t)im->data % dtype_size(im->dtype) != 0) {
+        set_error("%s: data %p is not aligned to its %zu-byte element", who, im->data, dtype_size(im->dtype));
+        return FOTO_ERR_ARG;
+    }
+    // the w x h pixels must be distinct elements: the lines along the minor stride may not
+    // reach into each other
+    const bool x_minor = im->stride_x <= im->stride_y;
+    const int64_t major = x_minor ? im->stride_y : im->stride_x, minor = x_minor ? im->stride_x : im->stride_y;
+    const int64_t len = x_minor ? w : h, lines = x_minor ? h : w;
+    if (lines > 1 && major < (len - 1) * minor + 1) {
+        set_error("%s: strides (%lld, %lld) make the %s of a %d x %d image overlap", who, (long long)im->stride_y,
+                  (long long)im->stride_x, x_minor ? "rows" : "columns", w, h);
+        return FOTO_ERR_ARG;
+    }
+    return 0;
+}
+
+// [p, p + bytes) must be device memory of `device`: hipPointerGetAttributes knows every
+// allocation of the runtime, a pointer it does not know (plain host memory) is an error there
+int dev_ptr_check(const void* p, size_t bytes, int device, const char* who, const char* what) {
+    if (!p) { set_error("%s: %s is null", who, what); return FOTO_ERR_ARG; }
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();   // (the lookup failure is this call's answer, not a sticky error)
+        set_error("%s: %s %p is not memory of the HIP runtime (%s); a device pointer is required", who, what, p,
+                  hipGetErrorString(e));
+        return FOTO_ERR_ARG;
+    }
+    if (at.type != hipMemoryTypeDevice) {
+        set_error("%s: %s %p is not device memory (memory type %d)", who, what, p, (int)at.type);
+        return FOTO_ERR_ARG;
+    }
+    if (at.device != device) {
+        set_error("%s: %s %p lives on device %d, the solver on device %d", who, what, p, at.device, device);
+        return FOTO_ERR_ARG;
+    }
+    // the extent, where the runtime can tell the allocation's range
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) == hipSuccess && base && size) {
+        const uintptr_t lo = (uintptr_t)base, hi = lo + size, a = (uintptr_t)p;
+        if (a < lo || a + bytes > hi) {
+            set_error("%s: %s %p + %zu bytes runs past its allocation [%p, +%zu)", who, what, p, bytes, (void*)base, size);
+            return FOTO_ERR_ARG;
+        }
+    } else {
+        (void)hipGetLastError();
+    }
+    return 0;
+}
+
+int image_dev_check(const foto_image* im, int w, int h, int device, const char* who) {
+    FOTO_TRY(image_check(im, w, h, who));
+    const size_t last = (size_t)(h - 1) * (size_t)im->stride_y + (size_t)(w - 1) * (size_t)im->stride_x;
+    return dev_ptr_check(im->data, (last + 1) * dtype_size(im->dtype), device, who, "image data");
+}
+
+int export_check(const void* out, int dtype, int layout, int64_t n, int device, const char* who) {
+    if (dtype != FOTO_F32 && dtype != FOTO_F64) {
+        set_error("%s: output dtype %d is not FOTO_F32 / FOTO_F64", who, dtype);
+        return FOTO_ERR_ARG;
+    }
+    if (layout != 0 && layout != 1) {
+        set_error("%s: layout %d is not 0 (planar u, v, m) / 1 (interleaved (u, v))", who, layout);
+        return FOTO_ERR_ARG;
+    }
+    if (out && (uintptr_t)out % dtype_size(dtype) != 0) {
+        set_error("%s: out %p is not aligned to its %zu-byte element", who, out, dtype_size(dtype));
+        return FOTO_ERR_ARG;
+    }
+    return dev_ptr_check(out, (size_t)n * (layout == 0 ? 3 : 2) * dtype_size(dtype), device, who, "out");
+}
+
+// ----------------------------------------------------------------------------- launchers
+
+hipError_t launch_ingest(const foto_image& im, int w, int h, double* dst, hipStream_t s) {
+    switch (im.dtype) {
+        case FOTO_U8: return ingest_t<unsigned char>(im, w, h, dst, s);
+        case FOTO_F32: return ingest_t<float>(im, w, h, dst, s);
+        case FOTO_F64: return ingest_t<double>(im, w, h, dst, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+int sum_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(flat_blocks(n), SUM_MAX_BLOCKS)); }
+
+hipError_t launch_sum(int64_t n, const double* x, double* part, double* tot, hipStream_t s) {
+    const int nb = sum_blocks(n);
+    k_sum_partial<<<nb, NT, 0, s>>>(n, x, part);
+    k_sum_final<<<1, NT, 0, s>>>(nb, part, tot);
+    return hipGetLastError();
+}
+
+hipError_t launch_div_scalar(int64_t n, double* x, const double* S, hipStream_t s) {
+    k_div_scalar<<<stream_blocks(n), NT, 0, s>>>(n, x, S);
+    return hipGetLastError();
+}
+
+hipError_t launch_export(int64_t n, const double* a, const double* b, const double* c, void* out, int dtype,
+                         int layout, hipStream_t s) {
+    if (dtype == FOTO_F32) return export_t<float>(n, a, b, c, out, layout, s);
+    if (dtype == FOTO_F64) return export_t<double>(n, a, b, c, out, layout, s);
+    return hipErrorInvalidValue;
+}
+
+// ----------------------------------------------------------------------------- stream contract
+
+int StreamLink::enter(hipStream_t user, hipStream_t own) {
+    if (!in) FOTO_HIP_CHECK(hipEventCreateWithFlags(&in, hipEventDisableTiming));
+    if (!out) FOTO_HIP_CHECK(hipEventCreateWithFlags(&out, hipEventDisableTiming));
+    FOTO_HIP_CHECK(hipEventRecord(in, user));
+    FOTO_HIP_CHECK(hipStreamWaitEvent(own, in, 0));
+    return 0;
+}
+
+int StreamLink::leave(hipStream_t own, hipStream_t user) {
+    FOTO_HIP_CHECK(hipEventRecord(out, own));
+    FOTO_HIP_CHECK(hipStreamWaitEvent(user, out, 0));
+    return 0;
+}
+
+StreamLink::~StreamLink() {
+    if (in) (void)hipEventDestroy(in);
+    if (out) (void)hipEventDestroy(out);
+}
+
+}  // namespace foto
+
+using namespace foto;
+
+extern "C" {
+
+int foto_image_check(const foto_image* im, int w, int h) { return image_check(im, w, h, "foto_image_check"); }
+
+int foto_dev_malloc(size_t bytes, void** out) {
+    if (!out) { set_error("foto_dev_malloc: null argument"); return FOTO_ERR_ARG; }
+    *out = nullptr;
+    FOTO_HIP_CHECK(hipMalloc(out, std::max<size_t>(bytes, 1)));
+    return 0;
+}
+
+int foto_dev_free(void* p) {
+    if (p) FOTO_HIP_CHECK(hipFree(p));
+    return 0;
+}
+
+int foto_dev_memcpy(void* dst, const void* src, size_t bytes, int kind) {
+    if (kind < 0 || kind > 2) { set_error("foto_dev_memcpy: kind %d is not 0 (H2D) / 1 (D2H) / 2 (D2D)", kind); return FOTO_ERR_ARG; }
+    if (bytes == 0) return 0;
+    if (!dst || !src) { set_error("foto_dev_memcpy: null pointer"); return FOTO_ERR_ARG; }
+    static const hipMemcpyKind kinds[3] = {hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice};
+    FOTO_HIP_CHECK(hipMemcpy(dst, src, bytes, kinds[kind]));
+    return 0;
+}
+
+}  // extern "C"
+
+static_assert(sizeof(foto_image) == 40, "foto_image layout");

@@ -111,6 +111,7 @@ constexpr int EV_SLOTS = 8;
 struct EvSlots {
     void* p[EV_SLOTS] = {};
     size_t cap[EV_SLOTS] = {};
+    StreamLink* link = nullptr;   // the *_dev entries: the caller's stream <-> the call's (kept, like the slots)
 };
 std::mutex ev_mu;
 std::vector<EvSlots> ev_dev;   // per device (a slot is only valid on the device it was made on)
@@ -120,6 +121,8 @@ struct EvScope {
     std::unique_lock<std::mutex> lk{ev_mu};
     EvSlots* sl = nullptr;
     int used = 0;
+    bool dev_in = false;   // the *_dev entries: inputs are device arrays already, nothing to upload
+    int device = -1;
     int init() {
         FOTO_TRY(stream_acquire(&s));
         const int dev = stream_device(s);
@@ -129,7 +132,25 @@ struct EvScope {
         }
         if ((int)ev_dev.size() <= dev) ev_dev.resize(dev + 1);
         sl = &ev_dev[dev];
+        device = dev;
         return 0;
+    }
+    // a *_dev call (after init and the pointer checks): its inputs are used in place once the
+    // caller's stream has produced them
+    int init_dev(hipStream_t user) {
+        dev_in = true;
+        if (!sl->link) sl->link = new StreamLink();
+        return sl->link->enter(user, s);
+    }
+    int leave(hipStream_t user) { return sl->link->leave(s, user); }
+    // n doubles at p are device memory of this call's device (nullptr: an absent input)
+    int check(const double* p, size_t n, const char* who, const char* what) {
+        if (!p) return 0;
+        if ((uintptr_t)p % sizeof(double) != 0) {
+            set_error("%s: %s %p is not aligned to 8 bytes", who, what, (const void*)p);
+            return FOTO_ERR_ARG;
+        }
+        return dev_ptr_check(p, n * sizeof(double), device, who, what);
     }
     int slot(size_t n, double** d) {
         const size_t bytes = std::max<size_t>(n, 1) * sizeof(double);
@@ -152,6 +173,7 @@ struct EvScope {
     }
     int up(const double* h, size_t n, double** d) {
         if (!h) { *d = nullptr; return 0; }
+        if (dev_in) { *d = const_cast<double*>(h); return 0; }
         FOTO_TRY(slot(n, d));
         FOTO_HIP_CHECK(hipMemcpyAsync(*d, h, n * sizeof(double), hipMemcpyHostToDevice, s));
         return 0;
@@ -166,15 +188,25 @@ struct EvScope {
 int ev_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + EV_NT - 1) / EV_NT, 2048)); }
 
 // the two passes; out: mean EE, std EE, mean AE, std AE, IE (any of the inputs may be absent)
+// (on_dev: the six inputs are device arrays, used in place -- the *_dev entries)
 int ev_errors(const double* u, const double* v, const double* uG, const double* vG, const double* I,
-              const double* IG, int w, int h, double* out5) {
+              const double* IG, int w, int h, double* out5, bool on_dev = false, hipStream_t user = nullptr,
+              const char* who = "") {
     if (w < 1 || h < 1) {
         set_error("flow errors: w, h must be >= 1");
         return FOTO_ERR_ARG;
     }
     const int64_t n = (int64_t)w * h;
     EvScope S;
-    FOTO_TRY(S.init());
+    if (on_dev) {
+        FOTO_TRY(S.init());   // (the pointers are checked before anything is enqueued or waited on)
+        const double* in[6] = {u, v, uG, vG, I, IG};
+        static const char* const names[6] = {"u", "v", "uGT", "vGT", "I", "IGT"};
+        for (int k = 0; k < 6; ++k) FOTO_TRY(S.check(in[k], (size_t)n, who, names[k]));
+        FOTO_TRY(S.init_dev(user));
+    } else {
+        FOTO_TRY(S.init());
+    }
     double *du, *dv, *duG, *dvG, *dI, *dIG, *part, *tot;
     FOTO_TRY(S.up(u, n, &du));
     FOTO_TRY(S.up(v, n, &dv));
@@ -204,6 +236,7 @@ int ev_errors(const double* u, const double* v, const double* uG, const double* 
         out5[3] = sqrt(h1[2] / h0[3]);
     }
     if (dI) out5[4] = sqrt(h0[4] / ((double)w * h));
+    if (on_dev) FOTO_TRY(S.leave(user));   // (the inputs may be overwritten by what the caller enqueues next)
     return 0;
 }
 
@@ -232,6 +265,54 @@ int foto_warp(const double* f1, const double* u, const double* v, const double* 
     FOTO_HIP_CHECK(hipGetLastError());
     FOTO_HIP_CHECK(hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, S.s));
     FOTO_HIP_CHECK(hipStreamSynchronize(S.s));
+    return 0;
+}
+
+int foto_warp_dev(const double* f1, const double* u, const double* v, const double* m, int w, int h, double* out,
+                  void* stream) {
+    if (!f1 || !u || !v || !out || w < 1 || h < 1) {
+        set_error("foto_warp_dev: null buffer or w, h < 1");
+        return FOTO_ERR_ARG;
+    }
+    const size_t n = (size_t)w * h;
+    EvScope S;
+    FOTO_TRY(S.init());
+    FOTO_TRY(S.check(f1, n, "foto_warp_dev", "f1"));
+    FOTO_TRY(S.check(u, n, "foto_warp_dev", "u"));
+    FOTO_TRY(S.check(v, n, "foto_warp_dev", "v"));
+    FOTO_TRY(S.check(m, n, "foto_warp_dev", "m"));
+    FOTO_TRY(S.check(out, n, "foto_warp_dev", "out"));
+    if (out == f1 || out == u || out == v || out == m) {
+        set_error("foto_warp_dev: out may not alias an input (the warp gathers)");
+        return FOTO_ERR_ARG;
+    }
+    FOTO_TRY(S.init_dev((hipStream_t)stream));
+    k_warp<<<ev_blocks((int64_t)n), EV_NT, 0, S.s>>>(f1, m, u, v, w, h, out);
+    FOTO_HIP_CHECK(hipGetLastError());
+    return S.leave((hipStream_t)stream);
+}
+
+int foto_flow_errors_dev(const double* u, const double* v, const double* uGT, const double* vGT, int w, int h,
+                         double* out4, void* stream) {
+    if (!u || !v || !uGT || !vGT || !out4) {
+        set_error("foto_flow_errors_dev: null buffer");
+        return FOTO_ERR_ARG;
+    }
+    double r[5];
+    FOTO_TRY(ev_errors(u, v, uGT, vGT, nullptr, nullptr, w, h, r, true, (hipStream_t)stream, "foto_flow_errors_dev"));
+    for (int k = 0; k < 4; ++k) out4[k] = r[k];
+    return 0;
+}
+
+int foto_intensity_error_dev(const double* I, const double* IGT, int w, int h, double* ie, void* stream) {
+    if (!I || !IGT || !ie) {
+        set_error("foto_intensity_error_dev: null buffer");
+        return FOTO_ERR_ARG;
+    }
+    double r[5];
+    FOTO_TRY(ev_errors(nullptr, nullptr, nullptr, nullptr, I, IGT, w, h, r, true, (hipStream_t)stream,
+                       "foto_intensity_error_dev"));
+    *ie = r[4];
     return 0;
 }
 

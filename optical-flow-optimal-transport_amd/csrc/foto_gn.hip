@@ -1971,6 +1971,7 @@ struct foto_gn_plan {
     hipEvent_t dl_ev[3] = {nullptr, nullptr, nullptr};   // u, v, m downloaded (the copy-out of one overlaps the next)
     std::unique_ptr<HostPool> pool;                        // host copies (made with the staging)
     int last_its = 0;
+    StreamLink link;                 // foto_gn_plan_solve_dev: the caller's stream <-> s
     double last[4] = {0, 0, 0, 0};   // ms setup+upload, ms PCG, iterations, iterations launched
     bool tail = false;               // small levels in one block (k_mg_tail, FOTO_MG_TAIL=1; measured slower)
 
@@ -2296,14 +2297,28 @@ static int gn_staging(foto_gn_plan* P) {
     return 0;
 }
 
+// foto_gn_plan_solve_dev's frames and target: ingest straight into d1 / d2, export straight from
+// x -- no pinned staging, no host pool; everything between the two is the host entry's code
+struct GnDev {
+    const foto_image* f1;
+    const foto_image* f2;
+    void* out;
+    int dtype, layout;
+    hipStream_t user;
+};
+
 static int gn_plan_solve(foto_gn_plan* P, const double* f1, const double* f2, double* u, double* v, double* m,
-                         int* iterations) {
+                         int* iterations, const GnDev* dv = nullptr) {
     const int w = P->w, h = P->h;
     const int64_t n = (int64_t)w * h;
     hipStream_t s = P->s;
     GnTrace tr;
+    if (dv) FOTO_TRY(P->link.enter(dv->user, s));   // (before the first read of a frame)
     FOTO_HIP_CHECK(hipEventRecord(P->ev[0], s));
-    if (P->hbuf) {
+    if (dv) {
+        FOTO_HIP_CHECK(launch_ingest(*dv->f1, w, h, P->d1, s));
+        FOTO_HIP_CHECK(launch_ingest(*dv->f2, w, h, P->d2, s));
+    } else if (P->hbuf) {
         double* hb = P->hbuf;
         pool_memcpy(P->pool.get(), hb, f1, n * sizeof(double));
         FOTO_HIP_CHECK(hipMemcpyAsync(P->d1, hb, n * sizeof(double), hipMemcpyHostToDevice, s));
@@ -2371,7 +2386,7 @@ static int gn_plan_solve(foto_gn_plan* P, const double* f1, const double* f2, do
         for (; j + G <= chunk; j += G, k += G) FOTO_HIP_CHECK(hipGraphLaunch(P->gexec, s));
         for (; j < chunk; ++j, ++k) FOTO_TRY(gn_iteration(P, k & 1));   // (the remainder, outside the graph)
         FOTO_HIP_CHECK(hipMemcpyAsync(P->hS, P->dS, sizeof(CGScal), hipMemcpyDeviceToHost, s));
-        if (k == chunk) FOTO_TRY(gn_staging(P));   // while the first iterations run
+        if (k == chunk && !dv) FOTO_TRY(gn_staging(P));   // while the first iterations run
         FOTO_HIP_CHECK(hipStreamSynchronize(s));
         if (P->hS->done) { done = true; break; }
     }
@@ -2383,18 +2398,23 @@ static int gn_plan_solve(foto_gn_plan* P, const double* f1, const double* f2, do
     }
     // the solution straight into the mapped pinned staging by a kernel: the first large
     // device-to-host hipMemcpy of a process took 8.5-14.8 ms at 640x480 (0.15-0.4 ms later)
-    FOTO_TRY(gn_staging(P));   // (maxiter 0: no iteration ran)
-    // u, v, m one after the other, each copied out while the next crosses PCIe
-    double* const outs[3] = {u, v, m};
-    for (int c = 0; c < 3; ++c) {
-        k_gn_download<<<flat_blocks(n), NT, 0, s>>>(n, P->x + c * n, P->hbuf_dev + (2 + c) * n);
-        FOTO_HIP_CHECK(hipGetLastError());
-        FOTO_HIP_CHECK(hipEventRecord(P->dl_ev[c], s));
-    }
-    for (int c = 0; c < 3; ++c) {
-        FOTO_HIP_CHECK(hipEventSynchronize(P->dl_ev[c]));
-        if (c == 0) tr.mark("solve: download u");
-        pool_memcpy(P->pool.get(), outs[c], P->hbuf + (2 + c) * n, n * sizeof(double));
+    if (dv) {
+        FOTO_HIP_CHECK(launch_export(n, P->x, P->x + n, P->x + 2 * n, dv->out, dv->dtype, dv->layout, s));
+        FOTO_TRY(P->link.leave(s, dv->user));
+    } else {
+        FOTO_TRY(gn_staging(P));   // (maxiter 0: no iteration ran)
+        // u, v, m one after the other, each copied out while the next crosses PCIe
+        double* const outs[3] = {u, v, m};
+        for (int c = 0; c < 3; ++c) {
+            k_gn_download<<<flat_blocks(n), NT, 0, s>>>(n, P->x + c * n, P->hbuf_dev + (2 + c) * n);
+            FOTO_HIP_CHECK(hipGetLastError());
+            FOTO_HIP_CHECK(hipEventRecord(P->dl_ev[c], s));
+        }
+        for (int c = 0; c < 3; ++c) {
+            FOTO_HIP_CHECK(hipEventSynchronize(P->dl_ev[c]));
+            if (c == 0) tr.mark("solve: download u");
+            pool_memcpy(P->pool.get(), outs[c], P->hbuf + (2 + c) * n, n * sizeof(double));
+        }
     }
     tr.mark("solve: copy out");
     const int its = done ? P->hS->iters : maxiter;
@@ -2430,6 +2450,17 @@ int foto_gn_plan_solve(foto_gn_plan* p, const double* f1, const double* f2, doub
                        int* iterations) {
     if (!p || !f1 || !f2 || !u || !v || !m) { set_error("null argument"); return FOTO_ERR_ARG; }
     return gn_plan_solve(p, f1, f2, u, v, m, iterations);
+}
+
+int foto_gn_plan_solve_dev(foto_gn_plan* p, const foto_image* f1, const foto_image* f2, void* out, int dtype,
+                           int layout, void* stream, int* iterations) {
+    if (!p || !f1 || !f2) { set_error("foto_gn_plan_solve_dev: null argument"); return FOTO_ERR_ARG; }
+    // device memory of the plan's device, checked before anything is enqueued
+    FOTO_TRY(image_dev_check(f1, p->w, p->h, p->device, "foto_gn_plan_solve_dev (f1)"));
+    FOTO_TRY(image_dev_check(f2, p->w, p->h, p->device, "foto_gn_plan_solve_dev (f2)"));
+    FOTO_TRY(export_check(out, dtype, layout, (int64_t)p->w * p->h, p->device, "foto_gn_plan_solve_dev"));
+    const GnDev dv{f1, f2, out, dtype, layout, (hipStream_t)stream};
+    return gn_plan_solve(p, nullptr, nullptr, nullptr, nullptr, nullptr, iterations, &dv);
 }
 
 int foto_gn_plan_timing(const foto_gn_plan* p, double* out4) {

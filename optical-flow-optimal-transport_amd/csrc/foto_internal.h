@@ -274,4 +274,35 @@ hipError_t launch_gn_pcg_upd(int w, int h, int k, const double* fx, const double
                              double alpha, double lam, const double* p, double* x, double* r, double* z,
                              CGScal* S, RedBuf rb, const double* gath_pq, double* gath_rz, hipStream_t s);
 
+// ----------------------------------------------------------------------------- device buffers
+// (foto_dev.hip; the *_dev entries of include/foto.h)
+// foto_image_check's rules; `who` prefixes the message
+int image_check(const foto_image* im, int w, int h, const char* who);
+// image_check, then hipPointerGetAttributes: the pixels must be device memory of `device`
+int image_dev_check(const foto_image* im, int w, int h, int device, const char* who);
+// [p, p + bytes) is device memory of `device`
+int dev_ptr_check(const void* p, size_t bytes, int device, const char* who, const char* what);
+// an export target: dtype F32 | F64, layout 0 | 1, n pixels, device memory of `device`
+int export_check(const void* out, int dtype, int layout, int64_t n, int device, const char* who);
+// dst[row * w + col] = (double)pixel(row, col) / divisor
+hipError_t launch_ingest(const foto_image& im, int w, int h, double* dst, hipStream_t s);
+// tot[0] = sum of x[0..n) in a fixed order; part holds sum_blocks(n) doubles
+int sum_blocks(int64_t n);
+hipError_t launch_sum(int64_t n, const double* x, double* part, double* tot, hipStream_t s);
+hipError_t launch_div_scalar(int64_t n, double* x, const double* S, hipStream_t s);   // x /= S[0]
+// layout 0: out[3][n] = a, b, c; 1: out[n][2] = (a, b); dtype FOTO_F32 | FOTO_F64
+hipError_t launch_export(int64_t n, const double* a, const double* b, const double* c, void* out, int dtype,
+                         int layout, hipStream_t s);
+
+// The stream contract of every *_dev call: libfoto's streams are non-blocking, so the caller's
+// stream (NULL: the legacy null stream) and the own one are ordered by two events, made once per
+// context / plan.  enter: what `user` has enqueued happens before what `own` runs next;
+// leave: what `own` has enqueued happens before what `user` runs next.
+struct StreamLink {
+    hipEvent_t in = nullptr, out = nullptr;
+    int enter(hipStream_t user, hipStream_t own);
+    int leave(hipStream_t own, hipStream_t user);
+    ~StreamLink();
+};
+
 }  // namespace foto

@@ -92,6 +92,20 @@ class GNStats(ctypes.Structure):
     ]
 
 
+FOTO_U8, FOTO_F32, FOTO_F64 = 0, 1, 2
+
+
+class Image(ctypes.Structure):
+    """foto_image (include/foto.h): a strided device view of one grey-scale frame."""
+    _fields_ = [
+        ("data", ctypes.c_void_p),
+        ("dtype", ctypes.c_int),
+        ("stride_y", ctypes.c_int64),
+        ("stride_x", ctypes.c_int64),
+        ("divisor", ctypes.c_double),
+    ]
+
+
 ITER_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int)
 
 _D = ctypes.POINTER(ctypes.c_double)
@@ -149,6 +163,20 @@ SIGNATURES = {
     "foto_warp": (_I, [_D, _D, _D, _D, _I, _I, _D]),
     "foto_flow_errors": (_I, [_D, _D, _D, _D, _I, _I, _D]),
     "foto_intensity_error": (_I, [_D, _D, _I, _I, _D]),
+    # device buffers (device pointers travel as void*)
+    "foto_image_check": (_I, [ctypes.POINTER(Image), _I, _I]),
+    "foto_bb_create_dev": (_I, [ctypes.POINTER(Image), ctypes.POINTER(Image), _I, _P, _I, _I, _I, _Dbl, _Dbl,
+                                ctypes.POINTER(BBOpts), _D, ctypes.POINTER(_P)]),
+    "foto_bb_reset_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _I, _P, _D]),
+    "foto_bb_flow_dev": (_I, [_P, _P, _I, _I, _P]),
+    "foto_gn_plan_solve_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _P, _I, _I, _P,
+                                    ctypes.POINTER(_I)]),
+    "foto_warp_dev": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
+    "foto_flow_errors_dev": (_I, [_P, _P, _P, _P, _I, _I, _D, _P]),
+    "foto_intensity_error_dev": (_I, [_P, _P, _I, _I, _D, _P]),
+    "foto_dev_malloc": (_I, [ctypes.c_size_t, ctypes.POINTER(_P)]),
+    "foto_dev_free": (_I, [_P]),
+    "foto_dev_memcpy": (_I, [_P, _P, ctypes.c_size_t, _I]),
 }
 
 _lib = None

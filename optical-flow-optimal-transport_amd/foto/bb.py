@@ -37,7 +37,7 @@ class BBSolver:
 
     def __init__(self, rho0, rhoT, Nt, Nx, Ny, r=1.0, reg_epsilon=1e-3, *, device=-1, cg_rtol=1e-6,
                  cg_maxiter=1000, cg_mode=CG_GAUSS, rank=0, world=1, nccl_id=None, virtual_ranks=1,
-                 timing=False, library=None):
+                 timing=False, library=None, _device_pair=None):
         self._L = library if library is not None else lib()
         Nt, Nx, Ny = int(Nt), int(Nx), int(Ny)
         if Nt < 2:
@@ -46,8 +46,27 @@ class BBSolver:
         self.r = float(r)
         self.eps = float(reg_epsilon)
         nxy = Nx * Ny
-        self._rho0 = f64(rho0, nxy, "rho0")
-        self._rhoT = f64(rhoT, nxy, "rhoT")
+        o = self._options(device, cg_rtol, cg_maxiter, cg_mode, rank, world, nccl_id, virtual_ranks, timing)
+        self._ctx = ctypes.c_void_p()
+        if _device_pair is None:
+            self._rho0 = f64(rho0, nxy, "rho0")
+            self._rhoT = f64(rhoT, nxy, "rhoT")
+            self._check(self._L.foto_bb_create(dptr(self._rho0), dptr(self._rhoT), Nt, Nx, Ny, self.r, self.eps,
+                                       ctypes.byref(o), ctypes.byref(self._ctx)))
+        else:   # from_device: the two frames are foto_image descriptors of device memory
+            a, b, normalize, stream = _device_pair
+            sums = np.zeros(2)
+            self._check(self._L.foto_bb_create_dev(ctypes.byref(a), ctypes.byref(b), 1 if normalize else 0,
+                                                   ctypes.c_void_p(stream), Nt, Nx, Ny, self.r, self.eps,
+                                                   ctypes.byref(o), dptr(sums), ctypes.byref(self._ctx)))
+            self.sums = (float(sums[0]), float(sums[1]))
+        self.world = int(world)
+        self.rank = int(rank)
+        self.crit = []
+        self.cg_its = []
+        self.cg_info = []
+
+    def _options(self, device, cg_rtol, cg_maxiter, cg_mode, rank, world, nccl_id, virtual_ranks, timing):
         o = _lib.BBOpts()
         self._L.foto_bb_opts_default(ctypes.byref(o))
         o.device = int(device)
@@ -62,14 +81,47 @@ class BBSolver:
             o.nccl_id = ctypes.cast(self._id, ctypes.c_void_p)
         o.virtual_ranks = int(virtual_ranks)
         o.timing = 1 if timing else 0
-        self._ctx = ctypes.c_void_p()
-        self._check(self._L.foto_bb_create(dptr(self._rho0), dptr(self._rhoT), Nt, Nx, Ny, self.r, self.eps,
-                                   ctypes.byref(o), ctypes.byref(self._ctx)))
-        self.world = int(world)
-        self.rank = int(rank)
+        return o
+
+    # -------------------------------------------------------------- device buffers
+    @classmethod
+    def from_device(cls, f0, f1, Nt, r=1.0, reg_epsilon=1e-3, *, normalize=False, stream=None, **opts):
+        """A solver on two device frames (anything foto.device.as_image accepts: torch ROCm
+        tensors, DeviceArrays, strided views; uint8 / float32 / float64, value = pixel / divisor):
+        foto_bb_create_dev.  The context is in the state the host constructor leaves for the same
+        values, so the solve is bit-identical.  ``normalize`` divides each frame by its own sum
+        (main.py:71-74); ``self.sums`` holds the two sums ((1, 1) without).  ``stream``: the
+        caller's stream (foto.device.stream_handle); the frames may be overwritten by work queued
+        on it as soon as this returns."""
+        from . import device as D
+        a, b = D._pair(f0, f1)
+        h, w = a.shape
+        st = D.stream_handle(stream, f0, f1)
+        return cls(None, None, Nt, w, h, r=r, reg_epsilon=reg_epsilon, _device_pair=(a, b, normalize, st), **opts)
+
+    def reset_device(self, f0, f1, *, normalize=False, stream=None):
+        """reset() on two device frames (foto_bb_reset_dev)."""
+        from . import device as D
+        a, b = D._pair(f0, f1)
+        if a.shape != (self.Ny, self.Nx):
+            raise ValueError(f"frames of shape {a.shape}; this solver was made for {(self.Ny, self.Nx)}")
+        sums = np.zeros(2)
+        self._check(self._L.foto_bb_reset_dev(self._ctx, ctypes.byref(a), ctypes.byref(b), 1 if normalize else 0,
+                                              ctypes.c_void_p(D.stream_handle(stream, f0, f1)), dptr(sums)))
+        self.sums = (float(sums[0]), float(sums[1]))
         self.crit = []
         self.cg_its = []
         self.cg_info = []
+
+    def flow_device(self, out=None, dtype="float32", layout="planar", stream=None):
+        """flow() left on the device (foto_bb_flow_dev): a DeviceArray (or ``out``, any
+        contiguous device array of that shape and dtype) of ``dtype`` float32 | float64, ``layout``
+        "planar" [3][Ny][Nx] = u, v, m or "interleaved" [Ny][Nx][2] = (u, v), the .flo payload."""
+        from . import device as D
+        out, ptr, dcode, lcode = D.export_target(out, dtype, layout, self.Ny, self.Nx)
+        self._check(self._L.foto_bb_flow_dev(self._ctx, ctypes.c_void_p(ptr), dcode, lcode,
+                                             ctypes.c_void_p(D.stream_handle(stream, out))))
+        return out
 
     def _check(self, rc):
         return check(rc, self._L)
@@ -222,6 +274,33 @@ def cached_solver(rho0, rhoT, Nt, Nx, Ny, r, reg_epsilon, **opts):
     while len(_ctx_cache) > CONTEXT_CACHE_SIZE:
         _ctx_cache.popitem(last=False)[1].close()
     return s
+
+
+def cached_solver_device(f0, f1, Nt, r, reg_epsilon, *, normalize=False, stream=None, **opts):
+    """cached_solver for two device frames (the same cache: a context serves host and device
+    pairs alike)."""
+    from . import device as D
+    a, b = D._pair(f0, f1)
+    h, w = a.shape
+    env = tuple(sorted((k, v) for k, v in os.environ.items() if k.startswith("FOTO_")))
+    key = (int(Nt), int(w), int(h), float(r), float(reg_epsilon), tuple(sorted(opts.items())), env)
+    s = _ctx_cache.pop(key, None)
+    if s is not None:
+        s.reset_device(a, b, normalize=normalize, stream=stream)
+    else:
+        s = BBSolver.from_device(a, b, Nt, r=r, reg_epsilon=reg_epsilon, normalize=normalize, stream=stream, **opts)
+    _ctx_cache[key] = s
+    while len(_ctx_cache) > CONTEXT_CACHE_SIZE:
+        _ctx_cache.popitem(last=False)[1].close()
+    return s
+
+
+def drop_cached(s):
+    """Forget and close a cached solver (after a failed solve: no half-used context stays)."""
+    for k, v in list(_ctx_cache.items()):
+        if v is s:
+            del _ctx_cache[k]
+    s.close()
 
 
 def clear_context_cache():

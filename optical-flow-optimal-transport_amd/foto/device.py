@@ -1,0 +1,353 @@
+"""Device buffers: GPU-resident frames in, GPU-resident flow out (include/foto.h, *_dev).
+
+``DeviceArray``   owned device memory over foto_dev_malloc / free / memcpy, with
+                  ``__cuda_array_interface__`` (v3), so it needs no other GPU library and any
+                  consumer of that interface (torch.as_tensor, cupy.asarray) can wrap it.
+``as_image``      anything exposing ``__cuda_array_interface__`` (a torch ROCm tensor, a
+                  DeviceArray, a strided view of either) -> the C ABI's foto_image.
+``bb_flow`` / ``gn_flow``  the two solvers on device frames, through the context / plan caches.
+
+This module never imports torch.  One HIP runtime per process: torch bundles its own
+libamdhip64, and device pointers of one runtime mean nothing to another -- import torch before
+the first foto call, so that libfoto binds to torch's copy (``runtime_check``).
+"""
+import ctypes
+import os
+import sys
+
+import numpy as np
+
+from . import _lib
+from ._lib import FotoError, check, lib
+
+_DTYPES = {"|u1": (_lib.FOTO_U8, np.uint8), "<f4": (_lib.FOTO_F32, np.float32), "<f8": (_lib.FOTO_F64, np.float64)}
+_OUT_DTYPES = {"float32": _lib.FOTO_F32, "float64": _lib.FOTO_F64}
+_LAYOUTS = {"planar": 0, "interleaved": 1}
+H2D, D2H, D2D = 0, 1, 2
+
+
+def mapped_hip_runtimes():
+    """The distinct libamdhip64 files mapped into this process (/proc/self/maps)."""
+    found = []
+    try:
+        with open("/proc/self/maps") as f:
+            for line in f:
+                path = line.rstrip("\n").split(None, 5)[-1] if line.count(" ") >= 5 else ""
+                if os.path.basename(path).startswith("libamdhip64"):
+                    real = os.path.realpath(path)
+                    if real not in found:
+                        found.append(real)
+    except OSError:
+        pass
+    return found
+
+
+def runtime_check():
+    """Raise FotoError when more than one HIP runtime is mapped: device pointers handed from one
+    (torch's) to the other (libfoto's) would be meaningless.  Returns the mapped runtime files."""
+    found = mapped_hip_runtimes()
+    if len(found) > 1:
+        raise FotoError("two HIP runtimes are mapped into this process: " + " and ".join(found) +
+                        "; device pointers cannot cross them.  Rule: import torch before the first foto call "
+                        "(libfoto then binds to torch's libamdhip64)")
+    return found
+
+
+def _typestr(dtype):
+    dt = np.dtype(dtype)
+    ts = dt.str if dt.itemsize > 1 else "|" + dt.str[1:]
+    if ts not in _DTYPES:
+        raise ValueError(f"dtype {dt}: device arrays hold uint8, float32 or float64")
+    return ts
+
+
+class _Owner:
+    """One foto_dev_malloc allocation, freed with its last DeviceArray view."""
+
+    def __init__(self, nbytes):
+        self.nbytes = int(nbytes)
+        p = ctypes.c_void_p()
+        check(lib().foto_dev_malloc(self.nbytes, ctypes.byref(p)))
+        self.ptr = p.value
+
+    def free(self):
+        if self.ptr:
+            lib().foto_dev_free(ctypes.c_void_p(self.ptr))
+            self.ptr = None
+
+    def __del__(self):
+        if sys.is_finalizing():   # the HIP runtime may already be torn down
+            return
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class DeviceArray:
+    """A (possibly strided) array in device memory.  ``DeviceArray(shape, dtype)`` allocates;
+    basic slicing, ``.T`` and integer indexing give views that share the allocation."""
+
+    def __init__(self, shape, dtype=np.float64, *, _owner=None, _offset=0, _strides=None):
+        self.shape = tuple(int(s) for s in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+        self.dtype = np.dtype(dtype)
+        self.typestr = _typestr(self.dtype)
+        size = int(np.prod(self.shape, dtype=np.int64)) if self.shape else 1
+        self._owner = _owner if _owner is not None else _Owner(max(size * self.dtype.itemsize, 1))
+        self._offset = int(_offset)
+        if _strides is None:
+            st, acc = [], self.dtype.itemsize
+            for s in reversed(self.shape):
+                st.append(acc)
+                acc *= max(s, 1)
+            _strides = tuple(reversed(st))
+        self.strides = tuple(int(s) for s in _strides)
+
+    # ---------------------------------------------------------------- interface
+    @property
+    def ptr(self):
+        return self._owner.ptr + self._offset
+
+    @property
+    def size(self):
+        return int(np.prod(self.shape, dtype=np.int64)) if self.shape else 1
+
+    @property
+    def ndim(self):
+        return len(self.shape)
+
+    @property
+    def contiguous(self):
+        acc = self.dtype.itemsize
+        for s, st in zip(reversed(self.shape), reversed(self.strides)):
+            if s > 1 and st != acc:
+                return False
+            acc *= s
+        return True
+
+    @property
+    def __cuda_array_interface__(self):
+        return {"shape": self.shape, "typestr": self.typestr, "data": (self.ptr, False), "version": 3,
+                "strides": None if self.contiguous else self.strides}
+
+    def _host_view(self, host):
+        """This array's shape / strides over `host`, a uint8 host copy of the whole allocation."""
+        n = (host.size - self._offset) // self.dtype.itemsize * self.dtype.itemsize
+        base = host[self._offset:self._offset + n].view(self.dtype)
+        return np.lib.stride_tricks.as_strided(base, shape=self.shape, strides=self.strides, writeable=False)
+
+    # ---------------------------------------------------------------- host <-> device
+    @classmethod
+    def from_numpy(cls, a):
+        a = np.ascontiguousarray(a)
+        d = cls(a.shape, a.dtype)
+        if a.nbytes:
+            check(lib().foto_dev_memcpy(ctypes.c_void_p(d.ptr), a.ctypes.data_as(ctypes.c_void_p), a.nbytes, H2D))
+        return d
+
+    def to_numpy(self):
+        host = np.empty(self._owner.nbytes, dtype=np.uint8)
+        check(lib().foto_dev_memcpy(host.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(self._owner.ptr),
+                                    host.nbytes, D2H))
+        return np.array(self._host_view(host))   # a contiguous, owned copy
+
+    def copy_from(self, other):
+        """Device-to-device copy of a same-shape contiguous array into this contiguous one."""
+        if not (self.contiguous and other.contiguous) or self.shape != other.shape or self.dtype != other.dtype:
+            raise ValueError("copy_from: same shape and dtype, both contiguous")
+        check(lib().foto_dev_memcpy(ctypes.c_void_p(self.ptr), ctypes.c_void_p(other.ptr),
+                                    self.size * self.dtype.itemsize, D2D))
+        return self
+
+    # ---------------------------------------------------------------- views
+    def _view(self, fn):
+        # numpy works out shape / strides / offset of the view on an array that is never read
+        probe = np.lib.stride_tricks.as_strided(np.empty(1, self.dtype), shape=self.shape, strides=self.strides,
+                                                writeable=False)
+        v = fn(probe)
+        off = v.__array_interface__["data"][0] - probe.__array_interface__["data"][0]
+        return DeviceArray(v.shape, self.dtype, _owner=self._owner, _offset=self._offset + off, _strides=v.strides)
+
+    def __getitem__(self, key):
+        keys = key if isinstance(key, tuple) else (key,)
+        if not all(isinstance(k, (slice, type(Ellipsis))) or (isinstance(k, (int, np.integer))) for k in keys):
+            raise TypeError("DeviceArray: basic indexing only (integers, slices, Ellipsis)")
+        # (an integer index becomes a length-1 slice and is squeezed: numpy would return a scalar)
+        norm = tuple(slice(k, k + 1 if k != -1 else None) if isinstance(k, (int, np.integer)) else k for k in keys)
+        drop = [i for i, k in enumerate(self._expand(keys)) if isinstance(k, (int, np.integer))]
+        v = self._view(lambda p: p[norm])
+        if drop:
+            shape = tuple(s for i, s in enumerate(v.shape) if i not in drop)
+            strides = tuple(s for i, s in enumerate(v.strides) if i not in drop)
+            v = DeviceArray(shape, self.dtype, _owner=self._owner, _offset=v._offset, _strides=strides)
+        return v
+
+    def _expand(self, keys):
+        """keys with an Ellipsis spelled out, one entry per axis"""
+        n_e = sum(1 for k in keys if k is Ellipsis)
+        if n_e > 1:
+            raise IndexError("an index can only have a single ellipsis")
+        out = []
+        for k in keys:
+            if k is Ellipsis:
+                out.extend([slice(None)] * (self.ndim - (len(keys) - 1)))
+            else:
+                out.append(k)
+        if len(out) > self.ndim:
+            raise IndexError("too many indices for DeviceArray")
+        return out + [slice(None)] * (self.ndim - len(out))
+
+    @property
+    def T(self):
+        return self._view(lambda p: p.T)
+
+    def reshape(self, *shape):
+        if not self.contiguous:
+            raise ValueError("reshape: contiguous arrays only")
+        shape = shape[0] if len(shape) == 1 and isinstance(shape[0], (tuple, list)) else shape
+        probe = np.lib.stride_tricks.as_strided(np.empty(1, self.dtype), shape=self.shape, strides=self.strides,
+                                                writeable=False)
+        v = probe.reshape(shape)
+        return DeviceArray(v.shape, self.dtype, _owner=self._owner, _offset=self._offset, _strides=v.strides)
+
+    def __repr__(self):
+        return f"DeviceArray(shape={self.shape}, dtype={self.dtype}, strides={self.strides}, ptr=0x{self.ptr:x})"
+
+
+# -------------------------------------------------------------------- descriptors
+
+def _interface(obj):
+    """(ptr, typestr, shape, byte strides or None, stream entry or None) of obj."""
+    if isinstance(obj, dict):
+        d = obj
+    else:
+        d = getattr(obj, "__cuda_array_interface__", None)
+        if d is None:
+            raise TypeError(f"{type(obj).__name__} does not expose __cuda_array_interface__ (a device array, e.g. a "
+                            "torch ROCm tensor or a foto.device.DeviceArray, is required)")
+    if "ptr" in d:   # the explicit (ptr, typestr, shape, strides) mapping
+        ptr = d["ptr"]
+    else:
+        ptr = d["data"][0]
+    return int(ptr or 0), str(d["typestr"]), tuple(int(s) for s in d["shape"]), d.get("strides"), d.get("stream")
+
+
+def stream_handle(stream=None, *objs):
+    """The hipStream_t (as an integer; 0 = the legacy null stream) for a call: an explicit
+    ``stream`` (an integer handle, or an object with ``.cuda_stream`` such as torch.cuda.Stream),
+    else the "stream" entry of the first object's interface that has one (1 = legacy default,
+    2 = per-thread default), else null."""
+    if stream is None:
+        for o in objs:
+            try:
+                s = _interface(o)[4]
+            except (TypeError, KeyError):
+                s = None
+            if s is not None:
+                stream = s
+                if stream == 0:
+                    raise ValueError("__cuda_array_interface__: stream 0 is not allowed (1 is the legacy default stream)")
+                return 0 if stream == 1 else int(stream)
+        return 0
+    if hasattr(stream, "cuda_stream"):
+        stream = stream.cuda_stream
+    return int(stream)
+
+
+def as_image(obj, divisor=None):
+    """The foto_image of a 2-D uint8 / float32 / float64 device array (rows = y, columns = x).
+    ``divisor`` defaults to 255 for uint8 and 1 otherwise: value = float64(pixel) / divisor.
+    The returned ``_lib.Image`` carries ``.shape`` = (h, w) and keeps ``obj`` alive."""
+    if isinstance(obj, _lib.Image):
+        return obj
+    if not isinstance(obj, DeviceArray):
+        runtime_check()   # a foreign object's pointers come from whichever runtime its library uses
+    ptr, typestr, shape, strides, _ = _interface(obj)
+    if typestr not in _DTYPES:
+        raise TypeError(f"typestr {typestr!r}: frames are uint8 ('|u1'), float32 ('<f4') or float64 ('<f8')")
+    if len(shape) != 2:
+        raise ValueError(f"shape {shape}: a frame is a 2-D (height, width) array; take one channel of a colour image")
+    code, npdt = _DTYPES[typestr]
+    item = np.dtype(npdt).itemsize
+    h, w = shape
+    if strides is None:
+        strides = (w * item, item)
+    sy, sx = (int(s) for s in strides)
+    if sy % item or sx % item:
+        raise ValueError(f"byte strides {(sy, sx)} are not multiples of the {item}-byte item size")
+    im = _lib.Image()
+    im.data = ptr
+    im.dtype = code
+    im.stride_y, im.stride_x = sy // item, sx // item
+    im.divisor = float(divisor) if divisor is not None else (255.0 if code == _lib.FOTO_U8 else 1.0)
+    im.shape = (h, w)
+    im._keep = obj
+    return im
+
+
+def _pair(f0, f1, divisor=None):
+    a, b = as_image(f0, divisor), as_image(f1, divisor)
+    if a.shape != b.shape:
+        raise ValueError(f"frames differ in shape: {a.shape} and {b.shape}")
+    return a, b
+
+
+def export_target(out, dtype, layout, h, w):
+    """(DeviceArray or the caller's object, pointer, dtype code, layout code) of a flow export."""
+    if dtype not in _OUT_DTYPES:
+        dtype = np.dtype(dtype).name
+    if dtype not in _OUT_DTYPES:
+        raise ValueError(f"dtype {dtype!r}: 'float32' or 'float64'")
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout {layout!r}: 'planar' ([3][h][w] = u, v, m) or 'interleaved' ([h][w][2] = (u, v))")
+    shape = (3, h, w) if layout == "planar" else (h, w, 2)
+    if out is None:
+        out = DeviceArray(shape, dtype)
+        return out, out.ptr, _OUT_DTYPES[dtype], _LAYOUTS[layout]
+    if not isinstance(out, DeviceArray):
+        runtime_check()
+    ptr, typestr, oshape, strides, _ = _interface(out)
+    want = _typestr(dtype)
+    if typestr != want or tuple(oshape) != shape:
+        raise ValueError(f"out: expected {dtype} of shape {shape}, got {typestr} of shape {tuple(oshape)}")
+    if strides is not None:
+        item, acc = np.dtype(dtype).itemsize, np.dtype(dtype).itemsize
+        for s, st in zip(reversed(shape), reversed(tuple(strides))):
+            if s > 1 and st != acc:
+                raise ValueError("out must be C-contiguous")
+            acc *= s
+    return out, ptr, _OUT_DTYPES[dtype], _LAYOUTS[layout]
+
+
+# -------------------------------------------------------------------- convenience
+
+def bb_flow(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, normalize=False,
+            dtype="float32", layout="planar", out=None, stream=None, **opts):
+    """benamou_brenier.solve on device frames, the flow left on the device: a context from the
+    cache (foto.bb.cached_solver's, reset to this pair), the reference's stop rules, one export.
+    Returns the DeviceArray (or ``out``)."""
+    from . import bb
+    a, b = _pair(f0, f1)
+    h, w = a.shape
+    st = stream_handle(stream, f0, f1)
+    if bb._cache_enabled(opts):
+        s = bb.cached_solver_device(a, b, Nt, r, reg_epsilon, normalize=normalize, stream=st, **opts)
+        try:
+            s.iterate(max_it, convergence_tol=convergence_tol, stop_rules=True)
+            return s.flow_device(out=out, dtype=dtype, layout=layout, stream=st)
+        except BaseException:
+            bb.drop_cached(s)
+            raise
+    with bb.BBSolver.from_device(a, b, Nt, r=r, reg_epsilon=reg_epsilon, normalize=normalize, stream=st, **opts) as s:
+        s.iterate(max_it, convergence_tol=convergence_tol, stop_rules=True)
+        return s.flow_device(out=out, dtype=dtype, layout=layout, stream=st)
+
+
+def gn_flow(f0, f1, alpha, lam, *, dtype="float32", layout="planar", out=None, stream=None):
+    """classical.GLLOpticalFlow.process on device frames (the plan from foto.gn's cache); returns
+    the DeviceArray (or ``out``) holding u, v, m."""
+    from . import gn
+    a, b = _pair(f0, f1)
+    h, w = a.shape
+    p = gn.cached_plan(w, h, alpha, lam)
+    return p.solve_device(a, b, out=out, dtype=dtype, layout=layout, stream=stream_handle(stream, f0, f1))[0]

@@ -5,6 +5,8 @@ warp            utils.apply_opticalflow (utils.py:186-248)  bit-identical
 flow_errors     utils.EE + utils.AE     (utils.py:294-338)  up to summation order
 intensity_error utils.IE                (utils.py:340-354)  up to summation order
 """
+import ctypes
+
 import numpy as np
 
 from ._lib import check, dptr, f64, lib
@@ -36,4 +38,60 @@ def intensity_error(I, IGT, w, h):
     a, b = f64(I, n, "I"), f64(IGT, n, "IGT")
     out = np.empty(1)
     check(lib().foto_intensity_error(dptr(a), dptr(b), w, h, dptr(out)))
+    return float(out[0])
+
+
+# ------------------------------------------------------------------ device buffers
+# The same three calls on contiguous float64 device arrays (foto.device.DeviceArray, torch ROCm
+# tensors, ...): the same kernels and reduction order, without the uploads.
+
+def _dev_f64(x, n, name):
+    from . import device as D
+    if not isinstance(x, D.DeviceArray):
+        D.runtime_check()
+    ptr, typestr, shape, strides, _ = D._interface(x)
+    size = int(np.prod(shape, dtype=np.int64))
+    if typestr != "<f8" or size != n:
+        raise ValueError(f"{name}: expected {n} float64 values on the device, got {size} of {typestr}")
+    if strides is not None:
+        acc = 8
+        for s, st in zip(reversed(shape), reversed(tuple(strides))):
+            if s > 1 and st != acc:
+                raise ValueError(f"{name}: must be C-contiguous")
+            acc *= s
+    return ctypes.c_void_p(ptr)
+
+
+def warp_device(f1, u, v, w, h, m=None, out=None, stream=None):
+    """warp() on device arrays; returns the DeviceArray (or ``out``) of h x w float64."""
+    from . import device as D
+    n = w * h
+    if out is None:
+        out = D.DeviceArray((h, w), np.float64)
+    st = D.stream_handle(stream, f1, u, v)
+    check(lib().foto_warp_dev(_dev_f64(f1, n, "f1"), _dev_f64(u, n, "u"), _dev_f64(v, n, "v"),
+                              _dev_f64(m, n, "m") if m is not None else None, w, h, _dev_f64(out, n, "out"),
+                              ctypes.c_void_p(st)))
+    return out
+
+
+def flow_errors_device(u, v, uGT, vGT, w, h, stream=None):
+    """flow_errors() on device arrays (host scalars back)."""
+    from . import device as D
+    n = w * h
+    out = np.empty(4)
+    st = D.stream_handle(stream, u, v, uGT, vGT)
+    check(lib().foto_flow_errors_dev(_dev_f64(u, n, "u"), _dev_f64(v, n, "v"), _dev_f64(uGT, n, "uGT"),
+                                     _dev_f64(vGT, n, "vGT"), w, h, dptr(out), ctypes.c_void_p(st)))
+    return tuple(float(x) for x in out)
+
+
+def intensity_error_device(I, IGT, w, h, stream=None):
+    """intensity_error() on device arrays (a host scalar back)."""
+    from . import device as D
+    n = w * h
+    out = np.empty(1)
+    st = D.stream_handle(stream, I, IGT)
+    check(lib().foto_intensity_error_dev(_dev_f64(I, n, "I"), _dev_f64(IGT, n, "IGT"), w, h, dptr(out),
+                                         ctypes.c_void_p(st)))
     return float(out[0])

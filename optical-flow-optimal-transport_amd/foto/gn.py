@@ -82,6 +82,22 @@ class Plan:
                                               ctypes.byref(its)))
         return u, v, m, info, its.value
 
+    def solve_device(self, f1, f2, out=None, dtype="float32", layout="planar", stream=None):
+        """solve() on two device frames (anything foto.device.as_image accepts), the solution
+        left on the device (foto_gn_plan_solve_dev): returns (out, info, iterations) with out a
+        DeviceArray (or the given contiguous device array) -- "planar" [3][h][w] = u, v, m or
+        "interleaved" [h][w][2] = (u, v).  No pinned staging, no host copies."""
+        from . import device as D
+        a, b = D._pair(f1, f2)
+        if a.shape != (self.h, self.w):
+            raise ValueError(f"frames of shape {a.shape}; this plan was made for {(self.h, self.w)}")
+        st = D.stream_handle(stream, f1, f2)
+        out, ptr, dcode, lcode = D.export_target(out, dtype, layout, self.h, self.w)
+        its = ctypes.c_int(0)
+        info = check(lib().foto_gn_plan_solve_dev(self._p, ctypes.byref(a), ctypes.byref(b), ctypes.c_void_p(ptr),
+                                                  dcode, lcode, ctypes.c_void_p(st), ctypes.byref(its)))
+        return out, info, its.value
+
     def timing(self):
         """{ms_setup, ms_pcg, iterations, launched} of the last solve (device events)."""
         out = np.zeros(4)
