@@ -68,6 +68,12 @@ int foto_cg(const double* b, int Nt, int Nx, int Ny, double r, double eps, doubl
 /* utils.opticalflow_from_benamoubrenier(phi, Nt, Nx, Ny, grad('N'), div('D'))
  * (utils.py:44-99, 148-183)                                                        */
 int foto_flow_from_phi(const double* phi, int Nt, int Nx, int Ny, double* u, double* v, double* m);
+/* Test entry: the flow path of foto_bb_flow_path (below) from a caller's phi, without a context.
+ * Record n-1 (n = 1..Nt-1) = utils.opticalflow_from_benamoubrenier(phi[: (n+1)*Nx*Ny], n+1, Nx,
+ * Ny, grad('N'), div('D')): the displacement after the first n steps of
+ * utils.reconstructTrajectory (utils.py:63-97) and m = -div('D')[u; v] (utils.py:181).
+ * u, v, m: each [Nt-1][Ny*Nx]; record Nt-2 carries the bits of foto_flow_from_phi.       */
+int foto_flow_path_from_phi(const double* phi, int Nt, int Nx, int Ny, double* u, double* v, double* m);
 
 /* ------------------------------------------------------------------ BB solver context
  * benamou_brenier.solve (benamou_brenier.py:151-271) split into create / iterate /
@@ -347,6 +353,40 @@ int foto_bb_reset_dev(foto_bb_ctx* c, const foto_image* f0, const foto_image* f1
  * utils.saveFlo (utils.py:273-292) writes after its 12-byte header.  (float)x rounds to nearest
  * even, as np.float32(x).  Same callback and in-flight rules as foto_bb_flow.            */
 int foto_bb_flow_dev(foto_bb_ctx* c, void* out, int dtype, int layout, void* stream);
+
+/* The transport path: what only a dynamic-OT solver has between its two frames.  Host and device
+ * twins, with the rules of foto_bb_flow / foto_bb_get_state and of foto_bb_flow_dev: the data is
+ * that of the last COMPLETED outer iteration (from the callback of the default single-GPU loop:
+ * the iteration it reports; from the one-in-flight loop's callback FOTO_ERR_STATE); a context
+ * that a failed iterate left inconsistent, and an RCCL context, return FOTO_ERR_STATE;
+ * virtual_ranks > 1 works (planes and steps come from the in-process shard that owns them).
+ * None of them allocates, and none changes anything the next foto_bb_iterate reads.
+ *
+ * Density frames: rho at plane positions s[k] (a HOST array) in [0, Nt-1]:
+ * n = min((int)s, Nt-2), w = s - n, value = scale * ((1 - w) * rho_n + w * rho_{n+1}), rho_n =
+ * plane n of mu's density part -- mu[n*Nx*Ny:(n+1)*Nx*Ny], the planes the commented-out export of
+ * benamou_brenier.py:262-267 saved as rhon[n] -- of the last completed outer iteration (before any
+ * iteration: the initial path of benamou_brenier.py:193-194).  The multiply by scale comes last,
+ * so an integer s with scale == 1 reproduces plane n bit for bit; scale undoes normalize = 1 when
+ * it is the frame sum from sums2.  out: [count][Ny][Nx], C-contiguous.  F32 is (float)x (to
+ * nearest even, np.float32); U8 is (uint8)(255 * clip(x, 0, 1) + 0.5), NaN -> 0: to nearest, unlike
+ * the truncating np.uint8(255 * np.clip(...)) of main.py:142, so that a u8 frame survives ingest
+ * and export (255 * (49 / 255.0) is 48.99999999999999).  FOTO_ERR_ARG: null pointers, count <= 0,
+ * an s[k] outside [0, Nt-1] or not finite, a scale not finite or <= 0, a dtype outside 0..2, an
+ * `out` that is not device memory of the context's device (checked before anything is enqueued;
+ * `out` is then untouched).  One kernel launch per 128 frames.                               */
+int foto_bb_frames(foto_bb_ctx* c, const double* s, int count, double scale, double* out);          /* host f64 */
+int foto_bb_frames_dev(foto_bb_ctx* c, const double* s, int count, double scale, void* out, int dtype,
+                       void* stream);
+/* Flow path: record n-1 (n = 1..Nt-1) = (u_n, v_n, m_n): the displacement after the first n steps
+ * of utils.reconstructTrajectory (utils.py:63-97) and m_n = -div('D')[u_n; v_n] (utils.py:181),
+ * i.e. utils.opticalflow_from_benamoubrenier(phi[: (n+1)*Nx*Ny], n+1, Nx, Ny, ...) (utils.py:148-183).
+ * Record Nt-2 is foto_bb_flow's result, bit for bit.  Host: u, v, m each [Nt-1][Ny*Nx].  Device:
+ * `out` holds Nt-1 consecutive records, each laid out as foto_bb_flow_dev lays out its one --
+ * layout 0: [Nt-1][3][Ny][Nx], layout 1: [Nt-1][Ny][Nx][2]; dtype FOTO_F32 | FOTO_F64 (m is computed
+ * from the float64 u, v).  FOTO_ERR_STATE before any outer iteration has run.               */
+int foto_bb_flow_path(foto_bb_ctx* c, double* u, double* v, double* m);
+int foto_bb_flow_path_dev(foto_bb_ctx* c, void* out, int dtype, int layout, void* stream);
 
 /* foto_gn_plan_solve (classical.py:68-130) on device frames, the solution exported to `out` as
  * foto_bb_flow_dev does (planar: u, v, m).  Same PCG launches, prediction, result and return

@@ -1203,6 +1203,97 @@ static int flow(foto_bb_ctx* c, double* u, double* v, double* m, const FlowDev* 
     return 0;
 }
 
+// ------------------------------------------------------------------ transport path exports
+// The in-process shard that owns global plane n (one device: world == 1, virtual ranks included).
+static Shard* plane_owner(foto_bb_ctx* c, int n) {
+    for (auto& sp : c->sh)
+        if (n >= sp->g.t0 && n < sp->g.t0 + sp->g.nloc) return sp.get();
+    return nullptr;
+}
+
+// foto_bb_flow_path / _dev: launch_traj one step at a time from the running positions (shard
+// 0's px, py; step n reads phi plane n of whichever shard owns it), and after each step the
+// record (u_n, v_n, m_n) straight from them -- two launches per step.  Host: the record goes to
+// shard 0's fu, fv, fm and from there into the caller's arrays.  Touches neither the statistics
+// nor anything the outer loop reads.
+static int flow_path(foto_bb_ctx* c, const Completed& k, double* hu, double* hv, double* hm, const FlowDev* dv) {
+    Shard& s0 = *c->sh[0];
+    const int64_t nxy = (int64_t)c->Nx * c->Ny;
+    if (dv) FOTO_TRY(c->link.enter(dv->user, c->s));   // (before the first write of `out`)
+    for (int n = 0; n + 1 < c->Nt; ++n) {
+        Shard* sp = plane_owner(c, n);
+        if (!sp) { set_error("flow path: no local shard owns plane %d", n); return FOTO_ERR_STATE; }
+        const double* phi = (sp == &s0) ? k.phi : sp->phi;
+        FOTO_HIP_CHECK(launch_traj(sp->g, phi, n, n + 1, s0.px, s0.py, n == 0, c->s));
+        if (dv) {
+            const size_t rec = (size_t)nxy * (dv->layout == 0 ? 3 : 2) * dtype_bytes(dv->dtype);
+            char* o = (char*)dv->out + (size_t)n * rec;
+            const size_t pl = (size_t)nxy * dtype_bytes(dv->dtype);
+            FOTO_HIP_CHECK(launch_flow_record(c->Nx, c->Ny, s0.px, s0.py, o, o + pl, o + 2 * pl, dv->dtype,
+                                              dv->layout, c->s));
+        } else {
+            FOTO_HIP_CHECK(launch_flow_record(c->Nx, c->Ny, s0.px, s0.py, s0.fu, s0.fv, s0.fm, FOTO_F64, 0, c->s));
+            FOTO_HIP_CHECK(hipMemcpyAsync(hu + n * nxy, s0.fu, nxy * sizeof(double), hipMemcpyDeviceToHost, c->s));
+            FOTO_HIP_CHECK(hipMemcpyAsync(hv + n * nxy, s0.fv, nxy * sizeof(double), hipMemcpyDeviceToHost, c->s));
+            FOTO_HIP_CHECK(hipMemcpyAsync(hm + n * nxy, s0.fm, nxy * sizeof(double), hipMemcpyDeviceToHost, c->s));
+        }
+    }
+    if (dv) return c->link.leave(c->s, dv->user);
+    FOTO_HIP_CHECK(hipStreamSynchronize(c->s));
+    return 0;
+}
+
+// The argument rules of foto_bb_frames / _dev (before anything is enqueued or written).
+static int frames_check(foto_bb_ctx* c, const double* s, int count, double scale, const void* out, int dtype,
+                        const char* who) {
+    if (!c) { set_error("%s: null ctx", who); return FOTO_ERR_ARG; }
+    if (c->rccl) { set_error("%s: not supported on RCCL-sharded contexts", who); return FOTO_ERR_STATE; }
+    if (c->broken) {
+        set_error("%s: a failed foto_bb_iterate left the context inconsistent; foto_bb_reset it", who);
+        return FOTO_ERR_STATE;
+    }
+    if (!s || !out) { set_error("%s: null pointer", who); return FOTO_ERR_ARG; }
+    if (count <= 0) { set_error("%s: count = %d must be > 0", who, count); return FOTO_ERR_ARG; }
+    if (!std::isfinite(scale) || !(scale > 0.0)) {
+        set_error("%s: scale %g must be finite and > 0", who, scale);
+        return FOTO_ERR_ARG;
+    }
+    if (dtype < FOTO_U8 || dtype > FOTO_F64) {
+        set_error("%s: dtype %d is not FOTO_U8 / FOTO_F32 / FOTO_F64", who, dtype);
+        return FOTO_ERR_ARG;
+    }
+    for (int k = 0; k < count; ++k) {
+        if (!std::isfinite(s[k]) || s[k] < 0.0 || s[k] > (double)(c->Nt - 1)) {
+            set_error("%s: s[%d] = %.17g is outside [0, Nt - 1 = %d]", who, k, s[k], c->Nt - 1);
+            return FOTO_ERR_ARG;
+        }
+    }
+    return 0;
+}
+
+// Frames [k0, k0 + cnt) of s into `out` (device memory of `dtype`), one launch: the density
+// planes are mu's t-part of the completed iteration, in whichever shard owns them.
+static int frames_launch(foto_bb_ctx* c, const Completed& k, const double* s, int cnt, double scale, void* out,
+                         int dtype) {
+    Shard& s0 = *c->sh[0];
+    const int64_t nxy = (int64_t)c->Nx * c->Ny;
+    FrameArgs fa;
+    for (int i = 0; i < cnt; ++i) {
+        const int n = std::min((int)s[i], c->Nt - 2);
+        const double w = s[i] - (double)n;
+        Shard* pa = plane_owner(c, n);
+        Shard* pb = plane_owner(c, n + 1);
+        if (!pa || !pb) { set_error("frames: no local shard owns plane %d / %d", n, n + 1); return FOTO_ERR_STATE; }
+        const double* ma = (pa == &s0) ? k.mu[0] : pa->mu[0];
+        const double* mb = (pb == &s0) ? k.mu[0] : pb->mu[0];
+        fa.a[i] = ma + (int64_t)(n - pa->g.t0) * nxy;
+        fa.b[i] = mb + (int64_t)(n + 1 - pb->g.t0) * nxy;
+        fa.w[i] = w;
+    }
+    FOTO_HIP_CHECK(launch_frames(fa, cnt, nxy, scale, out, dtype, c->s));
+    return 0;
+}
+
 }  // namespace foto
 
 // ============================================================================ C ABI (BB)
@@ -1574,6 +1665,75 @@ int foto_bb_flow(foto_bb_ctx* c, double* u, double* v, double* m) {
     const int rc = flow(c, u, v, m);
     s0.phi = keep;
     return rc;
+}
+
+static int flow_path_entry(foto_bb_ctx* c, double* u, double* v, double* m, const FlowDev* dv, const char* who) {
+    if (!c) { set_error("%s: null ctx", who); return FOTO_ERR_ARG; }
+    if (c->rccl) { set_error("%s: not supported on RCCL-sharded contexts", who); return FOTO_ERR_STATE; }
+    if (c->broken) {
+        set_error("%s: a failed foto_bb_iterate left the context inconsistent; foto_bb_reset it", who);
+        return FOTO_ERR_STATE;
+    }
+    if (!c->have_phi) {   // (before the output is looked at, as foto_bb_flow_dev)
+        set_error("%s: no outer iteration has run yet", who);
+        return FOTO_ERR_STATE;
+    }
+    if (dv) {
+        FOTO_TRY(export_check(dv->out, dv->dtype, dv->layout, (int64_t)c->Nx * c->Ny * (c->Nt - 1),
+                              stream_device(c->s), who));
+    } else if (!u || !v || !m) {
+        set_error("%s: null pointer", who);
+        return FOTO_ERR_ARG;
+    }
+    Completed k;
+    FOTO_TRY(completed_state(c, who, &k));
+    return flow_path(c, k, u, v, m, dv);
+}
+
+int foto_bb_flow_path(foto_bb_ctx* c, double* u, double* v, double* m) {
+    return flow_path_entry(c, u, v, m, nullptr, "foto_bb_flow_path");
+}
+
+int foto_bb_flow_path_dev(foto_bb_ctx* c, void* out, int dtype, int layout, void* stream) {
+    const FlowDev dv{out, dtype, layout, (hipStream_t)stream};
+    return flow_path_entry(c, nullptr, nullptr, nullptr, &dv, "foto_bb_flow_path_dev");
+}
+
+int foto_bb_frames(foto_bb_ctx* c, const double* s, int count, double scale, double* out) {
+    FOTO_TRY(frames_check(c, s, count, scale, out, FOTO_F64, "foto_bb_frames"));
+    Completed k;
+    FOTO_TRY(completed_state(c, "foto_bb_frames", &k));
+    // one frame at a time through shard 0's fu (a plane of float64 the flow extraction rewrites)
+    Shard& s0 = *c->sh[0];
+    const int64_t nxy = (int64_t)c->Nx * c->Ny;
+    for (int i = 0; i < count; ++i) {
+        FOTO_TRY(frames_launch(c, k, s + i, 1, scale, s0.fu, FOTO_F64));
+        FOTO_HIP_CHECK(hipMemcpyAsync(out + (int64_t)i * nxy, s0.fu, nxy * sizeof(double), hipMemcpyDeviceToHost,
+                                      c->s));
+    }
+    FOTO_HIP_CHECK(hipStreamSynchronize(c->s));
+    return 0;
+}
+
+int foto_bb_frames_dev(foto_bb_ctx* c, const double* s, int count, double scale, void* out, int dtype,
+                       void* stream) {
+    const char* who = "foto_bb_frames_dev";
+    FOTO_TRY(frames_check(c, s, count, scale, out, dtype, who));
+    const int64_t nxy = (int64_t)c->Nx * c->Ny;
+    const size_t fb = (size_t)nxy * dtype_bytes(dtype);
+    if ((uintptr_t)out % dtype_bytes(dtype) != 0) {
+        set_error("%s: out %p is not aligned to its %zu-byte element", who, out, dtype_bytes(dtype));
+        return FOTO_ERR_ARG;
+    }
+    FOTO_TRY(dev_ptr_check(out, (size_t)count * fb, stream_device(c->s), who, "out"));
+    Completed k;
+    FOTO_TRY(completed_state(c, who, &k));
+    FOTO_TRY(c->link.enter((hipStream_t)stream, c->s));   // (before the first write of `out`)
+    for (int k0 = 0; k0 < count; k0 += FRAMES_MAX) {      // (one launch for count <= FRAMES_MAX)
+        const int cnt = std::min(FRAMES_MAX, count - k0);
+        FOTO_TRY(frames_launch(c, k, s + k0, cnt, scale, (char*)out + (size_t)k0 * fb, dtype));
+    }
+    return c->link.leave(c->s, (hipStream_t)stream);
 }
 
 int foto_bb_shard(const foto_bb_ctx* c, int* t0, int* nloc) {

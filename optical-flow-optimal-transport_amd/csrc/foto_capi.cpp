@@ -233,6 +233,31 @@ int foto_flow_from_phi(const double* phi, int Nt, int Nx, int Ny, double* u, dou
     return S.sync();
 }
 
+int foto_flow_path_from_phi(const double* phi, int Nt, int Nx, int Ny, double* u, double* v, double* m) {
+    FOTO_TRY(check3(Nt, Nx, Ny));
+    FOTO_TRY(check2(Nx, Ny));
+    if (!phi || !u || !v || !m) { set_error("foto_flow_path_from_phi: null pointer"); return FOTO_ERR_ARG; }
+    Scope S;
+    FOTO_TRY(S.init());
+    const Geo g = make_geo(Nt, Nx, Ny);
+    const size_t N = (size_t)Nt * g.nxy, n = (size_t)g.nxy, R = (size_t)(Nt - 1) * n;
+    double *d, *px, *py, *du, *dv, *dm;
+    FOTO_TRY(S.up(phi, N, &d));
+    FOTO_TRY(S.dev(n, &px));
+    FOTO_TRY(S.dev(n, &py));
+    FOTO_TRY(S.dev(R, &du));
+    FOTO_TRY(S.dev(R, &dv));
+    FOTO_TRY(S.dev(R, &dm));
+    for (int k = 0; k + 1 < Nt; ++k) {   // the two launches per step of foto_bb_flow_path
+        FOTO_HIP_CHECK(launch_traj(g, d, k, k + 1, px, py, k == 0, S.s));
+        FOTO_HIP_CHECK(launch_flow_record(Nx, Ny, px, py, du + k * n, dv + k * n, dm + k * n, FOTO_F64, 0, S.s));
+    }
+    FOTO_TRY(S.down(u, du, R));
+    FOTO_TRY(S.down(v, dv, R));
+    FOTO_TRY(S.down(m, dm, R));
+    return S.sync();
+}
+
 // ----------------------------------------------------------------------------- GN
 
 int foto_gn_apply(const double* f1, const double* f2, int w, int h, double alpha, double lam, const double* x3,

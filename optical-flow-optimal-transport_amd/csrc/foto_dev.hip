@@ -106,6 +106,65 @@ __global__ __launch_bounds__(NT) void k_export(int64_t n, const double* __restri
     }
 }
 
+// (float)x rounds to nearest even; uint8 is (uint8)(255 * clip(x, 0, 1) + 0.5), NaN -> 0: to
+// nearest, so a u8 frame ingested with divisor 255 comes back (255 * (49 / 255.0) is 48.99...)
+template <class T> __device__ __forceinline__ T frame_cast(double x) { return (T)x; }
+template <> __device__ __forceinline__ unsigned char frame_cast<unsigned char>(double x) {
+    if (!(x >= 0.0)) x = 0.0;
+    if (x > 1.0) x = 1.0;
+    return (unsigned char)(255.0 * x + 0.5);
+}
+
+// The multiply by scale comes last: an integer position with scale == 1 gives the plane's bits.
+__device__ __forceinline__ double frame_value(const double* __restrict__ a, const double* __restrict__ b, double w,
+                                              double scale, int64_t p) {
+    if (w == 0.0) return scale * a[p];
+    if (w == 1.0) return scale * b[p];
+    return scale * ((1.0 - w) * a[p] + w * b[p]);
+}
+
+// Frame k = blockIdx.y: out[k][0..n) from one or two density planes.  One work item = one
+// 16-byte store of VE = 16 / sizeof(T) pixels; a frame starts at any element-aligned address
+// (n * sizeof(T) need not be a multiple of 16), so item 0 takes the pixels before the frame's
+// first 16-byte boundary, the last item the tail, one by one.
+template <class T>
+__global__ __launch_bounds__(NT) void k_frames(FrameArgs fa, int64_t n, double scale, T* __restrict__ out) {
+    constexpr int VE = 16 / (int)sizeof(T);
+    const int k = blockIdx.y;
+    const double* __restrict__ a = fa.a[k];
+    const double* __restrict__ b = fa.b[k];
+    const double w = fa.w[k];
+    T* __restrict__ o = out + (int64_t)k * n;
+    int64_t head = (int64_t)(((16 - ((uintptr_t)o & 15)) & 15) / sizeof(T));
+    if (head > n) head = n;
+    const int64_t t = (int64_t)blockIdx.x * NT + threadIdx.x;
+    if (t == 0) {
+        for (int64_t p = 0; p < head; ++p) o[p] = frame_cast<T>(frame_value(a, b, w, scale, p));
+        return;
+    }
+    const int64_t p0 = head + (t - 1) * VE;
+    if (p0 >= n) return;
+    if (p0 + VE <= n) {
+        typedef typename Vec16<T>::type V;
+        T e[VE];
+#pragma unroll
+        for (int j = 0; j < VE; ++j) e[j] = frame_cast<T>(frame_value(a, b, w, scale, p0 + j));
+        V q;
+        __builtin_memcpy(&q, e, 16);
+        *(V*)(o + p0) = q;
+    } else {
+        for (int64_t p = p0; p < n; ++p) o[p] = frame_cast<T>(frame_value(a, b, w, scale, p));
+    }
+}
+
+template <class T>
+hipError_t frames_t(const FrameArgs& fa, int count, int64_t n, double scale, void* out, hipStream_t s) {
+    constexpr int VE = 16 / (int)sizeof(T);
+    const int64_t items = (n + VE - 1) / VE + 2;   // the head item, the chunks, a tail behind a head
+    k_frames<T><<<dim3((unsigned)flat_blocks(items), (unsigned)count), NT, 0, s>>>(fa, n, scale, (T*)out);
+    return hipGetLastError();
+}
+
 int stream_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(flat_blocks(n), 1 << 16)); }
 
 size_t dtype_size(int dtype) { return dtype == FOTO_U8 ? 1 : dtype == FOTO_F32 ? 4 : 8; }
@@ -257,6 +316,19 @@ hipError_t launch_export(int64_t n, const double* a, const double* b, const doub
                          int layout, hipStream_t s) {
     if (dtype == FOTO_F32) return export_t<float>(n, a, b, c, out, layout, s);
     if (dtype == FOTO_F64) return export_t<double>(n, a, b, c, out, layout, s);
+    return hipErrorInvalidValue;
+}
+
+size_t dtype_bytes(int dtype) { return dtype_size(dtype); }
+
+hipError_t launch_frames(const FrameArgs& fa, int count, int64_t n, double scale, void* out, int dtype,
+                         hipStream_t s) {
+    if (count < 1 || count > FRAMES_MAX || n < 1) return hipErrorInvalidValue;
+    switch (dtype) {
+        case FOTO_U8: return frames_t<unsigned char>(fa, count, n, scale, out, s);
+        case FOTO_F32: return frames_t<float>(fa, count, n, scale, out, s);
+        case FOTO_F64: return frames_t<double>(fa, count, n, scale, out, s);
+    }
     return hipErrorInvalidValue;
 }
 

@@ -2419,6 +2419,9 @@ static int gn_plan_solve(foto_gn_plan* P, const double* f1, const double* f2, do
     tr.mark("solve: copy out");
     const int its = done ? P->hS->iters : maxiter;
     float t0 = 0.f, t1 = 0.f;
+    // (device path: nothing waited after ev[2] was recorded -- the host path's download events do --
+    // and an elapsed time of an event still pending is hipErrorNotReady)
+    if (dv) FOTO_HIP_CHECK(hipEventSynchronize(P->ev[2]));
     FOTO_HIP_CHECK(hipEventElapsedTime(&t0, P->ev[0], P->ev[1]));
     FOTO_HIP_CHECK(hipEventElapsedTime(&t1, P->ev[1], P->ev[2]));
     P->last[0] = t0; P->last[1] = t1; P->last[2] = its; P->last[3] = k;

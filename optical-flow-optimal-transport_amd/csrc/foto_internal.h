@@ -253,6 +253,12 @@ hipError_t launch_traj(const Geo& g, const double* phi, int n_lo, int n_hi, doub
                        int init, hipStream_t s);
 hipError_t launch_flow_finish(int Nx, int Ny, const double* px, const double* py, double* u, double* v,
                               double* m, hipStream_t s);
+// One record of the flow path straight from the running positions: k_flow_uv, the -div('D') of
+// launch_flow_finish (same operation order, same -1.0 scale; m from the float64 u, v) and the
+// export in one kernel.  dtype FOTO_F32 | FOTO_F64; layout 0: ou[i], ov[i], om[i] (three planes,
+// anywhere); layout 1: ou[2 i], ou[2 i + 1] = (u, v) (ov, om unused).
+hipError_t launch_flow_record(int Nx, int Ny, const double* px, const double* py, void* ou, void* ov, void* om,
+                              int dtype, int layout, hipStream_t s);
 
 hipError_t launch_dot_self(int64_t n, const double* x, RedBuf rb, double* gath, int rank, hipStream_t s);
 
@@ -293,6 +299,18 @@ hipError_t launch_div_scalar(int64_t n, double* x, const double* S, hipStream_t 
 // layout 0: out[3][n] = a, b, c; 1: out[n][2] = (a, b); dtype FOTO_F32 | FOTO_F64
 hipError_t launch_export(int64_t n, const double* a, const double* b, const double* c, void* out, int dtype,
                          int layout, hipStream_t s);
+// The frames of one k_frames launch, passed by value (no device scratch): frame k is
+// scale * ((1 - w) a + w b) of two planes of n doubles; w == 0 reads a alone, w == 1 b alone.
+constexpr int FRAMES_MAX = 128;
+struct FrameArgs {
+    const double* a[FRAMES_MAX];
+    const double* b[FRAMES_MAX];
+    double w[FRAMES_MAX];
+};
+// out[count][n] of dtype FOTO_U8 | FOTO_F32 | FOTO_F64, count <= FRAMES_MAX, one launch
+hipError_t launch_frames(const FrameArgs& fa, int count, int64_t n, double scale, void* out, int dtype,
+                         hipStream_t s);
+size_t dtype_bytes(int dtype);
 
 // The stream contract of every *_dev call: libfoto's streams are non-blocking, so the caller's
 // stream (NULL: the legacy null stream) and the own one are ordered by two events, made once per

@@ -1319,6 +1319,49 @@ hipError_t launch_flow_finish(int Nx, int Ny, const double* px, const double* py
     return launch_div2(Nx, Ny, u, v, m, 1, -1.0, s);   // m = -div(bc 'D') [u; v]
 }
 
+// One record of the flow path: k_flow_uv + k_div2(bc 'D', sign -1.0) + the export.  u, v of the
+// pixel and of its four neighbours are the same subtraction k_flow_uv stores, and the sum runs
+// in k_div2's order, so (u, v, m) carry the bits launch_flow_finish gives for these positions;
+// only the stores round (float32).  LAYOUT 0: three planes; 1: interleaved (u, v).
+template <class T, int LAYOUT>
+__global__ __launch_bounds__(NT) void k_flow_record(int Nx, int Ny, const double* __restrict__ px,
+                                                    const double* __restrict__ py, T* __restrict__ ou,
+                                                    T* __restrict__ ov, T* __restrict__ om) {
+    const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
+    if (i >= (int64_t)Nx * Ny) return;
+    const int y = (int)(i / Nx), x = (int)(i - (int64_t)y * Nx);
+    const double u = px[i] - (double)x;
+    const double v = py[i] - (double)y;
+    if (LAYOUT == 1) {
+        ou[2 * i] = (T)u;
+        ou[2 * i + 1] = (T)v;
+        return;
+    }
+    double s = 0.0;
+    acc_d1c(s, x, Nx, x > 0 ? px[i - 1] - (double)(x - 1) : 0.0, x < Nx - 1 ? px[i + 1] - (double)(x + 1) : 0.0, 1);
+    acc_d1c(s, y, Ny, y > 0 ? py[i - Nx] - (double)(y - 1) : 0.0, y < Ny - 1 ? py[i + Nx] - (double)(y + 1) : 0.0, 1);
+    ou[i] = (T)u;
+    ov[i] = (T)v;
+    om[i] = (T)(-1.0 * s);
+}
+
+template <class T>
+static hipError_t flow_record_t(int Nx, int Ny, const double* px, const double* py, void* ou, void* ov, void* om,
+                                int layout, hipStream_t s) {
+    const int nb = flat_blocks((int64_t)Nx * Ny);
+    if (layout == 0) k_flow_record<T, 0><<<nb, NT, 0, s>>>(Nx, Ny, px, py, (T*)ou, (T*)ov, (T*)om);
+    else k_flow_record<T, 1><<<nb, NT, 0, s>>>(Nx, Ny, px, py, (T*)ou, (T*)ov, (T*)om);
+    return hipGetLastError();
+}
+
+hipError_t launch_flow_record(int Nx, int Ny, const double* px, const double* py, void* ou, void* ov, void* om,
+                              int dtype, int layout, hipStream_t s) {
+    if (layout != 0 && layout != 1) return hipErrorInvalidValue;
+    if (dtype == FOTO_F32) return flow_record_t<float>(Nx, Ny, px, py, ou, ov, om, layout, s);
+    if (dtype == FOTO_F64) return flow_record_t<double>(Nx, Ny, px, py, ou, ov, om, layout, s);
+    return hipErrorInvalidValue;
+}
+
 }  // namespace foto
 
 namespace foto {

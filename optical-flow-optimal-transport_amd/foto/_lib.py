@@ -169,6 +169,12 @@ SIGNATURES = {
                                 ctypes.POINTER(BBOpts), _D, ctypes.POINTER(_P)]),
     "foto_bb_reset_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _I, _P, _D]),
     "foto_bb_flow_dev": (_I, [_P, _P, _I, _I, _P]),
+    # the transport path: density frames and the Nt - 1 partial flows
+    "foto_flow_path_from_phi": (_I, [_D, _I, _I, _I, _D, _D, _D]),
+    "foto_bb_frames": (_I, [_P, _D, _I, _Dbl, _D]),
+    "foto_bb_frames_dev": (_I, [_P, _D, _I, _Dbl, _P, _I, _P]),
+    "foto_bb_flow_path": (_I, [_P, _D, _D, _D]),
+    "foto_bb_flow_path_dev": (_I, [_P, _P, _I, _I, _P]),
     "foto_gn_plan_solve_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _P, _I, _I, _P,
                                     ctypes.POINTER(_I)]),
     "foto_warp_dev": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),

@@ -123,6 +123,47 @@ class BBSolver:
                                              ctypes.c_void_p(D.stream_handle(stream, out))))
         return out
 
+    # -------------------------------------------------------------- transport path
+    def frames(self, s, scale=1.0):
+        """Density frames [K, Ny, Nx] (float64, host) at plane positions ``s`` in [0, Nt-1] (an
+        int K: np.linspace(0, Nt-1, K)): scale * ((1 - w) rho_n + w rho_{n+1}) of the last
+        completed outer iteration's mu (before any: the linear initial path) -- foto_bb_frames.
+        An integer position with scale 1 is plane n bit for bit."""
+        from . import device as D
+        pos = D.frame_positions(s, self.Nt)
+        out = np.empty((pos.size, self.Ny, self.Nx))
+        self._check(self._L.foto_bb_frames(self._ctx, dptr(pos), int(pos.size), float(scale), dptr(out)))
+        return out
+
+    def frames_device(self, s, scale=1.0, out=None, dtype="float32", stream=None):
+        """frames() left on the device (foto_bb_frames_dev): a DeviceArray (or ``out``, any
+        contiguous device array) [K][Ny][Nx] of ``dtype`` uint8 | float32 | float64; uint8 is
+        255 * clip(x, 0, 1) rounded to nearest."""
+        from . import device as D
+        pos = D.frame_positions(s, self.Nt)
+        out, ptr, dcode = D.frames_target(out, dtype, pos.size, self.Ny, self.Nx)
+        self._check(self._L.foto_bb_frames_dev(self._ctx, dptr(pos), int(pos.size), float(scale),
+                                               ctypes.c_void_p(ptr), dcode,
+                                               ctypes.c_void_p(D.stream_handle(stream, out))))
+        return out
+
+    def flow_path(self):
+        """(u, v, m), each [Nt-1, Ny*Nx]: record n-1 is the flow after the first n trajectory
+        steps (flow() of the first n+1 planes of phi); the last record is flow()'s result."""
+        nxy = self.Nx * self.Ny
+        u, v, m = (np.empty((self.Nt - 1, nxy)) for _ in range(3))
+        self._check(self._L.foto_bb_flow_path(self._ctx, dptr(u), dptr(v), dptr(m)))
+        return u, v, m
+
+    def flow_path_device(self, out=None, dtype="float32", layout="planar", stream=None):
+        """flow_path() left on the device (foto_bb_flow_path_dev): Nt - 1 records laid out as
+        flow_device lays out its one, [Nt-1][3][Ny][Nx] or [Nt-1][Ny][Nx][2]."""
+        from . import device as D
+        out, ptr, dcode, lcode = D.path_target(out, dtype, layout, self.Nt, self.Ny, self.Nx)
+        self._check(self._L.foto_bb_flow_path_dev(self._ctx, ctypes.c_void_p(ptr), dcode, lcode,
+                                                  ctypes.c_void_p(D.stream_handle(stream, out))))
+        return out
+
     def _check(self, rc):
         return check(rc, self._L)
 

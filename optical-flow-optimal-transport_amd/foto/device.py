@@ -319,6 +319,63 @@ def export_target(out, dtype, layout, h, w):
     return out, ptr, _OUT_DTYPES[dtype], _LAYOUTS[layout]
 
 
+_FRAME_DTYPES = {"uint8": _lib.FOTO_U8, "float32": _lib.FOTO_F32, "float64": _lib.FOTO_F64}
+
+
+def _shaped_target(out, dtype, codes, shape, what):
+    """(DeviceArray or the caller's object, pointer, dtype code): a new DeviceArray of ``shape``
+    or the caller's ``out``, which must be C-contiguous device memory of that dtype and shape.
+    ValueError before the library is touched."""
+    if dtype not in codes:
+        dtype = np.dtype(dtype).name
+    if dtype not in codes:
+        raise ValueError(f"dtype {dtype!r}: {what} are " + " or ".join(repr(k) for k in codes))
+    if out is None:
+        out = DeviceArray(shape, dtype)
+        return out, out.ptr, codes[dtype]
+    if not isinstance(out, DeviceArray):
+        runtime_check()
+    ptr, typestr, oshape, strides, _ = _interface(out)
+    if typestr != _typestr(dtype) or tuple(oshape) != tuple(shape):
+        raise ValueError(f"out: expected {dtype} of shape {tuple(shape)}, got {typestr} of shape {tuple(oshape)}")
+    if strides is not None:
+        acc = np.dtype(dtype).itemsize
+        for s, st in zip(reversed(shape), reversed(tuple(strides))):
+            if s > 1 and st != acc:
+                raise ValueError("out must be C-contiguous")
+            acc *= s
+    return out, ptr, codes[dtype]
+
+
+def frame_positions(s, Nt):
+    """The plane positions of a frames export as a float64 vector: an int K means
+    np.linspace(0, Nt - 1, K), a sequence is taken as it is (one dimension)."""
+    if isinstance(s, (int, np.integer)) and not isinstance(s, (bool, np.bool_)):
+        if s < 1:
+            raise ValueError(f"frames: K = {s} must be >= 1")
+        return np.linspace(0.0, float(Nt - 1), int(s))
+    a = np.asarray(s, dtype=np.float64)
+    if a.ndim != 1:
+        raise ValueError(f"frames: s of shape {a.shape}; an int K or a 1-D sequence of plane positions")
+    return np.ascontiguousarray(a)
+
+
+def frames_target(out, dtype, count, h, w):
+    """(out, pointer, dtype code) of a frames export: [count][h][w] of uint8 | float32 | float64."""
+    return _shaped_target(out, dtype, _FRAME_DTYPES, (int(count), h, w), "frames")
+
+
+def path_target(out, dtype, layout, Nt, h, w):
+    """(out, pointer, dtype code, layout code) of a flow-path export: Nt - 1 records of
+    export_target's shape, [Nt-1][3][h][w] planar or [Nt-1][h][w][2] interleaved."""
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout {layout!r}: 'planar' ([Nt-1][3][h][w] = u, v, m) or 'interleaved' "
+                         "([Nt-1][h][w][2] = (u, v))")
+    shape = (Nt - 1, 3, h, w) if layout == "planar" else (Nt - 1, h, w, 2)
+    out, ptr, code = _shaped_target(out, dtype, _OUT_DTYPES, shape, "flow records")
+    return out, ptr, code, _LAYOUTS[layout]
+
+
 # -------------------------------------------------------------------- convenience
 
 def bb_flow(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, normalize=False,
@@ -341,6 +398,36 @@ def bb_flow(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100
     with bb.BBSolver.from_device(a, b, Nt, r=r, reg_epsilon=reg_epsilon, normalize=normalize, stream=st, **opts) as s:
         s.iterate(max_it, convergence_tol=convergence_tol, stop_rules=True)
         return s.flow_device(out=out, dtype=dtype, layout=layout, stream=st)
+
+
+def bb_path(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, frames=None, normalize=False,
+            frame_dtype="float32", dtype="float32", layout="planar", frames_out=None, out=None, stream=None,
+            **opts):
+    """bb_flow with the transport path instead of its end point: the same solve on the cached
+    context, then ``frames`` in-between density frames (an int K: np.linspace(0, Nt-1, K), or a
+    sequence of plane positions; default Nt: every plane) and the Nt - 1 partial flows, both left
+    on the device.  With ``normalize`` the frames are scaled by the frame-0 sum, back to the
+    intensity range of ``f0``.  Returns (frames [K][h][w], flow path [Nt-1][3][h][w] or
+    [Nt-1][h][w][2]); the last flow record is bb_flow's result."""
+    from . import bb
+    a, b = _pair(f0, f1)
+    st = stream_handle(stream, f0, f1)
+    pos = Nt if frames is None else frames
+
+    def run(s):
+        s.iterate(max_it, convergence_tol=convergence_tol, stop_rules=True)
+        fr = s.frames_device(pos, scale=s.sums[0] if normalize else 1.0, out=frames_out, dtype=frame_dtype, stream=st)
+        return fr, s.flow_path_device(out=out, dtype=dtype, layout=layout, stream=st)
+
+    if bb._cache_enabled(opts):
+        s = bb.cached_solver_device(a, b, Nt, r, reg_epsilon, normalize=normalize, stream=st, **opts)
+        try:
+            return run(s)
+        except BaseException:
+            bb.drop_cached(s)
+            raise
+    with bb.BBSolver.from_device(a, b, Nt, r=r, reg_epsilon=reg_epsilon, normalize=normalize, stream=st, **opts) as s:
+        return run(s)
 
 
 def gn_flow(f0, f1, alpha, lam, *, dtype="float32", layout="planar", out=None, stream=None):

@@ -101,6 +101,16 @@ def flow_from_phi(phi, Nt, Nx, Ny):
     return u, v, m
 
 
+def flow_path_from_phi(phi, Nt, Nx, Ny):
+    """(u, v, m), each [Nt-1, Ny*Nx]: record n-1 is utils.opticalflow_from_benamoubrenier of the
+    first n+1 planes of phi (the displacement after n trajectory steps); the last record has the
+    bits of ``flow_from_phi``."""
+    x = f64(phi, Nt * Nx * Ny, "phi")
+    u, v, m = (np.empty((max(Nt - 1, 0), Nx * Ny)) for _ in range(3))
+    check(lib().foto_flow_path_from_phi(dptr(x), Nt, Nx, Ny, dptr(u), dptr(v), dptr(m)))
+    return u, v, m
+
+
 def _bc(bc):
     if bc not in ("N", "D"):
         raise NotImplementedError("These boundary conditions are not implemented")
