@@ -48,10 +48,7 @@ constexpr int GQ_QB = 512;                 // half-bins of the solution table (t
 constexpr int GQ_QN = 32;                  // Chebyshev coefficients per table bin
 constexpr int GQ_TAB = GQ_QN * GQ_QB;      // [coefficient][bin]
 constexpr size_t GQ_TAB_BYTES = sizeof(double) * GQ_TAB;   // [coefficient][half-bin]
-#ifndef FOTO_GQ_CGNTH
-#define FOTO_GQ_CGNTH 256
-#endif
-constexpr int GQ_CGNTH = FOTO_GQ_CGNTH;     // CG block (A/B switch): GQ_NODES / GQ_CGNTH nodes per thread
+constexpr int GQ_CGNTH = 256;              // CG block: GQ_NODES / GQ_CGNTH nodes per thread
 
 struct GqState {
     int K;          // CG iterations (scipy's count)
@@ -177,14 +174,8 @@ __device__ __forceinline__ double dbl_dpp_rows(double v) {
 constexpr int GQ_PXB = 12;
 // (round 5: 8 x 4 instead of 16 x 2 -- the same voxel order per lane, so the same sums bit for
 // bit, at 120 instead of 153 VGPRs: four waves per SIMD, 36.6 -> 35.6 us, profiles/r05_hist_ab.txt)
-#ifndef FOTO_GQ_PE
-#define FOTO_GQ_PE 8
-#endif
-#ifndef FOTO_GQ_PB
-#define FOTO_GQ_PB 4
-#endif
-constexpr int GQ_PE = FOTO_GQ_PE;          // voxels per lane per batch
-constexpr int GQ_PB = FOTO_GQ_PB;          // batches per chunk (the wave reduction is per chunk)
+constexpr int GQ_PE = 8;                   // voxels per lane per batch
+constexpr int GQ_PB = 4;                   // batches per chunk (the wave reduction is per chunk)
 constexpr int GQ_PCH = 64 * GQ_PE * GQ_PB; // voxels per chunk
 struct GqChunk {
     int bin, start, len;
@@ -327,9 +318,6 @@ __global__ __launch_bounds__(64) void k_gq_exact(SpecTab T, const unsigned* __re
 }
 
 // one wave per chunk (grid-stride): the chunk's 16 moment sums -> part[chunk][m]
-#ifndef FOTO_GQ_PERM_NT
-#define FOTO_GQ_PERM_NT 0   // 1: the bin-order list (re-read next iteration) loaded non-temporal
-#endif
 __global__ __launch_bounds__(256) void k_gq_hist_perm(SpecTab T, const double* __restrict__ bh, const unsigned* __restrict__ perm,
                                                       const GqChunk* __restrict__ chunks, int nchunks,
                                                       const GqBins* __restrict__ B, const GqExact* __restrict__ X,
@@ -355,11 +343,7 @@ __global__ __launch_bounds__(256) void k_gq_hist_perm(SpecTab T, const double* _
 #pragma unroll
             for (int e = 0; e < GQ_PE; ++e) {
                 const int i = (bt * GQ_PE + e) * 64 + lane;
-#if FOTO_GQ_PERM_NT
-                pv[e] = (i < len) ? __builtin_nontemporal_load(&perm[start + i]) : 0xffffffffu;
-#else
                 pv[e] = (i < len) ? perm[start + i] : 0xffffffffu;
-#endif
             }
             double x[GQ_PE], rm[GQ_PE], mxv[GQ_PE];
 #pragma unroll
@@ -1319,15 +1303,10 @@ __global__ __launch_bounds__(GQ_XNTH) void k_gq_xhat(SpecTab T, const double* __
 // at 2 waves per SIMD; the element cost is now a few compares and 512-thread blocks keep 4 waves
 // per SIMD (2 blocks per CU at <= 80 KB of LDS each: ql <= 17 rows).
 constexpr int GQ_TFNTH = 512;
-#ifndef FOTO_TF_WPE
-#define FOTO_TF_WPE 4
-#endif
-#ifndef FOTO_TF_PF
-#define FOTO_TF_PF 4
-#endif
-constexpr int GQ_TFPF = FOTO_TF_PF;   // b^ loads kept in flight ahead of the element being finished
+constexpr int GQ_TFWPE = 4;   // waves per SIMD
+constexpr int GQ_TFPF = 4;    // b^ loads kept in flight ahead of the element being finished
 template <int NTT>
-__global__ __launch_bounds__(GQ_TFNTH) __attribute__((amdgpu_waves_per_eu(FOTO_TF_WPE))) void k_dct_t_inv_gq(
+__global__ __launch_bounds__(GQ_TFNTH) __attribute__((amdgpu_waves_per_eu(GQ_TFWPE))) void k_dct_t_inv_gq(
         SpecTab T, const double* __restrict__ Ch, const double* __restrict__ bh, const double* __restrict__ tab,
         const GqState* __restrict__ S, const GqBins* __restrict__ Bg, double ic1, double* __restrict__ out, int ql) {
     constexpr int H = TCol<NTT>::H;

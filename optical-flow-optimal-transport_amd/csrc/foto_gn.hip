@@ -423,14 +423,8 @@ hipError_t launch_gn_pcg_upd(int w, int h, int k, const double* fx, const double
 // atomics, no ticket), and every kernel that needs the sum adds the partials in the same
 // fixed order in each of its blocks, so all blocks take identical decisions.
 
-#ifndef FOTO_MG_COARSE
-#define FOTO_MG_COARSE 1024
-#endif
-#ifndef FOTO_MG_CSWEEPS
-#define FOTO_MG_CSWEEPS 12   // 48 -> 12: same PCG counts at 640x480, 584x388, 320x240 (r02 A/B), 12 % less PCG time
-#endif
-constexpr int MG_COARSE = FOTO_MG_COARSE;   // cells of the coarsest level (one block, one cell per thread)
-constexpr int MG_CSWEEPS = FOTO_MG_CSWEEPS;
+constexpr int MG_COARSE = 1024;    // cells of the coarsest level (one block, one cell per thread)
+constexpr int MG_CSWEEPS = 12;     // coarsest-level sweeps (DESIGN.md 3.5 has the A/B against 48)
 constexpr double MG_OMEGA = 0.8;
 constexpr int GT_X = 32, GT_Y = 16;   // fine tile of the level kernels (256 threads, 2 cells each)
 
@@ -871,12 +865,6 @@ struct MGUpd {
 //   r = f - A x over the tile + 1 halo cell                                   -> LDS; x -> xg
 //   fc = R r = P^T r / 4 for the tile's GT_Y/2 x GT_X/2 coarse cells (4 x 4 taps) -> fc
 // UPD (level 0 of a PCG iteration): f is r' = r - alpha q, formed here (MGUpd above)
-#ifndef FOTO_MG_B2LATE
-#define FOTO_MG_B2LATE 1
-#endif
-#ifndef FOTO_MG_RSALIAS
-#define FOTO_MG_RSALIAS 1
-#endif
 template <bool UPD, bool RC = false>
 __global__ __launch_bounds__(NT) void k_mg_down2(MGLev L, int wc, int hc, const CGScal* S,
                                                  const double* __restrict__ f, double* __restrict__ xg,
@@ -888,20 +876,16 @@ __global__ __launch_bounds__(NT) void k_mg_down2(MGLev L, int wc, int hc, const 
     constexpr int C1 = (XH * XW + NT - 1) / NT, C2 = (RH * RW + NT - 1) / NT;
     __shared__ double xs[3][XH][XW];
     __shared__ double fs[3][XH][XW];
-#if FOTO_MG_RSALIAS
     // r lives in fs's space (fs is dead once stage 2 has read it; one barrier more): 49 -> 35 KB
     // of LDS per block, four blocks per CU instead of three
     static_assert(3 * RH * RW <= 3 * XH * XW, "r fits f's space");
     double (*rs)[RH][RW] = reinterpret_cast<double (*)[RH][RW]>(&fs[0][0][0]);
-#else
-    __shared__ double rs[3][RH][RW];
-#endif
     const int done = S->done;
     const int w = L.w, h = L.h;
     const int64_t n = (int64_t)w * h;
     const int tiles_x = (w + GT_X - 1) / GT_X;
     const int x0 = (blockIdx.x % tiles_x) * GT_X, y0 = (blockIdx.x / tiles_x) * GT_Y;
-    // stage-2 cells' B (tile + 1 halo); level 0 of a PCG iteration (UPD, FOTO_MG_B2LATE=1): after
+    // stage-2 cells' B (tile + 1 halo); level 0 of a PCG iteration (UPD): after
     // stage 1 -- held from the start beside the stage-1 loads it took 150 VGPRs (3 waves per SIMD)
     static_assert(!RC || UPD, "RC: the level-0 leg of a PCG iteration");
     constexpr int NB = RC ? 3 : 6;   // per stage-2 cell: (fx, fy, f2) or B
@@ -923,7 +907,7 @@ __global__ __launch_bounds__(NT) void k_mg_down2(MGLev L, int wc, int hc, const 
             }
         }
     };
-    constexpr bool B2LATE = UPD && FOTO_MG_B2LATE;
+    constexpr bool B2LATE = UPD;
     if constexpr (!B2LATE) load_b2();
     // stage-1 cells' f (UPD: r and q) and D^-1 (tile + 2 halo; RC: the coefficients it is made of)
     constexpr int ND = RC ? 3 : 6;
@@ -1032,9 +1016,7 @@ __global__ __launch_bounds__(NT) void k_mg_down2(MGLev L, int wc, int hc, const 
         }
         rv[k][0] = r0; rv[k][1] = r1; rv[k][2] = r2;
     }
-#if FOTO_MG_RSALIAS
-    __syncthreads();   // (every read of fs done)
-#endif
+    __syncthreads();   // (every read of fs done: r takes its space)
 #pragma unroll
     for (int k = 0; k < C2; ++k) {
         const int c = threadIdx.x + k * NT;
@@ -1413,9 +1395,6 @@ __global__ __launch_bounds__(1024) void k_mg_tail(MGTail T, const CGScal* S) {
 // (i * syncs + s + 1) * blocks arrivals (i = the PCG iteration index, S->pad[0]); the host zeroes
 // it with the solve's scalars.  A poll that never completes (blocks not co-resident -- 64 small
 // blocks on a 256-CU device) gives up after ~1 s and flags S->pad[1] instead of hanging.
-#ifndef FOTO_PT_SLEEP
-#define FOTO_PT_SLEEP 2   // s_sleep between two polls of the arrival counter (A/B builds)
-#endif
 constexpr int MG_PT_TILES = 64;     // a level joins the tail when it has at most this many tiles
 constexpr int MG_PT_MAX = 8;
 struct MGPTail {
@@ -1442,9 +1421,7 @@ __device__ __forceinline__ void pt_grid_sync(unsigned* counter, unsigned target,
         __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         int spins = 0;
         while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-#if FOTO_PT_SLEEP
-            __builtin_amdgcn_s_sleep(FOTO_PT_SLEEP);
-#endif
+            __builtin_amdgcn_s_sleep(2);   // between two polls of the arrival counter
             if (++spins > (1 << 20)) {   // (~1 s: a barrier normally completes in microseconds)   // never co-resident: flag it, do not hang the device
                 __hip_atomic_store(&S->pad[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 break;
@@ -2185,7 +2162,7 @@ static int gn_plan_init(foto_gn_plan* P) {
     P->nb_pix = flat_blocks((int64_t)n);
     {
         const char* e = getenv("FOTO_MG_TAIL");
-        P->tail = e && atoi(e) != 0 && MG_COARSE <= 1024;   // (k_mg_tail: one coarsest cell per thread)
+        P->tail = e && atoi(e) != 0;
     }
     // level geometry
     int lw = w, lh = h;

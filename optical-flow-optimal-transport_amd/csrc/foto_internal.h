@@ -58,6 +58,16 @@ constexpr int NT = 256;  // threads per block for every kernel
 inline int march_blocks(const Geo& g) { return ((g.Nx + TX - 1) / TX) * ((g.Ny + TY - 1) / TY); }
 inline int flat_blocks(int64_t n) { return (int)((n + NT - 1) / NT); }
 
+inline int cus_count() {   // CUs of the current device (cached per device ordinal)
+    static int cache[64] = {0};
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess) return cus;
+    if (dev >= 0 && dev < 64 && cache[dev] > 0) return cache[dev];
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 256;
+    if (dev >= 0 && dev < 64) cache[dev] = cus;
+    return cus;
+}
+
 // Device-side CG scalars (one per shard).  Written only by the last block of a kernel
 // (or by block 0 for the done flag); read by later kernels.
 struct CGScal {

@@ -134,20 +134,12 @@ __device__ __forceinline__ double row_L(const Geo& g, int t, int y, int x, doubl
 // Block -> tile for the column marches.  Workgroups are dispatched to the 8 XCDs round robin
 // (block b on XCD b % 8), each with its own L2; give every XCD a contiguous range of row-major
 // tiles instead, so the tile below a tile (ntx blocks later) is read through the same L2 and
-// the y-halo rows hit there instead of being fetched from HBM again (FOTO_XCD_SWIZZLE=0 in
-// the build: plain order, for A/B runs).
-#ifndef FOTO_XCD_SWIZZLE
-#define FOTO_XCD_SWIZZLE 1
-#endif
+// the y-halo rows hit there instead of being fetched from HBM again.
 __device__ __forceinline__ int xcd_tile(int b) {
-#if FOTO_XCD_SWIZZLE
     constexpr int NXCD = 8;
     const int nb = gridDim.x, per = nb / NXCD, rem = nb % NXCD;
     const int xcd = b % NXCD, local = b / NXCD;
     return xcd * per + min(xcd, rem) + local;
-#else
-    return b;
-#endif
 }
 
 template <class Val, class Body>
@@ -420,10 +412,7 @@ hipError_t launch_div_st(const Geo& g, const double* wt, const double* wx, const
 
 // F = div_st(mu - r q); F[t=0] -= rho0 - rho[0] + r a[0]; F[t=Nt-1] += rhoT - rho + r a
 // (benamou_brenier.py:64-82, dt = 1).  F.F partial -> gath[rank] (= b.b for CG).
-#ifndef FOTO_RHS_TY
-#define FOTO_RHS_TY 1
-#endif
-constexpr int RHS_TY = FOTO_RHS_TY;    // rows per block: the y-neighbour rows a tile re-reads are 2 / RHS_TY extra
+constexpr int RHS_TY = 1;              // rows per block: the y-neighbour rows a tile re-reads are 2 / RHS_TY extra
 constexpr int RHS_NT = TX * RHS_TY;
 __global__ __launch_bounds__(RHS_NT) void k_rhs(Geo g, const double* __restrict__ mut, const double* __restrict__ mux,
                                             const double* __restrict__ muy, const double* __restrict__ qt,
@@ -535,9 +524,6 @@ __device__ __noinline__ double proj_trig_z(double al, double rho) {
 // fp32 log2 / exp2 (~1e-7 relative), two Newton steps y <- y (4 - S' y^3) / 3 (quadratic:
 // rounding level), then S^(1/3) = S' y^2 2^q and S^(-1/3) = y 2^-q.  Within 2-3 ulp of the
 // rounded values (the reference's x ** (1/3) is itself within an ulp of them).
-#ifndef FOTO_PROJ_FAST
-#define FOTO_PROJ_FAST 1
-#endif
 __device__ __forceinline__ void cbrt_pair(double S, double& c, double& ic) {
     const int e = __builtin_amdgcn_frexp_exp(S);
     const double m = __builtin_amdgcn_frexp_mant(S);
@@ -567,7 +553,6 @@ __device__ __forceinline__ void project_K(double al, double b1, double b2, doubl
         const double S = 0.3535533905932738 * rho +
                          0.16666666666666666 * sqrt(1.3333333333333333 * (al * al * al) + 4.0 * (al * al) +
                                                     4.5 * (rho * rho) + 4.0 * al + 1.3333333333333333);
-#if FOTO_PROJ_FAST
         double c, ic;
         if (S > 0.0 && S <= 1.7976931348623157e308) {
             cbrt_pair(S, c, ic);
@@ -576,10 +561,6 @@ __device__ __forceinline__ void project_K(double al, double b1, double b2, doubl
             ic = 1.0 / c;
         }
         const double zh = fma(-0.3333333333333333 * ap1, ic, c);
-#else
-        const double c = cbrt(S);
-        const double zh = (-0.3333333333333333 * ap1) / c + c;
-#endif
         aH = -(zh * zh);
         rH = SQRT2 * zh;
     } else {
@@ -589,14 +570,9 @@ __device__ __forceinline__ void project_K(double al, double b1, double b2, doubl
     }
     oa = aH;
     if (rho > 0.0) {
-#if FOTO_PROJ_FAST
         const double ir = 1.0 / rho;
         o1 = rH * (b1 * ir);
         o2 = rH * (b2 * ir);
-#else
-        o1 = rH * (b1 / rho);
-        o2 = rH * (b2 / rho);
-#endif
     } else {   // atan2(+-0, +0) = +-0, atan2(+-0, -0) = +-pi
         o1 = signbit(b1) ? -rH : rH;
         o2 = 0.0;
@@ -731,44 +707,13 @@ hipError_t launch_q_from_phi(const Geo& g, const double* phi, const double* mut,
 // 0-2) also take the 148 ring voxels.  Chunks of FOTO_PR_TCH planes (default 16) give the
 // grid more blocks than resident slots (a full-length march leaves a one-sixth-full second
 // round at 640 x 480).
-#ifndef FOTO_PR_Y
-#define FOTO_PR_Y 8
-#endif
-// mu' is read again only by the next outer iteration's prox, ~1.5 GB of other traffic later:
-// stored non-temporal it does not displace the lines the next kernels read (F, phi) --
-// 1646 -> 1655 it/s, the prox launch itself +1 us (A/B, profiles/r04n_ab_prox_nt.txt);
-// 2: F non-temporal too (the x-DCT reads it next: no better); 0: plain stores
-#ifndef FOTO_PR_NT
-#define FOTO_PR_NT 1
-#endif
-// The old mu is dead after this kernel: its loads are non-temporal.  Own voxels only (1):
-// 1675-1688 -> 1708-1719 it/s, the DCT chain after it 130 -> 124 us (F stays cached for the
-// x-DCT); the ring voxels' loads too (2, default): 1690-1716 -> 1703-1740, the prox launch
-// unchanged (A/B, profiles/r04n_ab_nt_loads.txt).  0: plain loads.
-#ifndef FOTO_PR_NTLD
-#define FOTO_PR_NTLD 2
-#endif
-#ifndef FOTO_PR_NTPHI
-#define FOTO_PR_NTPHI 0  // 1: phi loaded non-temporal (prox 165 -> 173 us: its halo is re-read)
-#endif
-#ifndef FOTO_PR_X
-#define FOTO_PR_X 64
-#endif
-// own voxels per thread (FOTO_PR_VPT=2 with FOTO_PR_Y=16: a 64 x 16 tile on 512 threads, rows y and
-// y + 8 per thread, the ring 164 voxels for 1024 instead of 148 for 512; 81.5 KB of LDS, so one
-// block per CU at up to 256 VGPRs)
-#ifndef FOTO_PR_VPT
-#define FOTO_PR_VPT 1
-#endif
-// 1: tiles whose phi region lies inside the plane run a copy of the march without bound tests
-// (prox_rhs_body<.., true>); 0: every tile runs the general one (A/B builds)
-#ifndef FOTO_PR_CHFAST
-#define FOTO_PR_CHFAST 0   // 1: block order tile-major with the chunks fastest (A/B builds)
-#endif
-#ifndef FOTO_PR_INTERIOR
-#define FOTO_PR_INTERIOR 1
-#endif
-constexpr int PR_X = FOTO_PR_X, PR_Y = FOTO_PR_Y, PR_VPT = FOTO_PR_VPT;
+// Cache policy of the streams.  mu' is read again only by the next outer iteration's prox,
+// ~1.5 GB of other traffic later: stored non-temporal it does not displace the lines the next
+// kernels read (F, phi; F itself is stored plainly, the x-DCT reads it next).  The old mu is dead
+// after this kernel: its loads, the own and the ring voxels', are non-temporal, so F stays cached
+// for the x-DCT.  phi is loaded plainly: its halo is re-read.  (A/B figures: DESIGN.md 3.5.)
+constexpr int PR_X = 64, PR_Y = 8;
+constexpr int PR_VPT = 1;                                   // own voxels per thread (the march is written over v < PR_VPT)
 constexpr int PR_NT = PR_X * PR_Y / PR_VPT;                 // 512 threads (64 x 8)
 constexpr int PR_YV = PR_Y / PR_VPT;                        // rows between a thread's own voxels
 constexpr int PR_PW = PR_X + 2, PR_PH = PR_Y + 2;         // stepB region
@@ -778,7 +723,7 @@ constexpr int PR_FN = PR_FW * PR_FH;                      // 816 phi values per 
 constexpr int PR_FR = (PR_FN + PR_NT - 1) / PR_NT;        // phi loads per thread per plane
 static_assert(PR_X == 64 && PR_NT <= 1024 && PR_HALO <= PR_NT && PR_Y % PR_VPT == 0,   // (32 x 16, 16 x 32, 32 x 8: slower, r03)
               "whole rows per thread, ring voxels on the first threads");
-constexpr int PR_WPE = PR_VPT == 1 ? 4 : 2;               // waves per SIMD (VGPR budget 128 / 256)
+constexpr int PR_WPE = 4;                                 // waves per SIMD (VGPR budget 128)
 
 // EDGE: the deferred-edge variant (sharded); the single-shard instantiation carries none of its
 // code (its extra registers spilled the kernel at the 128-VGPR cap: 171 -> 184 us)
@@ -840,11 +785,7 @@ __device__ __forceinline__ void prox_rhs_body(
         const bool ok = t0 + p >= 0 && p <= pz + 1 && t0 + p < Nt;
 #pragma unroll
         for (int j = 0; j < PR_FR; ++j)
-#if FOTO_PR_NTPHI == 1
-            v[j] = (ok && fin[j]) ? __builtin_nontemporal_load(&phi[p * nxy + foff[j]]) : 0.0;
-#else
             v[j] = (ok && fin[j]) ? phi[p * nxy + foff[j]] : 0.0;
-#endif
     };
     auto store_phi_from = [&](int p, const double (&v)[PR_FR]) {
 #pragma unroll
@@ -861,25 +802,17 @@ __device__ __forceinline__ void prox_rhs_body(
         if (p > pz) return;
 #pragma unroll
         for (int v = 0; v < PR_VPT; ++v) {
-#if FOTO_PR_NTLD
             if (own[v]) {   // (the old mu is dead after this kernel)
                 om[v][0] = __builtin_nontemporal_load(&mut[p * nxy + ooff[v]]);
                 om[v][1] = __builtin_nontemporal_load(&mux[p * nxy + ooff[v]]);
                 om[v][2] = __builtin_nontemporal_load(&muy[p * nxy + ooff[v]]);
             }
-#else
-            if (own[v]) { om[v][0] = mut[p * nxy + ooff[v]]; om[v][1] = mux[p * nxy + ooff[v]]; om[v][2] = muy[p * nxy + ooff[v]]; }
-#endif
         }
-#if FOTO_PR_NTLD >= 2
         if (hal) {
             hm[0] = __builtin_nontemporal_load(&mut[p * nxy + hoff]);
             hm[1] = __builtin_nontemporal_load(&mux[p * nxy + hoff]);
             hm[2] = __builtin_nontemporal_load(&muy[p * nxy + hoff]);
         }
-#else
-        if (hal) { hm[0] = mut[p * nxy + hoff]; hm[1] = mux[p * nxy + hoff]; hm[2] = muy[p * nxy + hoff]; }
-#endif
     };
     // stepB / stepC at stepB-region position (px, py) of local plane p (k_prox's body)
     auto stepb = [&](int p, int px, int py, int xg, int yg, const double (&m)[3], double (&w)[3], double& n0o,
@@ -924,15 +857,9 @@ __device__ __forceinline__ void prox_rhs_body(
                 stepb(p, opx, opy[v], ox, oy[v], mo[v], w, n0, a, gt, gx, gy, nu);
                 if (mine) {
                     const int64_t i = p * nxy + ooff[v];
-#if FOTO_PR_NT
                     __builtin_nontemporal_store(nu[0], &nut[i]);
                     __builtin_nontemporal_store(nu[1], &nux[i]);
                     __builtin_nontemporal_store(nu[2], &nuy[i]);
-#else
-                    nut[i] = nu[0];
-                    nux[i] = nu[1];
-                    nuy[i] = nu[2];
-#endif
                     const double gg = gx * gx + gy * gy;
                     num += n0 * fabs(gt + 0.5 * gg);
                     den += n0 * gg;
@@ -1016,11 +943,7 @@ __device__ __forceinline__ void prox_rhs_body(
                         (INTERIOR || yv < Ny - 1) ? WY[ci + PR_PW] : 0.0);
                 if (tn == 0) s -= (rho0[oo] - bcm[v]) + r * bcq[v];
                 if (tn == Nt - 1) s += (rhoT[oo] - bcm[v]) + r * bcq[v];
-#if FOTO_PR_NT >= 2
-                __builtin_nontemporal_store(s, &F[n * nxy + oo]);
-#else
                 F[n * nxy + oo] = s;
-#endif
                 ff += s * s;
             }
             wtm[v] = wtc[v];
@@ -1049,21 +972,14 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(PR_WPE)))
     const int Nx = g.Nx, Ny = g.Ny;
     const int ntx = (Nx + PR_X - 1) / PR_X, ntiles = ntx * ((Ny + PR_Y - 1) / PR_Y);
     const int lin = xcd_tile(blockIdx.x);
-#if FOTO_PR_CHFAST
-    // a tile's chunks adjacent in the block order (one XCD, resident together)
-    const int nch = (g.nloc + tch - 1) / tch;
-    const int tile = lin / nch, ch = lin - tile * nch;
-#else
     const int ch = lin / ntiles, tile = lin - ch * ntiles;
-#endif
     const int x0 = (tile % ntx) * PR_X, y0 = (tile / ntx) * PR_Y;
     double num, den, ff;
-#if FOTO_PR_INTERIOR
+    // tiles whose phi region lies inside the plane run a copy of the march without bound tests
     if (x0 >= 2 && x0 + PR_X + 2 <= Nx && y0 >= 2 && y0 + PR_Y + 2 <= Ny)
         prox_rhs_body<EDGE, true>(g, phi, mut, mux, muy, nut, nux, nuy, rho0, rhoT, r, inv_r, F, tch, defer_lo,
                                   defer_hi, wt_out, edge, wt_pre, fr, wb, ch, x0, y0, num, den, ff);
     else
-#endif
         prox_rhs_body<EDGE, false>(g, phi, mut, mux, muy, nut, nux, nuy, rho0, rhoT, r, inv_r, F, tch, defer_lo,
                                    defer_hi, wt_out, edge, wt_pre, fr, wb, ch, x0, y0, num, den, ff);
     double v[3] = {num, den, ff}, tot[3];

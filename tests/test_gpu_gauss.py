@@ -118,7 +118,7 @@ def test_gauss_sharded_small_grids_match_single(Nt, Nx, Ny, vr):
 
 @pytest.mark.parametrize("name", ["bb_c1.npz", "bb_c2s.npz"])
 def test_dct_xt_fused_opt_in(gold, monkeypatch, name):
-    """FOTO_DCT_XT=1 (opt-in, measured slower: foto_spectral.hip): the single-shard Gauss solve's
+    """FOTO_DCT_XT=1 (opt-in, measured slower: foto_dct.hip): the single-shard Gauss solve's
     3-D DCT as (x, t) then y and its inverse as y then (t, x), against the default x, y, t
     passes on the same pair -- the same transform up to rounding, which six CG solves amplify:
     CG counts equal, crit to 1e-9, phi to 1e-8 of max|phi| (tests/test_gpu_parity.py's CG bar;

@@ -3,7 +3,7 @@
 // |FFT - GEMM| / max |GEMM|, round trip |inv(fwd(x)) - x| / max |x|, and time per pass.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off \
 //       -I../optical-flow-optimal-transport_amd/csrc dct_check.hip -o dct_check
-#include "../optical-flow-optimal-transport_amd/csrc/foto_spectral.hip"
+#include "../optical-flow-optimal-transport_amd/csrc/foto_dct.hip"
 #include <cstdio>
 #include <vector>
 namespace foto { void set_error(const char*, ...) {} }

@@ -5,6 +5,7 @@
 // and beta compared with the product kernel's.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off \
 //       -I../optical-flow-optimal-transport_amd/csrc gqcg_lab.hip -o gqcg_lab
+#include "../optical-flow-optimal-transport_amd/csrc/foto_dct.hip"
 #include "../optical-flow-optimal-transport_amd/csrc/foto_spectral.hip"
 #include <cstdio>
 #include <cstdlib>

@@ -6,6 +6,7 @@
 // wave takes the slowest lane's count.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off \
 //       -I../optical-flow-optimal-transport_amd/csrc gqnodes_lab.hip -o gqnodes_lab
+#include "../optical-flow-optimal-transport_amd/csrc/foto_dct.hip"
 #include "../optical-flow-optimal-transport_amd/csrc/foto_spectral.hip"
 #include <cstdio>
 #include <cstdlib>
