@@ -74,6 +74,13 @@ int foto_flow_from_phi(const double* phi, int Nt, int Nx, int Ny, double* u, dou
  * utils.reconstructTrajectory (utils.py:63-97) and m = -div('D')[u; v] (utils.py:181).
  * u, v, m: each [Nt-1][Ny*Nx]; record Nt-2 carries the bits of foto_flow_from_phi.       */
 int foto_flow_path_from_phi(const double* phi, int Nt, int Nx, int Ny, double* u, double* v, double* m);
+/* Test entry: the records of foto_bb_track (below) from a caller's phi, without a context:
+ * utils.reconstructTrajectory(x, y, un, vn, Nx, Ny, n+1) (utils.py:44-99) for M start points
+ * pts[M][2] = (x, y), un / vn = grad('N') of the phi planes.  out: [Nt-1][M][2] (all_steps = 1) or
+ * [M][2] (all_steps = 0).  FOTO_ERR_ARG (before any device is touched): a null pointer, Nt < 2,
+ * M < 1 or > 2^31 - 1, all_steps not 0 / 1.                                                      */
+int foto_track_from_phi(const double* phi, int Nt, int Nx, int Ny, const double* pts, int64_t M,
+                        int all_steps, double* out);
 
 /* ------------------------------------------------------------------ BB solver context
  * benamou_brenier.solve (benamou_brenier.py:151-271) split into create / iterate /
@@ -387,6 +394,29 @@ int foto_bb_frames_dev(foto_bb_ctx* c, const double* s, int count, double scale,
  * from the float64 u, v).  FOTO_ERR_STATE before any outer iteration has run.               */
 int foto_bb_flow_path(foto_bb_ctx* c, double* u, double* v, double* m);
 int foto_bb_flow_path_dev(foto_bb_ctx* c, void* out, int dtype, int layout, void* stream);
+/* Point tracking, the Lagrangian half of the flow path: utils.reconstructTrajectory(xStart, yStart,
+ * un, vn, Nx, Ny, Nt) (utils.py:44-99) for M arbitrary start points instead of the pixel centres.
+ * pts[M][2] = (x, y) in the reference's pixel-index coordinates (pixel (i, j) has centre (x, y) =
+ * (i, j), x along Nx); sub-pixel values and values outside the frame are allowed (the reference
+ * clamps the cell and extrapolates, utils.py:63-97).  Positions are carried in float64 through all
+ * steps whatever the dtypes.  Record n-1 (n = 1..Nt-1) is the displacement (x_n - xStart, y_n -
+ * yStart) = reconstructTrajectory(xStart, yStart, un[:n+1], vn[:n+1], Nx, Ny, n+1) (utils.py:44-99),
+ * with un, vn = grad('N') of phi's planes (utils.py:148-183).  out: [R][M][2], C-contiguous, R = Nt-1
+ * with all_steps = 1, R = 1 (the last record) with all_steps = 0.  For start points at pixel centres
+ * record n-1 carries the bits of foto_bb_flow_path's (u, v) at that pixel, the last record those of
+ * foto_bb_flow.  Deviation: a non-finite coordinate gives a non-finite record for that point alone
+ * (the reference's int(nan) / int(inf) at utils.py:63-64 raise); it is neither an error nor an
+ * out-of-range read.  State rules: those of foto_bb_flow_path.  Host entry (utils.py:44-99): float64
+ * in and out, staged through grow-only device buffers of the context.  Device entry (utils.py:44-99):
+ * pts_dtype and dtype FOTO_F32 | FOTO_F64 (float32 points widen exactly; float32 records are
+ * (float)x, to nearest even); both pointers are checked to be device memory of the context's
+ * device, aligned to one (x, y) pair, before anything is enqueued; one launch and no allocation on
+ * a one-shard context (virtual_ranks > 1: one launch per shard, the float64 positions in between in
+ * a grow-only scratch of the context).  FOTO_ERR_ARG, with `out` untouched: a null pointer, M < 1 or
+ * > 2^31 - 1, all_steps not 0 / 1, a dtype outside {F32, F64}, a misaligned or non-device pointer. */
+int foto_bb_track(foto_bb_ctx* c, const double* pts, int64_t M, int all_steps, double* out);          /* host f64 */
+int foto_bb_track_dev(foto_bb_ctx* c, const void* pts, int pts_dtype, int64_t M, int all_steps, void* out,
+                      int dtype, void* stream);
 
 /* foto_gn_plan_solve (classical.py:68-130) on device frames, the solution exported to `out` as
  * foto_bb_flow_dev does (planar: u, v, m).  Same PCG launches, prediction, result and return

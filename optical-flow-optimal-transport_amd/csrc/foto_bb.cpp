@@ -227,10 +227,17 @@ struct foto_bb_ctx {
     StreamLink link;
     double* nrm = nullptr;
     double hsum[2] = {0, 0};
+    // point tracking (foto_bb_track / _dev), grow-only device scratch: the host entry's staged
+    // points [M][2] and records [R][M][2], and the running float64 positions [M][2] that travel
+    // between the launches of a path whose planes lie in several shards (virtual ranks)
+    enum { TRK_PTS = 0, TRK_OUT = 1, TRK_POS = 2 };
+    double* trk[3] = {nullptr, nullptr, nullptr};
+    size_t trk_cap[3] = {0, 0, 0};   // in doubles
     ~foto_bb_ctx() {
         if (sc) (void)hipStreamSynchronize(sc);
         if (s) (void)hipStreamSynchronize(s);   // (before the shards free their buffers)
         sh.clear();
+        for (double* b : trk) if (b) (void)hipFree(b);
         if (nc) (void)ncclCommDestroy(nc);
         if (hS) (void)hipHostFree(hS);
         for (double* h : hgath) if (h) (void)hipHostFree(h);
@@ -1667,7 +1674,9 @@ int foto_bb_flow(foto_bb_ctx* c, double* u, double* v, double* m) {
     return rc;
 }
 
-static int flow_path_entry(foto_bb_ctx* c, double* u, double* v, double* m, const FlowDev* dv, const char* who) {
+// The state rules of the exports that read phi (flow path, point tracking), before any argument
+// is looked at.
+static int path_state_check(foto_bb_ctx* c, const char* who) {
     if (!c) { set_error("%s: null ctx", who); return FOTO_ERR_ARG; }
     if (c->rccl) { set_error("%s: not supported on RCCL-sharded contexts", who); return FOTO_ERR_STATE; }
     if (c->broken) {
@@ -1678,6 +1687,11 @@ static int flow_path_entry(foto_bb_ctx* c, double* u, double* v, double* m, cons
         set_error("%s: no outer iteration has run yet", who);
         return FOTO_ERR_STATE;
     }
+    return 0;
+}
+
+static int flow_path_entry(foto_bb_ctx* c, double* u, double* v, double* m, const FlowDev* dv, const char* who) {
+    FOTO_TRY(path_state_check(c, who));
     if (dv) {
         FOTO_TRY(export_check(dv->out, dv->dtype, dv->layout, (int64_t)c->Nx * c->Ny * (c->Nt - 1),
                               stream_device(c->s), who));
@@ -1697,6 +1711,86 @@ int foto_bb_flow_path(foto_bb_ctx* c, double* u, double* v, double* m) {
 int foto_bb_flow_path_dev(foto_bb_ctx* c, void* out, int dtype, int layout, void* stream) {
     const FlowDev dv{out, dtype, layout, (hipStream_t)stream};
     return flow_path_entry(c, nullptr, nullptr, nullptr, &dv, "foto_bb_flow_path_dev");
+}
+
+// ------------------------------------------------------------------ point tracking
+// Grow-only device scratch of the context (freed with it).  Growing waits for the stream first:
+// an earlier call's launches may still read the buffer being replaced.
+static int track_scratch(foto_bb_ctx* c, int which, size_t n_doubles) {
+    if (c->trk_cap[which] >= n_doubles) return 0;
+    FOTO_HIP_CHECK(hipStreamSynchronize(c->s));
+    if (c->trk[which]) FOTO_HIP_CHECK(hipFree(c->trk[which]));
+    c->trk[which] = nullptr;
+    c->trk_cap[which] = 0;
+    void* b = nullptr;
+    FOTO_HIP_CHECK(hipMalloc(&b, n_doubles * sizeof(double)));
+    c->trk[which] = (double*)b;
+    c->trk_cap[which] = n_doubles;
+    return 0;
+}
+
+// Plane n's trajectory step reads phi plane n of the shard that owns it (shard 0: the completed
+// iteration's phi, as flow_path): one launch per run of planes in one buffer, so one launch on a
+// one-shard context.  Between launches the float64 positions travel through the TRK_POS scratch
+// -- positions rebuilt from stored displacements ((x - x0) + x0) would not have the same bits.
+static bool track_needs_pos(foto_bb_ctx* c) {
+    Shard* sp = plane_owner(c, 0);
+    return sp && sp->g.t0 + sp->g.nloc < c->Nt - 1;
+}
+
+static int track_run(foto_bb_ctx* c, const Completed& k, const void* pts, int pts_dtype, int64_t M, int all_steps,
+                     void* out, int dtype) {
+    Shard& s0 = *c->sh[0];
+    const int last = c->Nt - 1;
+    double* const pos = c->trk[foto_bb_ctx::TRK_POS];
+    for (int n = 0; n < last;) {
+        Shard* sp = plane_owner(c, n);
+        if (!sp) { set_error("point tracking: no local shard owns plane %d", n); return FOTO_ERR_STATE; }
+        const int n_hi = std::min(sp->g.t0 + sp->g.nloc, last);
+        const double* phi = (sp == &s0) ? k.phi : sp->phi;
+        FOTO_HIP_CHECK(launch_track(sp->g, phi, n, n_hi, pts, pts_dtype, n == 0 ? nullptr : pos,
+                                    n_hi == last ? nullptr : pos, out, dtype, M, all_steps, c->s));
+        n = n_hi;
+    }
+    return 0;
+}
+
+int foto_bb_track(foto_bb_ctx* c, const double* pts, int64_t M, int all_steps, double* out) {
+    const char* who = "foto_bb_track";
+    FOTO_TRY(path_state_check(c, who));
+    FOTO_TRY(track_arg_check(pts, out, M, all_steps, who));
+    Completed k;
+    FOTO_TRY(completed_state(c, who, &k));
+    const size_t np = 2 * (size_t)M, nr = np * (size_t)(all_steps ? c->Nt - 1 : 1);
+    FOTO_TRY(track_scratch(c, foto_bb_ctx::TRK_PTS, np));
+    FOTO_TRY(track_scratch(c, foto_bb_ctx::TRK_OUT, nr));
+    if (track_needs_pos(c)) FOTO_TRY(track_scratch(c, foto_bb_ctx::TRK_POS, np));
+    double* dp = c->trk[foto_bb_ctx::TRK_PTS];
+    double* dout = c->trk[foto_bb_ctx::TRK_OUT];
+    FOTO_HIP_CHECK(hipMemcpyAsync(dp, pts, np * sizeof(double), hipMemcpyHostToDevice, c->s));
+    FOTO_TRY(track_run(c, k, dp, FOTO_F64, M, all_steps, dout, FOTO_F64));
+    FOTO_HIP_CHECK(hipMemcpyAsync(out, dout, nr * sizeof(double), hipMemcpyDeviceToHost, c->s));
+    FOTO_HIP_CHECK(hipStreamSynchronize(c->s));
+    return 0;
+}
+
+int foto_bb_track_dev(foto_bb_ctx* c, const void* pts, int pts_dtype, int64_t M, int all_steps, void* out, int dtype,
+                      void* stream) {
+    const char* who = "foto_bb_track_dev";
+    FOTO_TRY(path_state_check(c, who));
+    FOTO_TRY(track_arg_check(pts, out, M, all_steps, who));
+    FOTO_TRY(track_dtype_check(pts, pts_dtype, who, "pts"));
+    FOTO_TRY(track_dtype_check(out, dtype, who, "out"));
+    const size_t np = 2 * (size_t)M, nr = np * (size_t)(all_steps ? c->Nt - 1 : 1);
+    const int dev = stream_device(c->s);
+    FOTO_TRY(dev_ptr_check(pts, np * dtype_bytes(pts_dtype), dev, who, "pts"));
+    FOTO_TRY(dev_ptr_check(out, nr * dtype_bytes(dtype), dev, who, "out"));
+    Completed k;
+    FOTO_TRY(completed_state(c, who, &k));
+    if (track_needs_pos(c)) FOTO_TRY(track_scratch(c, foto_bb_ctx::TRK_POS, np));   // (virtual ranks only)
+    FOTO_TRY(c->link.enter((hipStream_t)stream, c->s));   // (before the first read of `pts` / write of `out`)
+    FOTO_TRY(track_run(c, k, pts, pts_dtype, M, all_steps, out, dtype));
+    return c->link.leave(c->s, (hipStream_t)stream);
 }
 
 int foto_bb_frames(foto_bb_ctx* c, const double* s, int count, double scale, double* out) {

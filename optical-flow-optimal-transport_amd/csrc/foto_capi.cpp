@@ -258,6 +258,26 @@ int foto_flow_path_from_phi(const double* phi, int Nt, int Nx, int Ny, double* u
     return S.sync();
 }
 
+int foto_track_from_phi(const double* phi, int Nt, int Nx, int Ny, const double* pts, int64_t M, int all_steps,
+                        double* out) {
+    const char* who = "foto_track_from_phi";
+    FOTO_TRY(check3(Nt, Nx, Ny));
+    FOTO_TRY(check2(Nx, Ny));
+    if (!phi) { set_error("%s: null pointer", who); return FOTO_ERR_ARG; }
+    FOTO_TRY(track_arg_check(pts, out, M, all_steps, who));
+    Scope S;
+    FOTO_TRY(S.init());
+    const Geo g = make_geo(Nt, Nx, Ny);
+    const size_t N = (size_t)Nt * g.nxy, np = 2 * (size_t)M, nr = np * (size_t)(all_steps ? Nt - 1 : 1);
+    double *d, *dp, *dout;
+    FOTO_TRY(S.up(phi, N, &d));
+    FOTO_TRY(S.up(pts, np, &dp));
+    FOTO_TRY(S.dev(nr, &dout));
+    FOTO_HIP_CHECK(launch_track(g, d, 0, Nt - 1, dp, FOTO_F64, nullptr, nullptr, dout, FOTO_F64, M, all_steps, S.s));
+    FOTO_TRY(S.down(out, dout, nr));
+    return S.sync();
+}
+
 // ----------------------------------------------------------------------------- GN
 
 int foto_gn_apply(const double* f1, const double* f2, int w, int h, double alpha, double lam, const double* x3,

@@ -287,6 +287,31 @@ int export_check(const void* out, int dtype, int layout, int64_t n, int device, 
     return dev_ptr_check(out, (size_t)n * (layout == 0 ? 3 : 2) * dtype_size(dtype), device, who, "out");
 }
 
+int track_arg_check(const void* pts, const void* out, int64_t M, int all_steps, const char* who) {
+    if (!pts || !out) { set_error("%s: null pointer", who); return FOTO_ERR_ARG; }
+    if (M < 1 || M > (int64_t)INT32_MAX) {
+        set_error("%s: M = %lld points must be in [1, 2^31 - 1]", who, (long long)M);
+        return FOTO_ERR_ARG;
+    }
+    if (all_steps != 0 && all_steps != 1) {
+        set_error("%s: all_steps = %d is not 0 (the last record) / 1 (every record)", who, all_steps);
+        return FOTO_ERR_ARG;
+    }
+    return 0;
+}
+
+int track_dtype_check(const void* p, int dtype, const char* who, const char* what) {
+    if (dtype != FOTO_F32 && dtype != FOTO_F64) {
+        set_error("%s: %s dtype %d is not FOTO_F32 / FOTO_F64", who, what, dtype);
+        return FOTO_ERR_ARG;
+    }
+    if ((uintptr_t)p % (2 * dtype_size(dtype)) != 0) {   // one (x, y) pair is one vector load / store
+        set_error("%s: %s %p is not aligned to its %zu-byte (x, y) pair", who, what, p, 2 * dtype_size(dtype));
+        return FOTO_ERR_ARG;
+    }
+    return 0;
+}
+
 // ----------------------------------------------------------------------------- launchers
 
 hipError_t launch_ingest(const foto_image& im, int w, int h, double* dst, hipStream_t s) {

@@ -270,6 +270,15 @@ hipError_t launch_flow_finish(int Nx, int Ny, const double* px, const double* py
 hipError_t launch_flow_record(int Nx, int Ny, const double* px, const double* py, void* ou, void* ov, void* om,
                               int dtype, int layout, hipStream_t s);
 
+// Point tracking: trajectory steps n in [n_lo, n_hi) (within g's planes and below Nt - 1) for M
+// start points pts[M][2] of FOTO_F32 | FOTO_F64, one launch.  all_steps = 1: record n -> out[n][M][2]
+// (global n: `out` is the base of the whole [Nt-1][M][2] array); 0: the record of step Nt-2 ->
+// out[M][2], stored by the launch that runs that step.  pos_in (null: start at pts) and pos_out
+// (null: not stored) are [M][2] float64 running positions.  Records are displacements from pts.
+hipError_t launch_track(const Geo& g, const double* phi, int n_lo, int n_hi, const void* pts, int pts_dtype,
+                        const double* pos_in, double* pos_out, void* out, int dtype, int64_t M, int all_steps,
+                        hipStream_t s);
+
 hipError_t launch_dot_self(int64_t n, const double* x, RedBuf rb, double* gath, int rank, hipStream_t s);
 
 // GN
@@ -300,6 +309,10 @@ int image_dev_check(const foto_image* im, int w, int h, int device, const char* 
 int dev_ptr_check(const void* p, size_t bytes, int device, const char* who, const char* what);
 // an export target: dtype F32 | F64, layout 0 | 1, n pixels, device memory of `device`
 int export_check(const void* out, int dtype, int layout, int64_t n, int device, const char* who);
+// point tracking (foto_bb_track / _dev, foto_track_from_phi), host-only: non-null pointers, M in
+// [1, 2^31 - 1], all_steps 0 | 1; a device array of (x, y) pairs: dtype F32 | F64, aligned to a pair
+int track_arg_check(const void* pts, const void* out, int64_t M, int all_steps, const char* who);
+int track_dtype_check(const void* p, int dtype, const char* who, const char* what);
 // dst[row * w + col] = (double)pixel(row, col) / divisor
 hipError_t launch_ingest(const foto_image& im, int w, int h, double* dst, hipStream_t s);
 // tot[0] = sum of x[0..n) in a fixed order; part holds sum_blocks(n) doubles

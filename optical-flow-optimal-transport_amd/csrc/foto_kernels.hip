@@ -1278,6 +1278,102 @@ hipError_t launch_flow_record(int Nx, int Ny, const double* px, const double* py
     return hipErrorInvalidValue;
 }
 
+// ---------------------------------------------------------------------------- point tracking
+// reconstructTrajectory (utils.py:44-99) from arbitrary start points, one thread per point, for
+// the steps n in [n_lo, n_hi) of one base pointer; the position stays in registers (float64)
+// from step to step.  A step is k_traj's: the same trunc_clamp, weights and sum order, and each
+// un / vn the same single subtraction and multiply -- but the 12 distinct phi values it needs
+// (the 4 x 4 neighbourhood of (tx, ty) without its corners; un_at / vn_at issue 16 loads) are
+// loaded once, unconditionally and together, from indices clamped into the plane; what un_at /
+// vn_at return as 0 on an edge column / row is selected afterwards.  tx in [0, Nx-2] and ty in
+// [0, Ny-2] for every x, y (trunc_clamp maps NaN to 0 and clamps +-inf), so every index is inside
+// the plane whatever the point: a non-finite point gives a non-finite record and nothing else.
+// Record n (after step n) is the displacement from the start point, one 16-byte (float64) or
+// 8-byte (float32) store per thread, contiguous across the wave; ALL = 0 stores the record of
+// step Nt-2 only.  pos_in (may be null: the start points) / pos_out (may be null) carry the
+// running float64 positions between the launches of a path whose planes lie in several buffers
+// (they may be the same buffer: a thread reads its own pair before the loop and writes it after).
+template <class T> struct Pair2;
+template <> struct Pair2<float> { using type = float2; };
+template <> struct Pair2<double> { using type = double2; };
+
+template <class TI, class TO, int ALL>
+__global__ __launch_bounds__(NT) void k_track(Geo g, const double* __restrict__ phi, int n_lo, int n_hi,
+                                              const TI* __restrict__ pts, const double* pos_in, double* pos_out,
+                                              TO* __restrict__ out, int64_t M) {
+    using VI = typename Pair2<TI>::type;
+    using VO = typename Pair2<TO>::type;
+    const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
+    if (i >= M) return;
+    const int Nx = g.Nx, Ny = g.Ny;
+    const VI p0 = reinterpret_cast<const VI*>(pts)[i];
+    const double x0 = (double)p0.x, y0 = (double)p0.y;
+    double x = x0, y = y0;
+    if (pos_in) {
+        const double2 q = reinterpret_cast<const double2*>(pos_in)[i];
+        x = q.x;
+        y = q.y;
+    }
+    VO* const rec = reinterpret_cast<VO*>(out);
+    for (int n = n_lo; n < n_hi; ++n) {
+        const double* P = phi + (int64_t)(n - g.t0) * g.nxy;
+        const int tx = trunc_clamp(x, Nx - 2), ty = trunc_clamp(y, Ny - 2);
+        const int xm = tx > 0 ? tx - 1 : 0, xp = tx + 2 < Nx ? tx + 2 : Nx - 1;
+        const int ym = ty > 0 ? ty - 1 : 0, yp = ty + 2 < Ny ? ty + 2 : Ny - 1;
+        const double* r0 = P + (int64_t)ty * Nx;
+        const double* r1 = r0 + Nx;
+        const double* rm = P + (int64_t)ym * Nx;
+        const double* rp = P + (int64_t)yp * Nx;
+        // the 12 loads, ahead of their first use
+        const double a0 = r0[xm], b0 = r0[tx], c0 = r0[tx + 1], d0 = r0[xp];
+        const double a1 = r1[xm], b1 = r1[tx], c1 = r1[tx + 1], d1 = r1[xp];
+        const double bm = rm[tx], cm = rm[tx + 1];
+        const double bp = rp[tx], cp = rp[tx + 1];
+        const double dX = x - tx, dY = y - ty;
+        const double w1 = (1 - dY) * (1 - dX), w2 = dX * (1 - dY), w3 = dY * dX, w4 = (1 - dX) * dY;
+        const bool xl = tx == 0, xr = tx + 1 == Nx - 1;   // un is 0 on columns 0 and Nx-1
+        const bool yl = ty == 0, yr = ty + 1 == Ny - 1;   // vn is 0 on rows 0 and Ny-1
+        const double u00 = xl ? 0.0 : 0.5 * (c0 - a0), u01 = xr ? 0.0 : 0.5 * (d0 - b0);
+        const double u11 = xr ? 0.0 : 0.5 * (d1 - b1), u10 = xl ? 0.0 : 0.5 * (c1 - a1);
+        const double v00 = yl ? 0.0 : 0.5 * (b1 - bm), v01 = yl ? 0.0 : 0.5 * (c1 - cm);
+        const double v11 = yr ? 0.0 : 0.5 * (cp - c0), v10 = yr ? 0.0 : 0.5 * (bp - b0);
+        x += w1 * u00 + w2 * u01 + w3 * u11 + w4 * u10;
+        y += w1 * v00 + w2 * v01 + w3 * v11 + w4 * v10;
+        if (ALL || n == g.Nt - 2) {
+            VO r;
+            r.x = (TO)(x - x0);
+            r.y = (TO)(y - y0);
+            rec[(ALL ? (int64_t)n * M : 0) + i] = r;
+        }
+    }
+    if (pos_out) reinterpret_cast<double2*>(pos_out)[i] = make_double2(x, y);
+}
+
+template <class TI, class TO>
+static hipError_t track_t(const Geo& g, const double* phi, int n_lo, int n_hi, const void* pts, const double* pos_in,
+                          double* pos_out, void* out, int64_t M, int all_steps, hipStream_t s) {
+    const int nb = flat_blocks(M);
+    if (all_steps)
+        k_track<TI, TO, 1><<<nb, NT, 0, s>>>(g, phi, n_lo, n_hi, (const TI*)pts, pos_in, pos_out, (TO*)out, M);
+    else
+        k_track<TI, TO, 0><<<nb, NT, 0, s>>>(g, phi, n_lo, n_hi, (const TI*)pts, pos_in, pos_out, (TO*)out, M);
+    return hipGetLastError();
+}
+
+hipError_t launch_track(const Geo& g, const double* phi, int n_lo, int n_hi, const void* pts, int pts_dtype,
+                        const double* pos_in, double* pos_out, void* out, int dtype, int64_t M, int all_steps,
+                        hipStream_t s) {
+    if (M < 1 || M > INT32_MAX || g.Nx < 2 || g.Ny < 2) return hipErrorInvalidValue;
+    if (n_lo < g.t0 || n_hi > g.t0 + g.nloc || n_hi > g.Nt - 1) return hipErrorInvalidValue;
+    if (n_lo >= n_hi) return hipSuccess;
+    const bool i32 = pts_dtype == FOTO_F32, o32 = dtype == FOTO_F32;
+    if ((!i32 && pts_dtype != FOTO_F64) || (!o32 && dtype != FOTO_F64)) return hipErrorInvalidValue;
+    if (i32 && o32) return track_t<float, float>(g, phi, n_lo, n_hi, pts, pos_in, pos_out, out, M, all_steps, s);
+    if (i32) return track_t<float, double>(g, phi, n_lo, n_hi, pts, pos_in, pos_out, out, M, all_steps, s);
+    if (o32) return track_t<double, float>(g, phi, n_lo, n_hi, pts, pos_in, pos_out, out, M, all_steps, s);
+    return track_t<double, double>(g, phi, n_lo, n_hi, pts, pos_in, pos_out, out, M, all_steps, s);
+}
+
 }  // namespace foto
 
 namespace foto {

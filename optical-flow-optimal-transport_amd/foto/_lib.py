@@ -175,6 +175,10 @@ SIGNATURES = {
     "foto_bb_frames_dev": (_I, [_P, _D, _I, _Dbl, _P, _I, _P]),
     "foto_bb_flow_path": (_I, [_P, _D, _D, _D]),
     "foto_bb_flow_path_dev": (_I, [_P, _P, _I, _I, _P]),
+    # point tracking: trajectories from arbitrary start points
+    "foto_track_from_phi": (_I, [_D, _I, _I, _I, _D, ctypes.c_int64, _I, _D]),
+    "foto_bb_track": (_I, [_P, _D, ctypes.c_int64, _I, _D]),
+    "foto_bb_track_dev": (_I, [_P, _P, _I, ctypes.c_int64, _I, _P, _I, _P]),
     "foto_gn_plan_solve_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _P, _I, _I, _P,
                                     ctypes.POINTER(_I)]),
     "foto_warp_dev": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),

@@ -164,6 +164,33 @@ class BBSolver:
                                                   ctypes.c_void_p(D.stream_handle(stream, out))))
         return out
 
+    def track(self, points, all_steps=True):
+        """Trajectories of arbitrary start points (foto_bb_track): ``points`` is anything
+        np.asarray turns into (M, 2) = (x, y) in pixel-index coordinates (pixel (i, j) has centre
+        (i, j), x along Nx; sub-pixel and out-of-frame values allowed), a single (2,) point is
+        M = 1.  Returns float64 (R, M, 2): record n-1 is the displacement after the first n steps
+        of utils.reconstructTrajectory, R = Nt-1 (``all_steps``) or 1 (the last record).  At
+        pixel centres the records have the bits of flow_path()'s (u, v)."""
+        from . import device as D
+        pts = D.track_points(points)
+        M = pts.shape[0]
+        out = np.empty((self.Nt - 1 if all_steps else 1, M, 2))
+        self._check(self._L.foto_bb_track(self._ctx, dptr(pts), M, 1 if all_steps else 0, dptr(out)))
+        return out
+
+    def track_device(self, points, out=None, dtype="float32", all_steps=True, stream=None):
+        """track() on the device (foto_bb_track_dev): ``points`` is a C-contiguous (M, 2) float32
+        | float64 device array, the result a DeviceArray (or ``out``, any contiguous device array)
+        [R][M][2] of ``dtype`` float32 | float64.  Positions are float64 inside whatever the
+        dtypes."""
+        from . import device as D
+        pptr, pcode, M = D.track_source(points)
+        out, ptr, dcode = D.track_target(out, dtype, self.Nt - 1 if all_steps else 1, M)
+        self._check(self._L.foto_bb_track_dev(self._ctx, ctypes.c_void_p(pptr), pcode, M, 1 if all_steps else 0,
+                                              ctypes.c_void_p(ptr), dcode,
+                                              ctypes.c_void_p(D.stream_handle(stream, out, points))))
+        return out
+
     def _check(self, rc):
         return check(rc, self._L)
 

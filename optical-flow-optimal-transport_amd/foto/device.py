@@ -376,6 +376,41 @@ def path_target(out, dtype, layout, Nt, h, w):
     return out, ptr, code, _LAYOUTS[layout]
 
 
+def track_points(points):
+    """Host start points as a C-contiguous float64 (M, 2) array: anything np.asarray turns into
+    (M, 2); a single (2,) point is promoted to M = 1.  ValueError otherwise."""
+    a = np.asarray(points, dtype=np.float64)
+    if a.shape == (2,):
+        a = a.reshape(1, 2)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"points of shape {a.shape}: an (M, 2) array of (x, y) start points, or one (2,) point")
+    return np.ascontiguousarray(a)
+
+
+def track_source(points):
+    """(pointer, dtype code, M) of device start points: a C-contiguous (M, 2) float32 | float64
+    device array.  ValueError before the library is touched."""
+    if not isinstance(points, DeviceArray):
+        runtime_check()
+    ptr, typestr, shape, strides, _ = _interface(points)
+    if typestr not in ("<f4", "<f8"):
+        raise ValueError(f"points: typestr {typestr!r}; device start points are float32 or float64")
+    if len(shape) != 2 or shape[1] != 2:
+        raise ValueError(f"points of shape {shape}: a device (M, 2) array of (x, y) start points")
+    if strides is not None:
+        acc = np.dtype(typestr).itemsize
+        for s, st in zip(reversed(shape), reversed(tuple(strides))):
+            if s > 1 and st != acc:
+                raise ValueError("points must be C-contiguous")
+            acc *= s
+    return ptr, _DTYPES[typestr][0], int(shape[0])
+
+
+def track_target(out, dtype, R, M):
+    """(out, pointer, dtype code) of a point-tracking export: [R][M][2] of float32 | float64."""
+    return _shaped_target(out, dtype, _OUT_DTYPES, (int(R), int(M), 2), "track records")
+
+
 # -------------------------------------------------------------------- convenience
 
 def bb_flow(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, normalize=False,
@@ -418,6 +453,31 @@ def bb_path(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100
         s.iterate(max_it, convergence_tol=convergence_tol, stop_rules=True)
         fr = s.frames_device(pos, scale=s.sums[0] if normalize else 1.0, out=frames_out, dtype=frame_dtype, stream=st)
         return fr, s.flow_path_device(out=out, dtype=dtype, layout=layout, stream=st)
+
+    if bb._cache_enabled(opts):
+        s = bb.cached_solver_device(a, b, Nt, r, reg_epsilon, normalize=normalize, stream=st, **opts)
+        try:
+            return run(s)
+        except BaseException:
+            bb.drop_cached(s)
+            raise
+    with bb.BBSolver.from_device(a, b, Nt, r=r, reg_epsilon=reg_epsilon, normalize=normalize, stream=st, **opts) as s:
+        return run(s)
+
+
+def bb_track(f0, f1, Nt, points, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, normalize=False,
+             all_steps=True, dtype="float32", out=None, stream=None, **opts):
+    """bb_flow for a caller's own points instead of the pixel grid: the same solve on the cached
+    context, then the trajectories of the device start points ``points`` ((M, 2) float32 |
+    float64, (x, y) in pixel-index coordinates) left on the device.  Returns [Nt-1][M][2]
+    displacements (``all_steps``) or [1][M][2], the last record: where bb_flow moves each point."""
+    from . import bb
+    a, b = _pair(f0, f1)
+    st = stream_handle(stream, f0, f1, points)
+
+    def run(s):
+        s.iterate(max_it, convergence_tol=convergence_tol, stop_rules=True)
+        return s.track_device(points, out=out, dtype=dtype, all_steps=all_steps, stream=st)
 
     if bb._cache_enabled(opts):
         s = bb.cached_solver_device(a, b, Nt, r, reg_epsilon, normalize=normalize, stream=st, **opts)

@@ -111,6 +111,20 @@ def flow_path_from_phi(phi, Nt, Nx, Ny):
     return u, v, m
 
 
+def track_from_phi(phi, Nt, Nx, Ny, points, all_steps=True):
+    """float64 (R, M, 2): the displacement of each start point (x, y) of ``points`` ((M, 2), or one
+    (2,) point) after the first n steps of utils.reconstructTrajectory through grad('N') of phi's
+    planes, n = 1..Nt-1 (``all_steps``) or n = Nt-1 only (R = 1).  At pixel centres the records
+    have the bits of ``flow_path_from_phi``'s (u, v)."""
+    from .device import track_points
+    x = f64(phi, Nt * Nx * Ny, "phi")
+    pts = track_points(points)
+    M = pts.shape[0]
+    out = np.empty((max(Nt - 1, 0) if all_steps else 1, M, 2))
+    check(lib().foto_track_from_phi(dptr(x), Nt, Nx, Ny, dptr(pts), M, 1 if all_steps else 0, dptr(out)))
+    return out
+
+
 def _bc(bc):
     if bc not in ("N", "D"):
         raise NotImplementedError("These boundary conditions are not implemented")

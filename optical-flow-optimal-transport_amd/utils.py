@@ -50,7 +50,9 @@ def openGrayscaleImage(inputPathname):
 def reconstructTrajectory(xStart, yStart, u, v, Nx, Ny, Nt):
     """One particle through the (Nt x Nx*Ny) velocity slabs u, v with clamped bilinear
     interpolation (utils.py:44-99).  Host helper for a single start point; the solver
-    integrates all pixels on the GPU (opticalflow_from_benamoubrenier)."""
+    integrates all pixels on the GPU (opticalflow_from_benamoubrenier).  For many start
+    points use the GPU entries: ``foto.bb.BBSolver.track`` / ``track_device`` on a solver,
+    ``foto.ops.track_from_phi`` on a phi, ``foto.device.bb_track`` as a one-shot."""
     x, y = xStart, yStart
     for n in range(Nt - 1):
         tx = max(0, min(Nx - 2, int(x)))
