@@ -154,6 +154,7 @@ struct foto_bb_ctx {
     int Nt = 0, Nx = 0, Ny = 0;
     double r = 1, eps = 1e-3;
     foto_bb_opts o{};
+    Tuning tn;            // the environment's knobs as bb_create found them: fixed for the context's life
     int W = 1;            // total ranks (processes * virtual)
     bool rccl = false;
     ncclComm_t nc = nullptr;
@@ -414,8 +415,7 @@ static int ctx_init(foto_bb_ctx* c, const RhoSrc& src) {
         memcpy(&id, c->o.nccl_id, sizeof(id));
         FOTO_NCCL_CHECK(ncclCommInitRank(&c->nc, W, id, c->o.rank));
         // FOTO_COMM_STREAM=0: every RCCL call on the compute stream (A/B runs)
-        const char* cs = getenv("FOTO_COMM_STREAM");
-        if (!(cs && atoi(cs) == 0)) {
+        if (c->tn.comm_stream) {
             FOTO_TRY(stream_acquire(&c->sc));
             FOTO_HIP_CHECK(hipEventCreateWithFlags(&c->cfork, hipEventDisableTiming));
             FOTO_HIP_CHECK(hipEventCreateWithFlags(&c->cjoin, hipEventDisableTiming));
@@ -424,25 +424,20 @@ static int ctx_init(foto_bb_ctx* c, const RhoSrc& src) {
     }
     const int nlocal = c->rccl ? 1 : W;
     {
-        const char* e = getenv("FOTO_FUSE_PR");   // 0: separate k_prox / k_rhs (A/B runs)
-        c->fuse = !(e && atoi(e) == 0);
-        const char* pe = getenv("FOTO_PIPE");   // 0: one outer iteration in flight (A/B runs)
-        c->pipe = W == 1 && c->fuse && c->o.cg_mode == 3 && !(pe && atoi(pe) == 0);
+        c->fuse = c->tn.fuse_pr;   // FOTO_FUSE_PR=0: separate k_prox / k_rhs (A/B runs)
+        // FOTO_PIPE=0: one outer iteration in flight (A/B runs)
+        c->pipe = W == 1 && c->fuse && c->o.cg_mode == 3 && c->tn.pipe;
         // the crit readback as two stores of k_prox_rhs's last block into the slot (a copy launch
         // on the stream costs ~4 us; FOTO_HOST_CRIT=0: the copy)
         // phase events (the RHS / CG / prox split of foto_bb_stats) only with kernel timing on:
         // three timed event records per outer iteration cost ~13 us of GPU time at the bench
         // grid (1561-1572 vs 1603-1616 it/s, same box), and the crit sync uses a timing-free one
-        const char* pv = getenv("FOTO_PHASE_EV");
-        c->phase_force = pv && atoi(pv) == 1;
-        const char* hc = getenv("FOTO_HOST_CRIT");
-        c->hcrit = W == 1 && c->fuse && !(hc && atoi(hc) == 0);
+        c->phase_force = c->tn.phase_ev;
+        c->hcrit = W == 1 && c->fuse && c->tn.host_crit;
         // the crit sync: with the crit pair and the Gauss header stored into coherent host memory
         // by the kernels themselves (fenced there), the event needs no system-scope fence of its
         // own -- a fenced record writes the L2's dirty lines back once per outer iteration
-        // (FOTO_SYNC_FENCE=1: fenced)
-        const char* sf = getenv("FOTO_SYNC_FENCE");
-        const unsigned ff = (c->hcrit && !(sf && atoi(sf) == 1)) ? hipEventDisableSystemFence : 0u;
+        const unsigned ff = c->hcrit ? hipEventDisableSystemFence : 0u;
         for (auto& e : c->fin) FOTO_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming | ff));
     }
     for (int j = 0; j < nlocal; ++j) {
@@ -481,7 +476,7 @@ static int ctx_init(foto_bb_ctx* c, const RhoSrc& src) {
         FOTO_TRY(s.alloc(nxy * sizeof(double), &b)); s.fv = (double*)b;
         FOTO_TRY(s.alloc(nxy * sizeof(double), &b)); s.fm = (double*)b;
         const int64_t nb = std::max<int64_t>(march_blocks(s.g), flat_blocks((int64_t)s.g.nloc * nxy));
-        s.rb.cap = (int)std::max<int64_t>(2 * nb, 3 * (int64_t)prox_rhs_blocks(s.g));
+        s.rb.cap = (int)std::max<int64_t>(2 * nb, 3 * (int64_t)prox_rhs_blocks(s.g, c->tn.pr_tch));
         FOTO_TRY(s.alloc(sizeof(double) * s.rb.cap, &b)); s.rb.partials = (double*)b;
         FOTO_TRY(s.alloc(sizeof(unsigned) * 64, &b)); s.rb.ticket = (unsigned*)b;
         FOTO_HIP_CHECK(hipMemsetAsync(s.rb.ticket, 0, sizeof(unsigned) * 64, c->s));
@@ -492,7 +487,7 @@ static int ctx_init(foto_bb_ctx* c, const RhoSrc& src) {
         FOTO_HIP_CHECK(launch_init_mu(s.g, s.rho0, s.rhoT, s.mu[0], s.mu[1], s.mu[2], s.q[0], s.q[1], s.q[2], c->s));
         if (c->o.cg_mode >= 1 && c->o.cg_mode <= 3) {
             s.spec.reset(new SpectralPlan());
-            FOTO_TRY(s.spec->init(s.g, s.rank, W, c->r, c->eps, c->o.cg_mode, c->s));
+            FOTO_TRY(s.spec->init(s.g, s.rank, W, c->r, c->eps, c->o.cg_mode, c->tn, c->s));
         }
         c->sh.push_back(std::move(sp));
     }
@@ -566,19 +561,16 @@ static int cg_iteration(foto_bb_ctx* c, int k) {
 static bool a2a_big_planes(const foto_bb_ctx* c) { return (int64_t)c->Nx * c->Ny >= (1 << 19); }
 
 static int a2a_parts(const foto_bb_ctx* c) {
-    const char* e = getenv("FOTO_A2A_PARTS");
-    const int v = e ? atoi(e) : (a2a_big_planes(c) ? 2 : 1);
+    const int v = c->tn.a2a_parts != Tuning::AUTO ? c->tn.a2a_parts : (a2a_big_planes(c) ? 2 : 1);
     return std::max(1, std::min(8, v));
 }
 
 static int a2a_halo(const foto_bb_ctx* c) {
     if (c->W == 1) return 0;
-    const char* e = getenv("FOTO_A2A_HALO");
-    if (e ? atoi(e) == 0 : !a2a_big_planes(c)) return 0;
+    if (c->tn.a2a_halo != Tuning::AUTO ? c->tn.a2a_halo == 0 : !a2a_big_planes(c)) return 0;
     // the deferred-edge fused prox (and the unfused prox) read one phi halo plane per side; the
     // edge-recompute variant (FOTO_PR_EDGE=0) reads two and keeps its own exchange
-    const char* pe = getenv("FOTO_PR_EDGE");
-    return (c->fuse && pe && atoi(pe) == 0) ? 0 : 1;
+    return (c->fuse && !c->tn.pr_edge) ? 0 : 1;
 }
 
 // F on the deferred edge planes of every local shard, from its w_t halo (k_rhs_edge)
@@ -612,17 +604,14 @@ static bool slabs_of_3(const foto_bb_ctx* c) {
     return true;
 }
 static bool wt_overlap(const foto_bb_ctx* c) {
-    if (!c->rccl || !c->sc || c->o.cg_mode == 0 || c->sh.size() != 1 || !slabs_of_3(c)) return false;
-    const char* e = getenv("FOTO_WT_OVERLAP");
-    return !(e && atoi(e) == 0);
+    return c->rccl && c->sc && c->o.cg_mode != 0 && c->sh.size() == 1 && slabs_of_3(c) && c->tn.wt_overlap;
 }
 
 // k_wt_pre ahead of k_prox_rhs: RCCL where wt_overlap holds; virtual ranks with FOTO_WT_PRE=1
 // (the same kernel sequence, exchanged by copies on s -- tests, tools/proxy_scaling.py)
 static bool wt_pre_on(const foto_bb_ctx* c) {
     if (c->rccl) return wt_overlap(c);
-    const char* e = getenv("FOTO_WT_PRE");
-    return c->W > 1 && c->o.cg_mode != 0 && e && atoi(e) == 1 && slabs_of_3(c);
+    return c->W > 1 && c->o.cg_mode != 0 && c->tn.wt_pre && slabs_of_3(c);
 }
 
 // a w_t exchange that no forward will consume (a new prox supersedes it): forget or wait for it
@@ -834,8 +823,7 @@ static int prox_rhs(foto_bb_ctx* c, bool guarded, int par) {
     double* hcrit = c->hcrit ? c->dgath[par] + 2 * W : nullptr;
     // sharded: defer the slab-edge F (default: two planes per neighbour on the wire, phi and w_t)
     // or recompute the neighbours' boundary stepB (FOTO_PR_EDGE=0: five planes, 2 phi + 3 mu)
-    const char* pe = getenv("FOTO_PR_EDGE");
-    const bool defer = W > 1 && !(pe && atoi(pe) == 0);
+    const bool defer = W > 1 && c->tn.pr_edge;
     FOTO_TRY(wt_drop(c));   // (a redo's prox supersedes a pending exchange)
     const bool pre = defer && wt_pre_on(c);
     if (W > 1) {
@@ -873,7 +861,7 @@ static int prox_rhs(foto_bb_ctx* c, bool guarded, int par) {
         hipEvent_t e = c->kt.start(c->s);
         FOTO_HIP_CHECK(launch_prox_rhs(s.g, s.phi, s.fz_src[0], s.fz_src[1], s.fz_src[2], s.fz_dst[0], s.fz_dst[1],
                                        s.fz_dst[2], s.rho0, s.rhoT, c->r, s.rv, s.rb, s.gath_crit(W) + 2 * s.rank,
-                                       c->o.cg_mode == 0 ? s.gath_rr() + s.rank : nullptr, c->s,
+                                       c->o.cg_mode == 0 ? s.gath_rr() + s.rank : nullptr, c->tn.pr_tch, c->s,
                                        guarded ? s.spec->done_flag() : nullptr, dlo, dhi, s.wt, s.edge, hcrit,
                                        pre ? 1 : 0));
         c->kt.stop(e, c->s, FOTO_K_PROX, 64.0 * nv);
@@ -912,8 +900,7 @@ static int outer_tail(foto_bb_ctx* c, size_t kmark) {
     // it, guarded by the CG's done flag; the one sync (crit) then also delivers the CG result.
     // A solve that needs more work (s-step: more passes than predicted; Gauss: K beyond the
     // table) is finished after that sync, and prox re-runs (FOTO_CG_DEFER=0: always wait).
-    const char* de = getenv("FOTO_CG_DEFER");
-    const bool defer_on = !(de && atoi(de) == 0);
+    const bool defer_on = c->tn.cg_defer;
     SpectralPlan* dsp = (defer_on && W == 1 && c->o.cg_mode != 0 && s0.spec && s0.spec->deferrable())
                             ? s0.spec.get()
                             : nullptr;
@@ -1414,16 +1401,13 @@ static int bb_create(const RhoSrc& src, int Nt, int Nx, int Ny, double r, double
     // costs milliseconds and rounds like scipy's matvec -- crit within 1e-8 of the reference, where
     // the DCT-basis CGs sit at the reference's own last-bit sensitivity, 2.6e-6 on config 1), the
     // Gauss-compressed spectral CG above (the metric grid, configs 2-5)
-    if (o.cg_mode < 0) {
-        const char* e = getenv("FOTO_CG_AUTO_MAX");
-        const long long lim = e ? atoll(e) : (1LL << 18);
-        o.cg_mode = ((long long)Nt * Nx * Ny <= lim) ? 0 : 3;
-    }
+    const Tuning tn = tuning_from_env();   // read here, once: part of the context's identity
+    if (o.cg_mode < 0) o.cg_mode = ((long long)Nt * Nx * Ny <= tn.cg_auto_max) ? 0 : 3;
     // the spectral CGs recover x = C^T((b^ - r^) / lam) and need lam > 0, i.e. eps > 0; with
     // eps <= 0 (A singular, as the reference then runs it) only the stencil CG applies
     if (o.cg_mode != 0 && !(reg_epsilon > 0.0)) o.cg_mode = 0;
     auto c = std::make_unique<foto_bb_ctx>();
-    c->Nt = Nt; c->Nx = Nx; c->Ny = Ny; c->r = r; c->eps = reg_epsilon; c->o = o;
+    c->Nt = Nt; c->Nx = Nx; c->Ny = Ny; c->r = r; c->eps = reg_epsilon; c->o = o; c->tn = tn;
     c->rccl = o.world > 1;
     c->W = c->rccl ? o.world : std::max(1, o.virtual_ranks);
     c->kt.on = o.timing != 0;

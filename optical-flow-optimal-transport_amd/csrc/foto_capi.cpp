@@ -369,13 +369,12 @@ static int gn_solve_impl(const double* f1, const double* f2, int w, int h, doubl
         return FOTO_ERR_ARG;
     }
     if (maxiter < 0) { set_error("maxiter < 0"); return FOTO_ERR_ARG; }
-    const char* emg = getenv("FOTO_GN_MG");   // 0: 3x3 block-Jacobi preconditioner (A/B runs)
-    if (!(emg && atoi(emg) == 0)) {
+    const Tuning tn = tuning_from_env();   // (a context-free entry: read here, once per call)
+    if (tn.gn_mg) {   // FOTO_GN_MG=0: 3x3 block-Jacobi preconditioner (A/B runs)
         // multigrid-preconditioned CG through a plan (foto_gn.hip), cached per process like an
         // FFT plan: a call with the same (w, h, alpha, lambda, rtol, maxiter) as the previous
         // one reuses its buffers and graph (FOTO_GN_PLAN_CACHE=0: make and destroy a plan per call)
-        const char* ec = getenv("FOTO_GN_PLAN_CACHE");
-        const bool cache = !(ec && atoi(ec) == 0);
+        const bool cache = tn.gn_plan_cache;
         // (the cached plan is never destroyed at process exit: the HIP runtime may be gone by then)
         static std::mutex mu;
         static foto_gn_plan* cached = nullptr;

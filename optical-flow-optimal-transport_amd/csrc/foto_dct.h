@@ -12,16 +12,12 @@ void dct_eigen(int n, std::vector<double>& mu);
 // FFT plans: whether n = 2 m1 m2 has one, and its per-axis table
 bool fft_factors(int n, int* m1, int* m2);
 std::vector<double> fft_table(int n);
-bool dct_fft_enabled();   // FOTO_DCT_FFT != 0 (read once)
 
 // one axis of [outer][n][inner]: GEMM kernels (M: the n x n matrix) / FFT kernels (tab:
-// fft_table; hipErrorNotSupported when n has no instantiation or the FFT path is off)
+// fft_table; hipErrorNotSupported when n has no instantiation or tab is null -- a plan built
+// with Tuning::dct_fft off uploads no tables)
 hipError_t dct_axis(int outer, int n, int inner, const double* M, const double* in, double* out, hipStream_t s);
 hipError_t dct_fft_axis(int outer, int n, int inner, bool inv, const double* tab, const double* in, double* out,
                         hipStream_t s);
-// the fused (x, t) forward / (t, x) inverse of a single shard's [t][y][x] volume <-> [kt][y][kx]
-bool xt_supported(int Nx, int Nt);
-hipError_t dct_xt(int Nt, int Ny, int Nx, bool inv, const double* tab, const double* Ch, const double* in,
-                  double* out, hipStream_t s);
 
 }  // namespace foto

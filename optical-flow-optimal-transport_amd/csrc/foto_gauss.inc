@@ -11,7 +11,7 @@
 //   1. k_gq_hist: partition theta = acos(lam~) in [0, pi] (lam~ = lam scaled to [-1, 1]) into
 //      GQ_NB equal bins and take each bin's first 2 GQ_M Chebyshev moments in its local variable
 //      u in [-1, 1]: one read of b^, no other state.
-//   2. k_gq_nodes: per bin, the GQ_M-point Gauss rule of those moments (modified Chebyshev
+//   2. k_gq_nodes_w: per bin, the GQ_M-point Gauss rule of those moments (modified Chebyshev
 //      algorithm -> Jacobi matrix -> eigenvalues by Sturm bisection, Christoffel weights).  A
 //      degree-2K polynomial is a trig polynomial of degree 2K in theta; on a bin of width
 //      pi / GQ_NB its local Taylor remainder of order 2 GQ_M is (2K pi / 2 GQ_NB)^16 / 16! --
@@ -476,7 +476,7 @@ __device__ int gq_mcheb(const double (&mu)[GQ_NM], double (&al)[GQ_M], double (&
 // and be <= 1 keep p_i within 3^8).  A zero takes the sign opposite to its predecessor (the
 // standard convention).  The signs are taken from the bit patterns with 32-bit integer logic:
 // the same tests as fp64 compares (v < 0: sign bit set and not +-0), but no VALU -> SGPR mask
-// -> SALU -> VALU round trips -- those made a Sturm evaluation ~1400 cycles (tools/gqnodes_lab:
+// -> SALU -> VALU round trips -- those made a Sturm evaluation ~1400 cycles (the node lab at cb85e44:
 // 24 bisections = 33.5 k of a node thread's 46 k cycles).  Equal to the compare form on 3 M random
 // and quantised (exact-zero) cases.
 __device__ __forceinline__ void gq_sign(double v, unsigned& neg, unsigned& nz) {
@@ -514,7 +514,6 @@ __device__ __forceinline__ int gq_sturm(const double (&al)[GQ_M], const double (
     return (int)cnt;
 }
 
-// thread = (bin, node k): the k-th node of the bin's Gauss rule (weight 0 when k >= n)
 // Stieltjes procedure for an exact bin's discrete measure (points u[j], weights w[j], j < np):
 // the same monic recurrence coefficients as gq_mcheb (be[0] = the mass) and the same cut-off,
 // here on the points themselves -- no moment cancellation
@@ -556,140 +555,9 @@ __device__ int gq_stieltjes(const double (&u)[GQ_XS], const double (&w)[GQ_XS], 
     return GQ_M;
 }
 
-__global__ __launch_bounds__(64) void k_gq_nodes(const double* __restrict__ hist, const GqBins* __restrict__ B,
-                                                 const GqExact* __restrict__ X, int world, double lmin, double c1,
-                                                 GqNodes* __restrict__ nd) {
-    const int id = blockIdx.x * 64 + threadIdx.x;
-    if (id >= GQ_NODES) return;
-    const int bin = id / GQ_M, k = id - bin * GQ_M;
-    double mu[GQ_NM];
-#pragma unroll
-    for (int j = 0; j < GQ_NM; ++j) {
-        double v = 0.0;
-        for (int g = 0; g < world; ++g) v += hist[(int64_t)g * GQ_HIST + j * GQ_NB + bin];   // rank order
-        mu[j] = v;
-    }
-    const int xn = X->n[bin];
-    if (xn <= GQ_M) {   // exact bin with at most GQ_M points: they are the rule (zero weights allowed)
-        nd->lam[id] = (k < xn) ? X->lam[bin][k] : lmin;
-        nd->w[id] = (k < xn) ? mu[k] : 0.0;
-        return;
-    }
-    double al[GQ_M], be[GQ_M];
-    int n;
-    if (xn <= GQ_XS) {   // exact bin: the Gauss rule of its points
-        // points closer than 1e-8 in u (eigenvalues a few ulp apart that the 4-ulp merge kept
-        // apart) go into their weighted mean first: a rule's moments of degree < 16 move by
-        // ~(16 d)^2, while a cluster of nodes makes the Christoffel weights lose digits
-        // (a 1e-13-wide pair cost 7e-9 of a weight in the numpy restatement)
-        double u[GQ_XS], w[GQ_XS];
-        int m = 0;
-        double ustart = 0.0;
-        for (int j = 0; j < xn; ++j) {
-            const double uj = (X->sv[bin][j] - B->mid[bin]) * B->ihw[bin], wj = mu[j];
-            if (m > 0 && uj - ustart < 1e-8) {
-                const double W = w[m - 1] + wj;
-                if (W > 0.0) u[m - 1] = (u[m - 1] * w[m - 1] + uj * wj) / W;
-                w[m - 1] = W;
-            } else {
-                u[m] = uj;
-                w[m] = wj;
-                ustart = uj;
-                ++m;
-            }
-        }
-        for (int j = m; j < GQ_XS; ++j) { u[j] = 0.0; w[j] = 0.0; }
-        if (m <= GQ_M) {   // the merged points are the rule
-            nd->lam[id] = (k < m) ? lmin + c1 * fma(B->hw[bin], u[k], B->mid[bin]) : lmin;
-            nd->w[id] = (k < m) ? w[k] : 0.0;
-            return;
-        }
-        n = gq_stieltjes(u, w, m, al, be);
-    } else {
-        n = gq_mcheb(mu, al, be);
-    }
-    double lamk = lmin, wk = 0.0;
-    if (k < n) {
-        // the off-diagonal of J_n and its reciprocals, once (Gershgorin and the Christoffel
-        // recurrence took 30 square roots and 7 divisions per thread)
-        double sb[GQ_M], isb[GQ_M];
-#pragma unroll
-        for (int i = 0; i < GQ_M; ++i) {
-            sb[i] = (i < n) ? sqrt(be[i]) : 0.0;
-            isb[i] = (i < n) ? 1.0 / sb[i] : 0.0;
-        }
-        // Gershgorin interval of J_n, then bisection for the (k+1)-th smallest eigenvalue
-        double lo = 1e300, hi = -1e300;
-#pragma unroll
-        for (int i = 0; i < GQ_M; ++i) {
-            if (i < n) {
-                const double r = ((i > 0) ? sb[i] : 0.0) + ((i + 1 < n) ? sb[i + 1] : 0.0);
-                lo = fmin(lo, al[i] - r);
-                hi = fmax(hi, al[i] + r);
-            }
-        }
-        // bisection until the bracket holds this eigenvalue alone and is below ~1e-7 (then
-        // Newton on p_n, quadratic, kept inside the bracket); close nodes (exact bins) keep
-        // bisecting until isolated, and a Newton step that leaves the bracket hands back to
-        // bisection down to rounding
-        int clo = 0, chi = n;
-        auto bisect = [&](int itmin, int itmax) {
-            for (int it = 0; it < itmax; ++it) {
-                if (it >= itmin && chi - clo == 1) break;
-                const double mid = 0.5 * (lo + hi);
-                if (mid <= lo || mid >= hi) break;
-                const int c = gq_sturm(al, be, n, mid);
-                if (c > k) { hi = mid; chi = c; }
-                else { lo = mid; clo = c; }
-            }
-        };
-        bisect(24, 96);
-        double u = 0.5 * (lo + hi);
-        bool newton_ok = true;
-        for (int it = 0; it < 6; ++it) {
-            double pm = 1.0, p = al[0] - u, dm = 0.0, d = -1.0;
-#pragma unroll
-            for (int i = 1; i < GQ_M; ++i) {
-                if (i < n) {
-                    const double pn = (al[i] - u) * p - be[i] * pm;
-                    const double dn = (al[i] - u) * d - p - be[i] * dm;
-                    pm = p;
-                    p = pn;
-                    dm = d;
-                    d = dn;
-                }
-            }
-            if (d == 0.0 || p == 0.0) break;
-            const double un = u - p / d;
-            if (!(un > lo && un < hi)) { newton_ok = false; break; }
-            if (un == u) break;
-            u = un;
-        }
-        if (!newton_ok) {
-            bisect(200, 200);   // to rounding (the loop ends when the midpoint stops moving)
-            u = 0.5 * (lo + hi);
-        }
-        // Christoffel weight 1 / sum_j phat_j(u)^2 (orthonormal recurrence)
-        double pm = 0.0, p = isb[0], ssum = p * p;
-#pragma unroll
-        for (int j = 0; j + 1 < GQ_M; ++j) {
-            if (j + 1 < n) {
-                const double pn = ((u - al[j]) * p - ((j > 0) ? sb[j] : 0.0) * pm) * isb[j + 1];
-                pm = p;
-                p = pn;
-                ssum += p * p;
-            }
-        }
-        wk = 1.0 / ssum;
-        lamk = lmin + c1 * fma(B->hw[bin], u, B->mid[bin]);
-    }
-    nd->lam[id] = lamk;
-    nd->w[id] = wk;
-}
-
-// One wave per bin (round 5; k_gq_nodes above is the thread-per-node form, kept for A/B as
-// FOTO_GQ_NODES=thread).  tools/gqnodes_lab: a node thread spent 28 k of its 38 k cycles in 24
-// serial Sturm bisections, and only 32 waves ran on a 256-CU chip.  Here lanes 8k .. 8k+7 find
+// One wave per bin (round 5).  The round-4 form ran a thread per node (k_gq_nodes, and its lab
+// tools/gqnodes_lab.hip, in the history at cb85e44): a node thread spent 28 k of its 38 k cycles
+// in 24 serial Sturm bisections, and only 32 waves ran on a 256-CU chip.  Here lanes 8k .. 8k+7 find
 // node k together by 9-section -- each lane evaluates the Sturm count at one of the 8 interior
 // points of the bracket, a ballot picks the sub-interval -- 3.17 bits per round, so 8 rounds
 // replace the 24 bisections, and 256 waves fill the chip.  n, the bracket and the counts are the
@@ -697,7 +565,7 @@ __global__ __launch_bounds__(64) void k_gq_nodes(const double* __restrict__ hist
 // and the Christoffel weight run redundantly and lane 8k stores.
 // part != null (single shard): the bin's 16 moments are summed here from the chunk sums, in
 // k_gq_perm_reduce's order (lane l: chunks l, l + 64, ..., then gq_uniform_sum) -- the same bits,
-// one launch less; otherwise hist holds the world's histograms (rank order, as k_gq_nodes).
+// one launch less; otherwise hist holds the world's histograms, summed in rank order.
 __global__ __launch_bounds__(256) void k_gq_nodes_w(const double* __restrict__ hist, const double* __restrict__ part,
                                                     const int* __restrict__ cfirst, const GqBins* __restrict__ B,
                                                     const GqExact* __restrict__ X, int world, double lmin, double c1,
@@ -721,7 +589,7 @@ __global__ __launch_bounds__(256) void k_gq_nodes_w(const double* __restrict__ h
             }
         }
 #pragma unroll
-        for (int m = 0; m < GQ_NM; ++m) mu[m] = 0.0 + gq_uniform_sum(t[m]);   // (k_gq_nodes' 0 + hist)
+        for (int m = 0; m < GQ_NM; ++m) mu[m] = 0.0 + gq_uniform_sum(t[m]);   // (0 + sum: the bits of the hist path below)
     } else {
 #pragma unroll
         for (int j = 0; j < GQ_NM; ++j) {
@@ -740,7 +608,11 @@ __global__ __launch_bounds__(256) void k_gq_nodes_w(const double* __restrict__ h
     }
     double al[GQ_M], be[GQ_M];
     int n;
-    if (xn <= GQ_XS) {   // exact bin: the Gauss rule of its points (k_gq_nodes' merge, see there)
+    if (xn <= GQ_XS) {   // exact bin: the Gauss rule of its points
+        // points closer than 1e-8 in u (eigenvalues a few ulp apart that the 4-ulp merge kept
+        // apart) go into their weighted mean first: a rule's moments of degree < 16 move by
+        // ~(16 d)^2, while a cluster of nodes makes the Christoffel weights lose digits
+        // (a 1e-13-wide pair cost 7e-9 of a weight in the numpy restatement)
         double u[GQ_XS], w[GQ_XS];
         int m = 0;
         double ustart = 0.0;
@@ -816,7 +688,7 @@ __global__ __launch_bounds__(256) void k_gq_nodes_w(const double* __restrict__ h
                 }
             }
         };
-        auto bisect = [&](int itmax) {   // (rounding: the last bits, as k_gq_nodes)
+        auto bisect = [&](int itmax) {   // (rounding: the last bits)
             for (int it = 0; it < itmax; ++it) {
                 const double mid = 0.5 * (lo + hi);
                 if (mid <= lo || mid >= hi) break;
@@ -1249,13 +1121,16 @@ __device__ __forceinline__ int gq_load_tab(double* tabL, const double* __restric
 // (105 us vs ~60 for the pair): a column kernel holds the 64 KB table at 2 waves per SIMD and
 // could keep only one or two b^ loads per lane in flight ahead of its long acos + Clenshaw
 // chains, while the elementwise kernel runs 1024-thread blocks (16 waves per CU) over
-// coalesced pairs of elements.
+// coalesced pairs of elements.  Round 5 tried again with cheaper elements and 512-thread
+// blocks (k_dct_t_inv_gq, bit-identical): 92 us against 74 for the pair; it is in the history
+// at cb85e44.
 
 // x^ = Q(lam) b^ over the whole box: persistent 1024-thread blocks (the table loaded once per
 // block); a wave takes whole rows (one division per row), two elements per lane when Nx is even.
 // (Round 4: a whole 640-wide row's loads issued before any use, 5 or 8 pairs per lane: DCT chain
 // 143 vs 139-140 us, not kept.)
 constexpr int GQ_XNTH = 1024;
+constexpr int GQ_XQL = 17;   // table rows a block holds in LDS (68 KB: two blocks per CU); rows beyond from global
 __global__ __launch_bounds__(GQ_XNTH) void k_gq_xhat(SpecTab T, const double* __restrict__ bh,
                                                      const double* __restrict__ tab, const GqState* __restrict__ S,
                                                      const GqBins* __restrict__ Bg, double ic1, double* __restrict__ out,
@@ -1290,77 +1165,5 @@ __global__ __launch_bounds__(GQ_XNTH) void k_gq_xhat(SpecTab T, const double* __
                 dst[kx] = gq_q(tabL, tab, b, (lt - L.mid[b]) * L.ihw[b], qn, ql) * src[kx];
             }
         }
-    }
-}
-
-// x^ = Q(lam) b^ fused into the inverse t-DCT column kernel (round 5; FOTO_GQ_TFUSE=0: k_gq_xhat
-// then k_dct_t_inv_xhat<PLAIN>, the round-4 pair).  A thread owns a (kx, ky) column: its NTT b^
-// loads are issued first, then the tables come into LDS (bins + the table's first ql rows, one
-// barrier), then Q is evaluated per element exactly as k_gq_xhat does it (the same lam, bin,
-// local variable and Clenshaw: x^ bit-identical) and the column goes through the inverse DCT in
-// registers as k_dct_t_inv_xhat's.  x^ never goes to memory: 16 B per voxel and a launch less.
-// Round 3 measured this fusion slower (105 vs 95 us) with an acos per element and a 64 KB table
-// at 2 waves per SIMD; the element cost is now a few compares and 512-thread blocks keep 4 waves
-// per SIMD (2 blocks per CU at <= 80 KB of LDS each: ql <= 17 rows).
-constexpr int GQ_TFNTH = 512;
-constexpr int GQ_TFWPE = 4;   // waves per SIMD
-constexpr int GQ_TFPF = 4;    // b^ loads kept in flight ahead of the element being finished
-template <int NTT>
-__global__ __launch_bounds__(GQ_TFNTH) __attribute__((amdgpu_waves_per_eu(GQ_TFWPE))) void k_dct_t_inv_gq(
-        SpecTab T, const double* __restrict__ Ch, const double* __restrict__ bh, const double* __restrict__ tab,
-        const GqState* __restrict__ S, const GqBins* __restrict__ Bg, double ic1, double* __restrict__ out, int ql) {
-    constexpr int H = TCol<NTT>::H;
-    constexpr int D = GQ_TFPF < NTT ? GQ_TFPF : NTT;
-    static_assert(D % 2 == 0 && D >= 2, "the window moves by pairs");
-    extern __shared__ double tabL[];
-    __shared__ __attribute__((aligned(16))) GqBins L;
-    const int64_t ncols = (int64_t)T.nyl * T.Nx;
-    const int64_t c = (int64_t)blockIdx.x * GQ_TFNTH + threadIdx.x;
-    const bool ok = c < ncols;
-    const int64_t cc = ok ? c : 0;
-    // the first D elements' loads, then the tables (their barrier)
-    double pf[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) pf[k] = ld_dead(&bh[k * ncols + cc]);
-    gq_load_bins(&L, Bg);
-    const int qn = gq_load_tab(tabL, tab, S, ql);   // (its barrier covers the bins too)
-    const int kyl = (int)(cc / T.Nx), kx = (int)(cc - (int64_t)kyl * T.Nx), ky = T.y0 + kyl;
-    const double myv = T.my[ky], mxv = T.mx[kx];
-    // x^_k = Q(lam_k) b^_k element by element (k_gq_xhat's lam, bin, local variable and Clenshaw,
-    // bit for bit), each folded at once into the inverse DCT's half sums: e_j over the even k,
-    // o_j over the odd ones, in k_dct_t_inv_xhat's order (m ascending) -- the column's 32 values
-    // never need to be live together
-    double e[H], o[H];
-#pragma unroll
-    for (int j = 0; j < H; ++j) { e[j] = 0.0; o[j] = 0.0; }
-    // a runtime loop over the pairs (2m, 2m + 1): unrolled over the column, the compiler held the
-    // DCT matrix's 512 uniform values in scalar registers across it and spilled; the b^ loads
-    // run D elements ahead through a register window shifted by two per pair
-    auto qx = [&](int k, double bv) {
-        const double rowmu = T.mt[k] + myv;   // k_gq_xhat's rowmu
-        const double lt = gq_s(T.r * (rowmu + mxv), ic1);
-        const int b = gq_find_bin(L.hi, L.cell, lt);
-        return gq_q(tabL, tab, b, (lt - L.mid[b]) * L.ihw[b], qn, ql) * bv;
-    };
-#pragma unroll 1
-    for (int m = 0; m < H; ++m) {
-        const double b0 = pf[0], b1 = pf[1];
-#pragma unroll
-        for (int i = 0; i + 2 < D; ++i) pf[i] = pf[i + 2];
-        const int kn = 2 * m + D;   // the next two loads into the window's last slots
-        pf[D - 2] = (kn < NTT) ? ld_dead(&bh[kn * ncols + cc]) : 0.0;
-        pf[D - 1] = (kn + 1 < NTT) ? ld_dead(&bh[(kn + 1) * ncols + cc]) : 0.0;
-        const double xe = qx(2 * m, b0);
-#pragma unroll
-        for (int j = 0; j < H; ++j) e[j] = fma(Ch[m * H + j], xe, e[j]);
-        const double xo = qx(2 * m + 1, b1);
-#pragma unroll
-        for (int j = 0; j < H; ++j) o[j] = fma(Ch[H * H + m * H + j], xo, o[j]);
-    }
-    if (!ok) return;
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-        out[j * ncols + c] = e[j] + o[j];
-        out[(NTT - 1 - j) * ncols + c] = e[j] - o[j];
     }
 }

@@ -1209,437 +1209,14 @@ __global__ __launch_bounds__(1024) void k_mg_coarse(MGLev L, const CGScal* S, co
     }
 }
 
-// The small levels in one block (FOTO_MG_TAIL=1; off by default -- measured slower): below ~80x60
-// cells a level kernel is a few blocks whose launch and drain look costlier than its work (6-9 us
-// each, five of the 13 launches of a PCG iteration at 640x480).  k_mg_tail runs the down legs of
-// levels l0 .. c-1, the coarsest solve and the up legs back to l0 in one 1024-thread block, level
-// arrays in global memory (L2-resident), a barrier between stages, every cell with the level
-// kernels' formulas in their order (the same preconditioner bit for bit).  Replayed from the
-// hipGraph the separate launches are cheap, and one CU's stages are latency-bound: 180 us per
-// PCG iteration with the tail from 80x60 down, 137.6 from 40x30, 133.5-133.8 without (r03, A/B on
-// one box).
-constexpr int MG_TAIL_MAX = 6;
-constexpr int MG_TAIL_CELLS = 1300;   // levels at most this many cells join the tail (5000: slower)
-struct MGTail {
-    int nl;                            // levels in the tail; the last one is the coarsest
-    MGLev L[MG_TAIL_MAX];
-    double* f[MG_TAIL_MAX];
-    double* x[MG_TAIL_MAX];
-    double* y[MG_TAIL_MAX];
-};
-
-__global__ __launch_bounds__(1024) void k_mg_tail(MGTail T, const CGScal* S) {
-    if (S->done) return;
-    const int tid = threadIdx.x;
-    const int nl = T.nl;
-    for (int l = 0; l + 1 < nl; ++l) {   // down legs (k_mg_down2's three stages, level-wide)
-        const MGLev L = T.L[l];
-        const int w = L.w, h = L.h;
-        const int64_t n = (int64_t)w * h;
-        const double* f = T.f[l];
-        double* x = T.x[l];
-        double* rr = T.y[l];   // the residual; y is the up leg's output, free until then
-        for (int64_t i = tid; i < n; i += 1024) {
-            double z0, z1, z2;
-            mg_dinv(L, i, f[i], f[n + i], f[2 * n + i], z0, z1, z2);
-            x[i] = z0 * MG_OMEGA; x[n + i] = z1 * MG_OMEGA; x[2 * n + i] = z2 * MG_OMEGA;
-        }
-        __syncthreads();
-        for (int64_t i = tid; i < n; i += 1024) {
-            const int gy = (int)(i / w), gx = (int)(i - (int64_t)gy * w);
-            double a0, a1, a2, v0, v1, v2;
-            mg_apply_t(L, gx, gy, i, [&](int fl, int dy, int dx) { return x[fl * n + i + (int64_t)dy * w + dx]; }, a0,
-                       a1, a2, v0, v1, v2);
-            rr[i] = f[i] - a0; rr[n + i] = f[n + i] - a1; rr[2 * n + i] = f[2 * n + i] - a2;
-        }
-        __syncthreads();
-        const int wc = T.L[l + 1].w, hc = T.L[l + 1].h;
-        const int64_t nc = (int64_t)wc * hc;
-        double* fc = T.f[l + 1];
-        for (int64_t I0 = tid; I0 < nc; I0 += 1024) {
-            const int J = (int)(I0 / wc), K = (int)(I0 - (int64_t)J * wc);
-            double wy[4], wx[4];
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                const int y = 2 * J - 1 + d, xx = 2 * K - 1 + d;
-                wy[d] = (y >= 0 && y < h) ? mg_w1(y, J, hc) : 0.0;
-                wx[d] = (xx >= 0 && xx < w) ? mg_w1(xx, K, wc) : 0.0;
-            }
-            double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-#pragma unroll
-            for (int dy = 0; dy < 4; ++dy) {
-                double b0 = 0.0, b1 = 0.0, b2 = 0.0;
-                const int y = 2 * J - 1 + dy;
-#pragma unroll
-                for (int dx = 0; dx < 4; ++dx) {
-                    const int xx = 2 * K - 1 + dx;
-                    const bool in = y >= 0 && y < h && xx >= 0 && xx < w;
-                    const int64_t i = in ? (int64_t)y * w + xx : 0;
-                    b0 += wx[dx] * (in ? rr[i] : 0.0);
-                    b1 += wx[dx] * (in ? rr[n + i] : 0.0);
-                    b2 += wx[dx] * (in ? rr[2 * n + i] : 0.0);
-                }
-                a0 += wy[dy] * b0; a1 += wy[dy] * b1; a2 += wy[dy] * b2;
-            }
-            fc[I0] = 0.25 * a0;
-            fc[nc + I0] = 0.25 * a1;
-            fc[2 * nc + I0] = 0.25 * a2;
-        }
-        __syncthreads();
-    }
-    {   // the coarsest level: k_mg_coarse<false>'s sweeps
-        const MGLev L = T.L[nl - 1];
-        __shared__ double xs[2][3 * MG_COARSE];
-        const int n = L.w * L.h, i = tid;
-        const bool in = i < n;
-        const int y = in ? i / L.w : 0, xx = in ? i - y * L.w : 0;
-        const double* f = T.f[nl - 1];
-        double f0 = 0, f1 = 0, f2v = 0;
-        double b[6] = {0, 0, 0, 0, 0, 0}, d[6] = {0, 0, 0, 0, 0, 0};
-        const bool hxm = xx > 0, hxp = xx < L.w - 1, hym = y > 0, hyp = y < L.h - 1;
-        const double c = (double)mg_ncount(xx, y, L.w, L.h);
-        if (in) {
-            f0 = f[i]; f1 = f[n + i]; f2v = f[2 * n + i];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) { b[k] = L.B[k * n + i]; d[k] = L.Dinv[k * n + i]; }
-            const double z0 = d[0] * f0 + d[1] * f1 + d[2] * f2v, z1 = d[1] * f0 + d[3] * f1 + d[4] * f2v,
-                         z2 = d[2] * f0 + d[4] * f1 + d[5] * f2v;
-            xs[0][i] = MG_OMEGA * z0; xs[0][n + i] = MG_OMEGA * z1; xs[0][2 * n + i] = MG_OMEGA * z2;
-        }
-        __syncthreads();
-        const double sc[3] = {L.s0, L.s1, L.s2};
-        int cur = 0;
-        for (int sweep = 1; sweep < MG_CSWEEPS; ++sweep) {
-            if (in) {
-                const double* xc = xs[cur];
-                double v[3], a[3];
-#pragma unroll
-                for (int fl = 0; fl < 3; ++fl) {
-                    const double* q = xc + fl * n;
-                    v[fl] = q[i];
-                    const double nb = (hxm ? q[i - 1] : 0.0) + (hxp ? q[i + 1] : 0.0) + (hym ? q[i - L.w] : 0.0) +
-                                      (hyp ? q[i + L.w] : 0.0);
-                    a[fl] = sc[fl] * (c * v[fl] - nb);
-                }
-                const double r0 = f0 - (a[0] + b[0] * v[0] + b[1] * v[1] + b[2] * v[2]);
-                const double r1 = f1 - (a[1] + b[1] * v[0] + b[3] * v[1] + b[4] * v[2]);
-                const double r2 = f2v - (a[2] + b[2] * v[0] + b[4] * v[1] + b[5] * v[2]);
-                xs[cur ^ 1][i] = v[0] + MG_OMEGA * (d[0] * r0 + d[1] * r1 + d[2] * r2);
-                xs[cur ^ 1][n + i] = v[1] + MG_OMEGA * (d[1] * r0 + d[3] * r1 + d[4] * r2);
-                xs[cur ^ 1][2 * n + i] = v[2] + MG_OMEGA * (d[2] * r0 + d[4] * r1 + d[5] * r2);
-            }
-            cur ^= 1;
-            __syncthreads();
-        }
-        if (in) {
-            double* xo = T.x[nl - 1];
-            xo[i] = xs[cur][i]; xo[n + i] = xs[cur][n + i]; xo[2 * n + i] = xs[cur][2 * n + i];
-        }
-        __syncthreads();
-    }
-    for (int l = nl - 2; l >= 0; --l) {   // up legs (k_mg_up2<false>'s two stages, level-wide)
-        const MGLev L = T.L[l];
-        const int w = L.w, h = L.h;
-        const int64_t n = (int64_t)w * h;
-        const int wc = T.L[l + 1].w, hc = T.L[l + 1].h;
-        const int64_t nc = (int64_t)wc * hc;
-        const double* ec = (l + 1 == nl - 1) ? T.x[nl - 1] : T.y[l + 1];
-        double* x = T.x[l];   // x' = x + P ec, in place
-        for (int64_t i = tid; i < n; i += 1024) {
-            const int gy = (int)(i / w), gx = (int)(i - (int64_t)gy * w);
-            const int X0 = gx >> 1, Y0 = gy >> 1;
-            int X1 = (gx & 1) ? X0 + 1 : X0 - 1, Y1 = (gy & 1) ? Y0 + 1 : Y0 - 1;
-            X1 = X1 < 0 ? 0 : (X1 > wc - 1 ? wc - 1 : X1);
-            Y1 = Y1 < 0 ? 0 : (Y1 > hc - 1 ? hc - 1 : Y1);
-            const int64_t c00 = (int64_t)Y0 * wc + X0, c01 = (int64_t)Y0 * wc + X1, c10 = (int64_t)Y1 * wc + X0,
-                          c11 = (int64_t)Y1 * wc + X1;
-#pragma unroll
-            for (int fl = 0; fl < 3; ++fl) {
-                const double* e = ec + fl * nc;
-                x[fl * n + i] = x[fl * n + i] + (0.5625 * e[c00] + 0.1875 * e[c01] + 0.1875 * e[c10] + 0.0625 * e[c11]);
-            }
-        }
-        __syncthreads();
-        const double* f = T.f[l];
-        double* out = T.y[l];
-        for (int64_t i = tid; i < n; i += 1024) {
-            const int gy = (int)(i / w), gx = (int)(i - (int64_t)gy * w);
-            double a0, a1, a2, v0, v1, v2, z0, z1, z2;
-            mg_apply_t(L, gx, gy, i, [&](int fl, int dy, int dx) { return x[fl * n + i + (int64_t)dy * w + dx]; }, a0,
-                       a1, a2, v0, v1, v2);
-            const double f0 = f[i], f1 = f[n + i], f2v = f[2 * n + i];
-            mg_dinv(L, i, f0 - a0, f1 - a1, f2v - a2, z0, z1, z2);
-            out[i] = v0 + MG_OMEGA * z0;
-            out[n + i] = v1 + MG_OMEGA * z1;
-            out[2 * n + i] = v2 + MG_OMEGA * z2;
-        }
-        __syncthreads();
-    }
-}
-
-// ----------------------------------------------------------------------------- persistent small levels
-// The levels from l0 down (each at most MG_PT_TILES tiles), the coarsest solve and the up legs
-// back to l0 in ONE launch of tiles(l0) blocks (round 5, opt-in FOTO_MG_PTAIL=1): every small
-// level kernel sat at a ~5.5 us launch floor.  Measured slower (profiles/r05_gn_ptail.txt): at
-// 640x480 the launch takes 55 us for the 7 stages that the level kernels run in 43 -- a stage
-// here is ~8 us, its `sc1` loads of the previous stage's tiles (dropped from the L2 by the `sc1`
-// stores, served across the XCDs) plus the barrier cost as much as a kernel boundary does; the
-// polls' s_sleep is not it (the same without).  Stage s's blocks hand their tiles to
-// stage s + 1's through a grid barrier: every wave waits for its stores, the block joins a
-// workgroup barrier, one lane adds to an agent-scope arrival counter and polls it with `sc1`
-// loads until the whole grid has arrived.  Every load and store of the handed-off level arrays
-// (f, x, y) is an `sc1` access (agent-scope relaxed atomics: L2-served, coherent across the
-// XCDs without cache flushes -- MI355X_MICROARCH.md's hand-off table, row 1); B and D^-1 are
-// read-only here.  Each cell's arithmetic is the level kernels' in their order (the same
-// preconditioner bit for bit).  The counter only grows: launch i of a solve waits for
-// (i * syncs + s + 1) * blocks arrivals (i = the PCG iteration index, S->pad[0]); the host zeroes
-// it with the solve's scalars.  A poll that never completes (blocks not co-resident -- 64 small
-// blocks on a 256-CU device) gives up after ~1 s and flags S->pad[1] instead of hanging.
-constexpr int MG_PT_TILES = 64;     // a level joins the tail when it has at most this many tiles
-constexpr int MG_PT_MAX = 8;
-struct MGPTail {
-    int nl;                         // levels l0 .. c (the last is the coarsest)
-    MGLev L[MG_PT_MAX];
-    double* f[MG_PT_MAX];
-    double* x[MG_PT_MAX];
-    double* y[MG_PT_MAX];
-    unsigned* counter;
-    int syncs;                      // grid barriers per launch
-};
-
-__device__ __forceinline__ double pt_ld(const double* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void pt_st(double* p, double v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ void pt_grid_sync(unsigned* counter, unsigned target, CGScal* S) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's sc1 stores have completed
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int spins = 0;
-        while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            __builtin_amdgcn_s_sleep(2);   // between two polls of the arrival counter
-            if (++spins > (1 << 20)) {   // (~1 s: a barrier normally completes in microseconds)   // never co-resident: flag it, do not hang the device
-                __hip_atomic_store(&S->pad[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
-    }
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(NT) void k_mg_ptail(MGPTail T, CGScal* S) {
-    if (S->done) return;
-    constexpr int XW = GT_X + 4, XH = GT_Y + 4, RW = GT_X + 2, RH = GT_Y + 2;
-    // one LDS pool: the level stages' x / r tiles, or the coarsest solve's two 3n buffers
-    constexpr int PT_POOL = (3 * XH * XW + 3 * RH * RW) > 6 * MG_COARSE ? (3 * XH * XW + 3 * RH * RW) : 6 * MG_COARSE;
-    __shared__ double pool[PT_POOL];
-    auto xs = reinterpret_cast<double(*)[XH][XW]>(pool);
-    auto rs = reinterpret_cast<double(*)[RH][RW]>(pool + 3 * XH * XW);
-    const unsigned nb = gridDim.x;
-    unsigned target = (unsigned)S->pad[0] * (unsigned)T.syncs * nb;
-    const int nl = T.nl, c = nl - 1;
-    // ---- down legs: k_mg_down2<false>'s three stages, tile = blockIdx.x
-    for (int l = 0; l < c; ++l) {
-        const MGLev L = T.L[l];
-        const int w = L.w, h = L.h, wc = T.L[l + 1].w, hc = T.L[l + 1].h;
-        const int tiles_x = (w + GT_X - 1) / GT_X, ntiles = tiles_x * ((h + GT_Y - 1) / GT_Y);
-        if ((int)blockIdx.x < ntiles) {
-            const int64_t n = (int64_t)w * h, nc = (int64_t)wc * hc;
-            const double* f = T.f[l];
-            double* xg = T.x[l];
-            double* fc = T.f[l + 1];
-            const int x0 = (blockIdx.x % tiles_x) * GT_X, y0 = (blockIdx.x / tiles_x) * GT_Y;
-            for (int cc = threadIdx.x; cc < XH * XW; cc += NT) {
-                const int ly = cc / XW, lx = cc - ly * XW, gy = y0 - 2 + ly, gx = x0 - 2 + lx;
-                double z0 = 0.0, z1 = 0.0, z2 = 0.0;
-                if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
-                    const int64_t i = (int64_t)gy * w + gx;
-                    mg_dinv(L, i, pt_ld(&f[i]), pt_ld(&f[n + i]), pt_ld(&f[2 * n + i]), z0, z1, z2);
-                    z0 *= MG_OMEGA; z1 *= MG_OMEGA; z2 *= MG_OMEGA;
-                }
-                xs[0][ly][lx] = z0; xs[1][ly][lx] = z1; xs[2][ly][lx] = z2;
-            }
-            __syncthreads();
-            for (int cc = threadIdx.x; cc < RH * RW; cc += NT) {
-                const int ly = cc / RW, lx = cc - ly * RW, gy = y0 - 1 + ly, gx = x0 - 1 + lx;
-                double r0 = 0.0, r1 = 0.0, r2 = 0.0;
-                if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
-                    const int64_t i = (int64_t)gy * w + gx;
-                    double a0, a1, a2, v0, v1, v2;
-                    mg_apply_t(L, gx, gy, i, [&](int fl, int dy, int dx) { return xs[fl][ly + 1 + dy][lx + 1 + dx]; },
-                               a0, a1, a2, v0, v1, v2);
-                    r0 = pt_ld(&f[i]) - a0; r1 = pt_ld(&f[n + i]) - a1; r2 = pt_ld(&f[2 * n + i]) - a2;
-                    if (ly >= 1 && ly <= GT_Y && lx >= 1 && lx <= GT_X) {
-                        pt_st(&xg[i], v0); pt_st(&xg[n + i], v1); pt_st(&xg[2 * n + i], v2);
-                    }
-                }
-                rs[0][ly][lx] = r0; rs[1][ly][lx] = r1; rs[2][ly][lx] = r2;
-            }
-            __syncthreads();
-            for (int cc = threadIdx.x; cc < (GT_Y / 2) * (GT_X / 2); cc += NT) {
-                const int cy = cc / (GT_X / 2), cx = cc - cy * (GT_X / 2);
-                const int J = y0 / 2 + cy, K = x0 / 2 + cx;
-                if (J >= hc || K >= wc) continue;
-                double wy[4], wx[4];
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const int y = 2 * J - 1 + d, x = 2 * K - 1 + d;
-                    wy[d] = (y >= 0 && y < h) ? mg_w1(y, J, hc) : 0.0;
-                    wx[d] = (x >= 0 && x < w) ? mg_w1(x, K, wc) : 0.0;
-                }
-                double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-#pragma unroll
-                for (int dy = 0; dy < 4; ++dy) {
-                    double b0 = 0.0, b1 = 0.0, b2 = 0.0;
-#pragma unroll
-                    for (int dx = 0; dx < 4; ++dx) {
-                        const int ly = 2 * cy + dy, lx = 2 * cx + dx;
-                        b0 += wx[dx] * rs[0][ly][lx];
-                        b1 += wx[dx] * rs[1][ly][lx];
-                        b2 += wx[dx] * rs[2][ly][lx];
-                    }
-                    a0 += wy[dy] * b0; a1 += wy[dy] * b1; a2 += wy[dy] * b2;
-                }
-                const int64_t I = (int64_t)J * wc + K;
-                pt_st(&fc[I], 0.25 * a0);
-                pt_st(&fc[nc + I], 0.25 * a1);
-                pt_st(&fc[2 * nc + I], 0.25 * a2);
-            }
-        }
-        target += nb;
-        pt_grid_sync(T.counter, target, S);
-    }
-    // ---- the coarsest level: k_mg_coarse<false>'s sweeps in block 0, up to 4 cells per thread
-    if (blockIdx.x == 0) {
-        constexpr int CP = (MG_COARSE + NT - 1) / NT;
-        const MGLev L = T.L[c];
-        const int n = L.w * L.h;
-        auto xb = [&](int i) { return pool + i * (3 * MG_COARSE); };   // the two sweep buffers
-        const double* f = T.f[c];
-        double f0[CP], f1[CP], f2v[CP], b[CP][6], d[CP][6], cn[CP];
-        int ci[CP];
-        bool in[CP], hxm[CP], hxp[CP], hym[CP], hyp[CP];
-#pragma unroll
-        for (int q = 0; q < CP; ++q) {
-            const int i = threadIdx.x + q * NT;
-            ci[q] = i;
-            in[q] = i < n;
-            const int y = in[q] ? i / L.w : 0, xx = in[q] ? i - y * L.w : 0;
-            hxm[q] = xx > 0; hxp[q] = xx < L.w - 1; hym[q] = y > 0; hyp[q] = y < L.h - 1;
-            cn[q] = (double)mg_ncount(xx, y, L.w, L.h);
-            f0[q] = f1[q] = f2v[q] = 0.0;
-            for (int k = 0; k < 6; ++k) { b[q][k] = 0.0; d[q][k] = 0.0; }
-            if (in[q]) {
-                f0[q] = pt_ld(&f[i]); f1[q] = pt_ld(&f[n + i]); f2v[q] = pt_ld(&f[2 * n + i]);
-#pragma unroll
-                for (int k = 0; k < 6; ++k) { b[q][k] = L.B[k * n + i]; d[q][k] = L.Dinv[k * n + i]; }
-                const double z0 = d[q][0] * f0[q] + d[q][1] * f1[q] + d[q][2] * f2v[q],
-                             z1 = d[q][1] * f0[q] + d[q][3] * f1[q] + d[q][4] * f2v[q],
-                             z2 = d[q][2] * f0[q] + d[q][4] * f1[q] + d[q][5] * f2v[q];
-                xb(0)[i] = MG_OMEGA * z0; xb(0)[n + i] = MG_OMEGA * z1; xb(0)[2 * n + i] = MG_OMEGA * z2;
-            }
-        }
-        __syncthreads();
-        const double sc[3] = {L.s0, L.s1, L.s2};
-        int cur = 0;
-        for (int sweep = 1; sweep < MG_CSWEEPS; ++sweep) {
-#pragma unroll
-            for (int q = 0; q < CP; ++q) {
-                if (!in[q]) continue;
-                const int i = ci[q];
-                const double* xc = xb(cur);
-                double v[3], a[3];
-#pragma unroll
-                for (int fl = 0; fl < 3; ++fl) {
-                    const double* qq = xc + fl * n;
-                    v[fl] = qq[i];
-                    const double nbv = (hxm[q] ? qq[i - 1] : 0.0) + (hxp[q] ? qq[i + 1] : 0.0) +
-                                       (hym[q] ? qq[i - L.w] : 0.0) + (hyp[q] ? qq[i + L.w] : 0.0);
-                    a[fl] = sc[fl] * (cn[q] * v[fl] - nbv);
-                }
-                const double r0 = f0[q] - (a[0] + b[q][0] * v[0] + b[q][1] * v[1] + b[q][2] * v[2]);
-                const double r1 = f1[q] - (a[1] + b[q][1] * v[0] + b[q][3] * v[1] + b[q][4] * v[2]);
-                const double r2 = f2v[q] - (a[2] + b[q][2] * v[0] + b[q][4] * v[1] + b[q][5] * v[2]);
-                xb(cur ^ 1)[i] = v[0] + MG_OMEGA * (d[q][0] * r0 + d[q][1] * r1 + d[q][2] * r2);
-                xb(cur ^ 1)[n + i] = v[1] + MG_OMEGA * (d[q][1] * r0 + d[q][3] * r1 + d[q][4] * r2);
-                xb(cur ^ 1)[2 * n + i] = v[2] + MG_OMEGA * (d[q][2] * r0 + d[q][4] * r1 + d[q][5] * r2);
-            }
-            cur ^= 1;
-            __syncthreads();
-        }
-        double* xo = T.x[c];
-#pragma unroll
-        for (int q = 0; q < CP; ++q) {
-            if (!in[q]) continue;
-            const int i = ci[q];
-            pt_st(&xo[i], xb(cur)[i]); pt_st(&xo[n + i], xb(cur)[n + i]); pt_st(&xo[2 * n + i], xb(cur)[2 * n + i]);
-        }
-    }
-    target += nb;
-    pt_grid_sync(T.counter, target, S);
-    // ---- up legs: k_mg_up2<false>'s two stages
-    for (int l = c - 1; l >= 0; --l) {
-        const MGLev L = T.L[l];
-        const int w = L.w, h = L.h, wc = T.L[l + 1].w, hc = T.L[l + 1].h;
-        const int tiles_x = (w + GT_X - 1) / GT_X, ntiles = tiles_x * ((h + GT_Y - 1) / GT_Y);
-        if ((int)blockIdx.x < ntiles) {
-            const int64_t n = (int64_t)w * h, nc = (int64_t)wc * hc;
-            const double* ec = (l + 1 == c) ? T.x[c] : T.y[l + 1];
-            const double* f = T.f[l];
-            const double* xg = T.x[l];
-            double* outp = T.y[l];
-            const int x0 = (blockIdx.x % tiles_x) * GT_X, y0 = (blockIdx.x / tiles_x) * GT_Y;
-            for (int cc = threadIdx.x; cc < RH * RW; cc += NT) {
-                const int ly = cc / RW, lx = cc - ly * RW, gy = y0 - 1 + ly, gx = x0 - 1 + lx;
-                double v[3] = {0.0, 0.0, 0.0};
-                if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
-                    const int64_t i = (int64_t)gy * w + gx;
-                    const int X0 = gx >> 1, Y0 = gy >> 1;
-                    int X1 = (gx & 1) ? X0 + 1 : X0 - 1, Y1 = (gy & 1) ? Y0 + 1 : Y0 - 1;
-                    X1 = X1 < 0 ? 0 : (X1 > wc - 1 ? wc - 1 : X1);
-                    Y1 = Y1 < 0 ? 0 : (Y1 > hc - 1 ? hc - 1 : Y1);
-                    const int64_t c00 = (int64_t)Y0 * wc + X0, c01 = (int64_t)Y0 * wc + X1,
-                                  c10 = (int64_t)Y1 * wc + X0, c11 = (int64_t)Y1 * wc + X1;
-#pragma unroll
-                    for (int fl = 0; fl < 3; ++fl) {
-                        const double* e = ec + fl * nc;
-                        v[fl] = pt_ld(&xg[fl * n + i]) + (0.5625 * pt_ld(&e[c00]) + 0.1875 * pt_ld(&e[c01]) +
-                                                          0.1875 * pt_ld(&e[c10]) + 0.0625 * pt_ld(&e[c11]));
-                    }
-                }
-                xs[0][ly][lx] = v[0]; xs[1][ly][lx] = v[1]; xs[2][ly][lx] = v[2];
-            }
-            __syncthreads();
-            for (int cc = threadIdx.x; cc < GT_Y * GT_X; cc += NT) {
-                const int ly = cc / GT_X, lx = cc - ly * GT_X, gy = y0 + ly, gx = x0 + lx;
-                if (gx >= w || gy >= h) continue;
-                const int64_t i = (int64_t)gy * w + gx;
-                double a0, a1, a2, v0, v1, v2, z0, z1, z2;
-                mg_apply_t(L, gx, gy, i, [&](int fl, int dy, int dx) { return xs[fl][ly + 1 + dy][lx + 1 + dx]; }, a0,
-                           a1, a2, v0, v1, v2);
-                const double f0 = pt_ld(&f[i]), f1 = pt_ld(&f[n + i]), f2v = pt_ld(&f[2 * n + i]);
-                mg_dinv(L, i, f0 - a0, f1 - a1, f2v - a2, z0, z1, z2);
-                pt_st(&outp[i], v0 + MG_OMEGA * z0);
-                pt_st(&outp[n + i], v1 + MG_OMEGA * z1);
-                pt_st(&outp[2 * n + i], v2 + MG_OMEGA * z2);
-            }
-        }
-        if (l > 0) {
-            target += nb;
-            pt_grid_sync(T.counter, target, S);
-        }
-    }
-}
-
 // ----------------------------------------------------------------------------- last level + coarsest in LDS
 // The down leg of the level above the coarsest, the coarsest solve and that level's up leg in one
 // block whose vectors never leave the LDS (round 5, default where the level has at most
 // MG_LT_CELLS cells: 40x30 at 640x480 and 320x240; FOTO_MG_LTAIL=0: the three level kernels).
-// The one-block tail of round 3 kept its level arrays in global memory and was slower; here
+// Two earlier forms of a fused tail lost their A/B and are in the history at cb85e44: round 3's
+// one block over all small levels with the level arrays in global memory (k_mg_tail: 137.6-180 us
+// per PCG iteration against 133.5-133.8), and round 5's persistent multi-block launch with
+// spin-wait grid barriers (k_mg_ptail: 55 us for the 7 stages the level kernels run in 43).  Here
 // f, x, r and the coarse vectors sit in ~94 KB of LDS, each cell's B and D^-1 in registers, and
 // the stages are separated by workgroup barriers only.  Every cell's arithmetic is the level
 // kernels' (k_mg_down2, k_mg_coarse, k_mg_up2) in their order: the same preconditioner bit for
@@ -1922,14 +1499,9 @@ struct foto_gn_plan {
            *r = nullptr, *z = nullptr, *p0 = nullptr, *p1 = nullptr;
     double *rr_part = nullptr, *pq_part = nullptr, *rz_part[2] = {nullptr, nullptr};
     double *r2 = nullptr, *q = nullptr, *rr_part2 = nullptr;   // the folded update (fold)
-    bool recomp = true;              // level-0 legs form B, D^-1 from fx, fy, f2 (FOTO_GN_RECOMP=0: load them)
-    bool exact_tail = true;          // launch the predicted count exactly (FOTO_GN_EXACT=0: whole graphs)
-    bool setup_fuse = true;          // B and block inverses per level in one pass (FOTO_GN_SETUP_FUSE=0: not)
-    bool fold = true;                // k_gnp_upd folded into the level-0 down leg (FOTO_GN_FOLD=0: not)
-    size_t pt_l0 = 0;                // first level of the persistent small-level launch (0: none; FOTO_MG_PTAIL=1: on)
+    Tuning tn;                       // the environment's knobs as foto_gn_plan_create found them
+    bool fold = true;                // k_gnp_upd folded into the level-0 down leg (tn.gn_fold, more than one level)
     bool lt = false;                 // the last level + coarsest in one LDS-resident block (k_mg_ltail)
-    int graph_its = 4;               // PCG iterations per graph replay (FOTO_GN_GRAPH, even)
-    unsigned* pt_counter = nullptr;  // its grid-barrier arrivals (zeroed per solve)
     int nb_pix = 0, nb_rz = 0;
     CGScal* dS = nullptr;
     CGScal* hS = nullptr;
@@ -1950,7 +1522,6 @@ struct foto_gn_plan {
     int last_its = 0;
     StreamLink link;                 // foto_gn_plan_solve_dev: the caller's stream <-> s
     double last[4] = {0, 0, 0, 0};   // ms setup+upload, ms PCG, iterations, iterations launched
-    bool tail = false;               // small levels in one block (k_mg_tail, FOTO_MG_TAIL=1; measured slower)
 
     MGLev desc(size_t l) const {
         const Lev& L = lev[l];
@@ -1981,10 +1552,10 @@ static int mg_coarse_threads(const foto_gn_plan::Lev& L) {
 }
 
 // z = V(r) and the partials of r.z -> rz_out
-// level 0's legs: B and D^-1 formed from the GN coefficients (P->recomp) or loaded
+// level 0's legs: B and D^-1 formed from the GN coefficients (tn.gn_recomp) or loaded
 static void mg_down0(foto_gn_plan* P, int wc, int hc, double* x, double* fc, const MGUpd& upd) {
     const auto& L = P->lev[0];
-    if (P->recomp)
+    if (P->tn.gn_recomp)
         k_mg_down2<true, true><<<mg_tiles(L.w, L.h), NT, 0, P->s>>>(P->desc(0), wc, hc, P->dS, nullptr, x, fc, upd);
     else
         k_mg_down2<true, false><<<mg_tiles(L.w, L.h), NT, 0, P->s>>>(P->desc(0), wc, hc, P->dS, nullptr, x, fc, upd);
@@ -1993,13 +1564,16 @@ static void mg_down0(foto_gn_plan* P, int wc, int hc, double* x, double* fc, con
 static void mg_up0(foto_gn_plan* P, int wc, int hc, const double* e, const double* r, const double* x, double* z,
                    double* rz_out) {
     const auto& L = P->lev[0];
-    if (P->recomp)
+    if (P->tn.gn_recomp)
         k_mg_up2<true, true><<<mg_tiles(L.w, L.h), NT, 0, P->s>>>(P->desc(0), wc, hc, P->dS, e, r, x, z, rz_out,
                                                                  MGCoef{P->fx, P->fy, P->d2});
     else
         k_mg_up2<true, false><<<mg_tiles(L.w, L.h), NT, 0, P->s>>>(P->desc(0), wc, hc, P->dS, e, r, x, z, rz_out);
 }
 
+// Down legs of levels 0 .. b - 1, the bottom step, up legs b - 1 .. 0.  The bottom step is
+// k_mg_coarse on the coarsest level c (b = c), or with P->lt k_mg_ltail on levels c - 1 and c
+// in one block (b = c - 1); either leaves the correction e on level b.
 static int gn_vcycle(foto_gn_plan* P, const double* r, double* z, double* rz_out, const MGUpd* upd = nullptr) {
     hipStream_t s = P->s;
     const size_t nl = P->lev.size();
@@ -2008,47 +1582,9 @@ static int gn_vcycle(foto_gn_plan* P, const double* r, double* z, double* rz_out
         FOTO_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    // the tail: the first level l0 >= 1 from which every level has at most MG_TAIL_CELLS cells
-    size_t l0 = nl;
-    if (P->tail) {
-        for (size_t l = 1; l < nl; ++l)
-            if ((int64_t)P->lev[l].w * P->lev[l].h <= MG_TAIL_CELLS && nl - l <= (size_t)MG_TAIL_MAX) { l0 = l; break; }
-    }
-    if (P->pt_l0 > 0) l0 = P->pt_l0;   // (the persistent launch replaces the one-block tail)
-    if (P->lt) {   // level c - 1 and the coarsest in one block: the level kernels above and below it
-        const size_t c = nl - 1;
-        for (size_t l = 0; l + 1 < c; ++l) {
-            const auto& L = P->lev[l];
-            const auto& C = P->lev[l + 1];
-            if (l == 0 && upd)
-                mg_down0(P, C.w, C.h, L.x, C.f, *upd);
-            else
-                k_mg_down2<false><<<mg_tiles(L.w, L.h), NT, 0, s>>>(P->desc(l), C.w, C.h, P->dS, l == 0 ? r : L.f, L.x,
-                                                                   C.f, MGUpd{});
-            FOTO_HIP_CHECK(hipGetLastError());
-        }
-        const auto& L = P->lev[c - 1];
-        const auto& C = P->lev[c];
-        k_mg_ltail<<<1, MG_LT_NTH, mg_lt_lds(L.w * L.h, C.w * C.h) * sizeof(double), s>>>(P->desc(c - 1), P->desc(c),
-                                                                                          P->dS, L.f, L.y);
-        FOTO_HIP_CHECK(hipGetLastError());
-        const double* e = L.y;
-        for (size_t l = c - 1; l-- > 0;) {
-            const auto& Lu = P->lev[l];
-            const auto& Cu = P->lev[l + 1];
-            if (l == 0) {
-                mg_up0(P, Cu.w, Cu.h, e, r, Lu.x, z, rz_out);
-            } else {
-                k_mg_up2<false><<<mg_tiles(Lu.w, Lu.h), NT, 0, s>>>(P->desc(l), Cu.w, Cu.h, P->dS, e, Lu.f, Lu.x, Lu.y,
-                                                                    nullptr);
-                e = Lu.y;
-            }
-            FOTO_HIP_CHECK(hipGetLastError());
-        }
-        return 0;
-    }
-    const size_t ldown = std::min(l0, nl - 1);
-    for (size_t l = 0; l < ldown; ++l) {
+    const size_t c = nl - 1;
+    const size_t b = P->lt ? c - 1 : c;
+    for (size_t l = 0; l < b; ++l) {
         const auto& L = P->lev[l];
         const auto& C = P->lev[l + 1];
         if (l == 0 && upd)
@@ -2058,44 +1594,20 @@ static int gn_vcycle(foto_gn_plan* P, const double* r, double* z, double* rz_out
                                                                C.f, MGUpd{});
         FOTO_HIP_CHECK(hipGetLastError());
     }
-    const size_t c = nl - 1;
-    const double* e = nullptr;
-    size_t lup = nl - 1;   // up legs below this level run as level kernels
-    if (P->pt_l0 > 0) {
-        MGPTail T{};
-        T.nl = (int)(nl - l0);
-        for (size_t l = l0; l < nl; ++l) {
-            T.L[l - l0] = P->desc(l);
-            T.f[l - l0] = P->lev[l].f;
-            T.x[l - l0] = P->lev[l].x;
-            T.y[l - l0] = P->lev[l].y;
-        }
-        T.counter = P->pt_counter;
-        T.syncs = 2 * (T.nl - 1);   // a barrier after each down leg, the coarsest solve, each up leg but the last
-        k_mg_ptail<<<mg_tiles(P->lev[l0].w, P->lev[l0].h), NT, 0, s>>>(T, P->dS);
-        FOTO_HIP_CHECK(hipGetLastError());
-        e = P->lev[l0].y;
-        lup = l0;
-    } else if (l0 < nl) {
-        MGTail T{};
-        T.nl = (int)(nl - l0);
-        for (size_t l = l0; l < nl; ++l) {
-            T.L[l - l0] = P->desc(l);
-            T.f[l - l0] = P->lev[l].f;
-            T.x[l - l0] = P->lev[l].x;
-            T.y[l - l0] = P->lev[l].y;
-        }
-        k_mg_tail<<<1, 1024, 0, s>>>(T, P->dS);
-        FOTO_HIP_CHECK(hipGetLastError());
-        e = (l0 == c) ? P->lev[c].x : P->lev[l0].y;
-        lup = l0;
+    const double* e;
+    if (P->lt) {
+        const auto& L = P->lev[b];
+        const auto& C = P->lev[c];
+        k_mg_ltail<<<1, MG_LT_NTH, mg_lt_lds(L.w * L.h, C.w * C.h) * sizeof(double), s>>>(P->desc(b), P->desc(c), P->dS,
+                                                                                          L.f, L.y);
+        e = L.y;
     } else {
         k_mg_coarse<false><<<1, mg_coarse_threads(P->lev[c]), 0, s>>>(P->desc(c), P->dS, P->lev[c].f, P->lev[c].x,
                                                                       nullptr);
-        FOTO_HIP_CHECK(hipGetLastError());
         e = P->lev[c].x;
     }
-    for (size_t l = lup; l-- > 0;) {
+    FOTO_HIP_CHECK(hipGetLastError());
+    for (size_t l = b; l-- > 0;) {
         const auto& L = P->lev[l];
         const auto& C = P->lev[l + 1];
         if (l == 0) {
@@ -2147,6 +1659,9 @@ struct GnTrace {
     }
 };
 
+// PCG iterations per graph replay (even: the parities alternate)
+constexpr int GN_GRAPH_ITS = 4;
+
 static int gn_plan_init(foto_gn_plan* P) {
     const int w = P->w, h = P->h;
     const size_t n = (size_t)w * h;
@@ -2160,10 +1675,6 @@ static int gn_plan_init(foto_gn_plan* P) {
     FOTO_HIP_CHECK(hipHostMalloc((void**)&P->hS, sizeof(CGScal)));
     tr.mark("pinned scalars");   // (the pinned staging is made during the first solve: gn_staging)
     P->nb_pix = flat_blocks((int64_t)n);
-    {
-        const char* e = getenv("FOTO_MG_TAIL");
-        P->tail = e && atoi(e) != 0;
-    }
     // level geometry
     int lw = w, lh = h;
     double sc = 1.0;
@@ -2180,16 +1691,7 @@ static int gn_plan_init(foto_gn_plan* P) {
         sc *= 0.25;
     }
     P->nb_rz = P->lev.size() == 1 ? 1 : mg_tiles(w, h);
-    {
-        const char* sf = getenv("FOTO_GN_SETUP_FUSE");
-        P->setup_fuse = !(sf && atoi(sf) == 0);
-        const char* rc = getenv("FOTO_GN_RECOMP");
-        P->recomp = !(rc && atoi(rc) == 0);
-        const char* ex = getenv("FOTO_GN_EXACT");
-        P->exact_tail = !(ex && atoi(ex) == 0);
-        const char* e = getenv("FOTO_GN_FOLD");
-        P->fold = P->lev.size() > 1 && !(e && atoi(e) == 0);   // (one level: no down leg to fold into)
-    }
+    P->fold = P->lev.size() > 1 && P->tn.gn_fold;   // (one level: no down leg to fold into)
     const size_t nscal = sizeof(CGScal) / sizeof(double) + 1;
     const size_t nfold = P->fold ? 6 * n + (size_t)P->nb_rz : 0;
     const size_t total = 23 * n + lev_total + 2 * (size_t)P->nb_pix + 2 * (size_t)P->nb_rz + nfold + nscal + 64;
@@ -2213,22 +1715,9 @@ static int gn_plan_init(foto_gn_plan* P) {
         P->rr_part2 = q; q += P->nb_rz;
     }
     P->dS = (CGScal*)q;
-    q += nscal;
-    P->pt_counter = (unsigned*)q;   // (within total's slack)
-    {   // the persistent small-level launch: from the first level of at most MG_PT_TILES tiles
-        const char* e = getenv("FOTO_MG_PTAIL");
-        const size_t nl = P->lev.size();
-        if (e && atoi(e) != 0 && !P->tail)   // (opt-in: measured slower, see k_mg_ptail)
-            for (size_t l = 1; l + 1 < nl; ++l)
-                if (mg_tiles(P->lev[l].w, P->lev[l].h) <= MG_PT_TILES) {
-                    if (nl - l <= (size_t)MG_PT_MAX) P->pt_l0 = l;
-                    break;
-                }
-    }
     {   // the last level above the coarsest and the coarsest in LDS (FOTO_MG_LTAIL=0: level kernels)
-        const char* e = getenv("FOTO_MG_LTAIL");
         const size_t nl = P->lev.size();
-        if (!(e && atoi(e) == 0) && !P->tail && P->pt_l0 == 0 && nl >= 3 &&
+        if (P->tn.mg_ltail && nl >= 3 &&
             (int64_t)P->lev[nl - 2].w * P->lev[nl - 2].h <= MG_LT_CELLS &&
             (int64_t)P->lev[nl - 1].w * P->lev[nl - 1].h <= MG_LT_NTH) {
             P->lt = true;
@@ -2238,18 +1727,13 @@ static int gn_plan_init(foto_gn_plan* P) {
                                                (int)bytes));
         }
     }
-    // P->graph_its iterations (p0 -> p1 -> p0 ...) captured once; the kernels read the iteration
+    // GN_GRAPH_ITS iterations (p0 -> p1 -> p0 ...) captured once; the kernels read the iteration
     // index from the device, so the graph is replayed unchanged.  Round 5: 4 instead of 2 -- a
     // replay boundary cost ~17 us of idle GPU (profiles/r05_gn_trace.txt: 8.4 us per iteration
     // before k_gnp_dir), and a reused plan launches its predicted count in one go either way
-    {
-        const char* e = getenv("FOTO_GN_GRAPH");
-        const int g = e ? atoi(e) : 4;
-        P->graph_its = (g >= 2 && g <= 16 && g % 2 == 0) ? g : 4;
-    }
     FOTO_HIP_CHECK(hipStreamBeginCapture(P->s, hipStreamCaptureModeThreadLocal));
     int c2 = 0;
-    for (int it = 0; it < P->graph_its && c2 >= 0; ++it) c2 = gn_iteration(P, it & 1);
+    for (int it = 0; it < GN_GRAPH_ITS && c2 >= 0; ++it) c2 = gn_iteration(P, it & 1);
     const hipError_t ec = hipStreamEndCapture(P->s, &P->graph);
     FOTO_TRY(c2);
     FOTO_HIP_CHECK(ec);
@@ -2268,8 +1752,7 @@ static int gn_staging(foto_gn_plan* P) {
     FOTO_HIP_CHECK(hipHostMalloc((void**)&P->hbuf, 5 * n * sizeof(double)));
     memset(P->hbuf, 0, 5 * n * sizeof(double));   // first touch on the host, not by the device
     FOTO_HIP_CHECK(hipHostGetDevicePointer((void**)&P->hbuf_dev, P->hbuf, 0));
-    const char* e = getenv("FOTO_GN_HOST_THREADS");
-    const int workers = e ? std::max(0, std::min(16, atoi(e))) : 4;
+    const int workers = P->tn.gn_host_threads;
     if (workers > 0) P->pool = std::make_unique<HostPool>(workers);
     return 0;
 }
@@ -2307,12 +1790,11 @@ static int gn_plan_solve(foto_gn_plan* P, const double* f1, const double* f2, do
     }
     tr.mark("solve: upload staged");
     FOTO_HIP_CHECK(hipMemsetAsync(P->dS, 0, sizeof(CGScal), s));
-    if (P->pt_l0 > 0) FOTO_HIP_CHECK(hipMemsetAsync(P->pt_counter, 0, sizeof(unsigned), s));
     FOTO_HIP_CHECK(hipMemsetAsync(P->x, 0, 3 * n * sizeof(double), s));
     FOTO_HIP_CHECK(launch_gn_coeffs(w, h, P->d1, P->d2, P->fx, P->fy, P->ft, s));
     FOTO_HIP_CHECK(launch_gn_rhs(w, h, P->fx, P->fy, P->d2, P->ft, P->b, s));
     // image-dependent multigrid coefficients
-    if (P->setup_fuse) {
+    if (P->tn.gn_setup_fuse) {
         k_mg_b0_d<<<flat_blocks(n), NT, 0, s>>>(P->desc(0), P->fx, P->fy, P->d2, P->lev[0].B, P->lev[0].Dinv);
         FOTO_HIP_CHECK(hipGetLastError());
         for (size_t l = 1; l < P->lev.size(); ++l) {
@@ -2341,19 +1823,19 @@ static int gn_plan_solve(foto_gn_plan* P, const double* f1, const double* f2, do
     FOTO_TRY(gn_vcycle(P, P->r, P->z, P->rz_part[0]));
     FOTO_HIP_CHECK(hipEventRecord(P->ev[1], s));
     tr.mark("solve: setup enqueued");
-    // replay the graph (G = graph_its iterations); the first wait comes after the previous solve's
+    // replay the graph (G = GN_GRAPH_ITS iterations); the first wait comes after the previous solve's
     // count: the top-of-iteration test that ends a solve of `its` iterations runs in iteration
     // its, so its + 1 iterations are launched (rounded up to whole graphs)
     int k = 0;
     bool done = false;
     const int maxiter = P->maxiter;
-    const int G = P->graph_its;
+    constexpr int G = GN_GRAPH_ITS;
     const int first = P->last_its > 0 ? ((P->last_its + 1 + G - 1) / G) * G : 16;
     // (round 6: a reused plan launches exactly its predicted its + 1, the remainder past whole
     // graphs as single iterations -- a graph's surplus iterations each cost ~25 us of early exits)
     const int first_exact = P->last_its > 0 ? P->last_its + 1 : 16;
     while (k < maxiter) {
-        const int chunk = std::min(k == 0 ? (P->exact_tail ? first_exact : first) : G, maxiter - k);
+        const int chunk = std::min(k == 0 ? (P->tn.gn_exact ? first_exact : first) : G, maxiter - k);
         int j = 0;
         if ((k & 1) && chunk > 0) {   // (after an under-predicted exact count: the graph starts on parity 0)
             FOTO_TRY(gn_iteration(P, 1));
@@ -2369,10 +1851,6 @@ static int gn_plan_solve(foto_gn_plan* P, const double* f1, const double* f2, do
     }
     FOTO_HIP_CHECK(hipEventRecord(P->ev[2], s));
     tr.mark("solve: PCG done");
-    if (P->hS->pad[1]) {   // (k_mg_ptail: a grid barrier gave up -- blocks not co-resident)
-        set_error("GN: the persistent small-level launch could not synchronise its blocks (FOTO_MG_PTAIL=0 avoids it)");
-        return FOTO_ERR_HIP;
-    }
     // the solution straight into the mapped pinned staging by a kernel: the first large
     // device-to-host hipMemcpy of a process took 8.5-14.8 ms at 640x480 (0.15-0.4 ms later)
     if (dv) {
@@ -2421,6 +1899,7 @@ int foto_gn_plan_create(int w, int h, double alpha, double lambda_, double rtol,
     if (maxiter < 0) { set_error("maxiter < 0"); return FOTO_ERR_ARG; }
     auto P = std::make_unique<foto_gn_plan>();
     P->w = w; P->h = h; P->alpha = alpha; P->lam = lambda_; P->rtol = rtol; P->maxiter = maxiter;
+    P->tn = tuning_from_env();   // read here, once: fixed for the plan's life
     FOTO_TRY(gn_plan_init(P.get()));
     *out = P.release();
     return 0;

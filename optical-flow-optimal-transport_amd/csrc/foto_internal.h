@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/foto.h"
+#include "foto_tuning.h"
 
 namespace foto {
 
@@ -103,14 +104,9 @@ struct KTimer {
         if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
         // timing only, no system-scope fence: a fenced record writes the L2's dirty lines back
         // before the next launch, which the untimed loop never does -- the launch after it then
-        // ran on a clean L2 (k_prox_rhs 171 us against 179.5 in the loop; FOTO_KT_FENCE=1: fenced)
-        static const bool fence = [] {
-            const char* f = getenv("FOTO_KT_FENCE");
-            return f && atoi(f) == 1;
-        }();
+        // ran on a clean L2 (k_prox_rhs 171 us against 179.5 in the loop)
         hipEvent_t e;
-        if (hipEventCreateWithFlags(&e, fence ? hipEventDefault : hipEventDisableSystemFence) != hipSuccess)
-            return nullptr;
+        if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) return nullptr;
         return e;
     }
     // returns the start event to be paired by stop()
@@ -234,16 +230,17 @@ hipError_t launch_prox(const Geo& g, const double* phi, double* mut, double* mux
                        double* qx, double* qy, double r, RedBuf rb, double* gath, int rank, hipStream_t s,
                        const int* guard = nullptr);
 // k_prox fused with the next iteration's RHS (mu -> nu, F, this rank's crit num/den ->
-// gath_crit[0..1], F.F -> gath_rr[0] when non-null); needs rb.cap >= 3 * prox_rhs_blocks(g).
+// gath_crit[0..1], F.F -> gath_rr[0] when non-null); needs rb.cap >= 3 * prox_rhs_blocks(g, tch).
+// tch: planes per chunk (Tuning::pr_tch).
 // Sharded (g.t0 > 0 or g.t0 + g.nloc < g.Nt), either: defer_lo / defer_hi = 0 -- stepB is
 // recomputed on the neighbours' boundary planes: phi needs two valid halo planes on each side
 // and mu one; or defer_lo / defer_hi = 1 on the sides that have a neighbour -- phi needs one
 // halo plane, F of that edge plane is left to launch_rhs_edge after w_t's halo exchange
 // (wt_out: a halo-padded field, planes 0, 1, nloc - 2, nloc - 1 written; edge: 2 x 4 planes).
-int prox_rhs_blocks(const Geo& g);
+int prox_rhs_blocks(const Geo& g, int tch);
 hipError_t launch_prox_rhs(const Geo& g, const double* phi, const double* mut, const double* mux, const double* muy,
                            double* nut, double* nux, double* nuy, const double* rho0, const double* rhoT, double r,
-                           double* F, RedBuf rb, double* gath_crit, double* gath_rr, hipStream_t s,
+                           double* F, RedBuf rb, double* gath_crit, double* gath_rr, int tch, hipStream_t s,
                            const int* guard = nullptr, int defer_lo = 0, int defer_hi = 0, double* wt_out = nullptr,
                            double* edge = nullptr, double* hcrit = nullptr, int wt_pre = 0);
 // w_t = mu'_t - r q_t of the deferred edge planes (0 if defer_lo, nloc - 1 if defer_hi) into

@@ -467,12 +467,7 @@ __global__ __launch_bounds__(RHS_NT) void k_rhs(Geo g, const double* __restrict_
 hipError_t launch_rhs(const Geo& g, const double* mut, const double* mux, const double* muy, const double* qt,
                       const double* qx, const double* qy, const double* rho0, const double* rhoT, double r,
                       double* F, RedBuf rb, double* gath, int rank, hipStream_t s) {
-    // planes per chunk (FOTO_RHS_TCH; default 8: four chunks at Nt = 32)
-    static const int tch = [] {
-        const char* e = getenv("FOTO_RHS_TCH");
-        const int v = e ? atoi(e) : 8;
-        return v > 0 ? v : 8;
-    }();
+    constexpr int tch = 8;   // planes per chunk: four chunks at Nt = 32
     const int nch = (g.nloc + tch - 1) / tch;
     const int nb = ((g.Nx + TX - 1) / TX) * ((g.Ny + RHS_TY - 1) / RHS_TY) * nch;
     k_rhs<<<nb, RHS_NT, 0, s>>>(g, mut, mux, muy, qt, qx, qy, rho0, rhoT, r, F, rb, gath, rank, tch);
@@ -995,34 +990,32 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(PR_WPE)))
     }
 }
 
-// planes per chunk (FOTO_PR_TCH, read per call for A/B tests).  Measured at 640x480x32
-// (MI355X, 2 blocks of 512 threads per CU): 4 / 8 / 16 / 32 planes -> 232 / 195 / 173 / 193 us
-// (more chunks: more recomputed boundary planes; fewer: a partly filled last round of blocks).
-int prox_rhs_tch(const Geo& g) {
-    const char* e = getenv("FOTO_PR_TCH");
-    const int v = e ? atoi(e) : 16;
-    return std::min(v > 0 ? v : 16, g.nloc);
-}
+// planes per chunk: the configured count (Tuning::pr_tch, FOTO_PR_TCH; default 16), at most the
+// slab.  Measured at 640x480x32 (MI355X, 2 blocks of 512 threads per CU): 4 / 8 / 16 / 32 planes
+// -> 232 / 195 / 173 / 193 us (more chunks: more recomputed boundary planes; fewer: a partly
+// filled last round of blocks).
+static int prox_rhs_tch(const Geo& g, int tch) { return std::min(tch, g.nloc); }
 
-int prox_rhs_blocks(const Geo& g) {
-    const int tch = prox_rhs_tch(g);
+int prox_rhs_blocks(const Geo& g, int tch) {
+    tch = prox_rhs_tch(g, tch);
     return ((g.Nx + PR_X - 1) / PR_X) * ((g.Ny + PR_Y - 1) / PR_Y) * ((g.nloc + tch - 1) / tch);
 }
 
 hipError_t launch_prox_rhs(const Geo& g, const double* phi, const double* mut, const double* mux, const double* muy,
                            double* nut, double* nux, double* nuy, const double* rho0, const double* rhoT, double r,
-                           double* F, RedBuf rb, double* gath_crit, double* gath_rr, hipStream_t s, const int* guard,
-                           int defer_lo, int defer_hi, double* wt_out, double* edge, double* hcrit, int wt_pre) {
-    const int nb = prox_rhs_blocks(g);
+                           double* F, RedBuf rb, double* gath_crit, double* gath_rr, int tch, hipStream_t s,
+                           const int* guard, int defer_lo, int defer_hi, double* wt_out, double* edge, double* hcrit,
+                           int wt_pre) {
+    const int nb = prox_rhs_blocks(g, tch);
     if (rb.cap < 3 * nb) return hipErrorInvalidValue;
     if ((defer_lo || defer_hi) && (!wt_out || !edge)) return hipErrorInvalidValue;
     if (defer_lo || defer_hi)
         k_prox_rhs<true><<<nb, PR_NT, 0, s>>>(g, phi, mut, mux, muy, nut, nux, nuy, rho0, rhoT, r, 1.0 / r, F, rb,
-                                              gath_crit, gath_rr, guard, prox_rhs_tch(g), defer_lo, defer_hi, wt_out, edge,
+                                              gath_crit, gath_rr, guard, prox_rhs_tch(g, tch), defer_lo, defer_hi, wt_out, edge,
                                               hcrit, wt_pre);
     else
         k_prox_rhs<false><<<nb, PR_NT, 0, s>>>(g, phi, mut, mux, muy, nut, nux, nuy, rho0, rhoT, r, 1.0 / r, F, rb,
-                                               gath_crit, gath_rr, guard, prox_rhs_tch(g), 0, 0, nullptr, nullptr,
+                                               gath_crit, gath_rr, guard, prox_rhs_tch(g, tch), 0, 0, nullptr, nullptr,
                                                hcrit, 0);
     return hipGetLastError();
 }

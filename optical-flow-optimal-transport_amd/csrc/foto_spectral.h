@@ -7,7 +7,8 @@ namespace foto {
 struct SpectralPlan {
     // rank / world: the shard's place in the time-slab decomposition (world > 1 needs
     // sstep = 2; the spectral box of rank g is rows [y0, y0 + nyl) of every kt plane).
-    int init(const Geo& g, int rank, int world, double r, double eps, int sstep, hipStream_t s);
+    // tn: the knobs the owning context read when it was built; the plan keeps its copy.
+    int init(const Geo& g, int rank, int world, double r, double eps, int sstep, const Tuning& tn, hipStream_t s);
     // single shard: b (physical, clobbered) -> x (physical); scipy stopping rule.
     int solve(double* b, double* x, double rtol, int maxiter, int predicted, int* iters, int* info, KTimer* kt,
               hipStream_t s);

@@ -1565,7 +1565,6 @@ struct SpecImpl {
     int nb_ring = 0;
     double* Cth = nullptr;        // t-axis DCT-II even | odd halves (column kernels)
     bool tcol = false;            // single shard, s-step, Nt in FOTO_TCOL_SIZES
-    bool xt = false;              // single shard, Gauss CG: x and t DCTs in one pass (k_dct_xt_fwd / k_dct_tx_inv)
     int tcol_nb = 0;              // column kernels' blocks
     int last_passes = 0;          // passes of the previous s-step solve (first chunk size)
     // deferred solves in flight (solve_deferred -> finish), oldest first: one for the s-step
@@ -1578,6 +1577,7 @@ struct SpecImpl {
     Pend pq[2];
     int npend = 0;
     int sstep = 1;
+    Tuning tn;                    // the knobs as the owning context read them (init's argument)
     std::vector<void*> allocs;
     int nblocks = 0;
     double c0 = 0, c1 = 1;
@@ -1589,13 +1589,10 @@ struct SpecImpl {
     GqState* dgq2[2] = {nullptr, nullptr};   // their device addresses (coherent host memory)
     GqNodes* gqn = nullptr;
     double* gq_hist = nullptr;    // world histograms (slot rank is this box's)
-    bool gq_nodes_wave = true;    // k_gq_nodes_w (FOTO_GQ_NODES=thread: k_gq_nodes, the round-4 form)
-    bool gq_tfuse = false;        // x^ inside the inverse t-DCT (k_dct_t_inv_gq; FOTO_GQ_TFUSE)
     double* gq_tab = nullptr;
     GqBins* gq_bins = nullptr;    // bin edges of the measure and the solution table
     GqQCos* gq_qcos = nullptr;    // the solution table's transform constants
     GqPub* gq_pub = nullptr;      // k_gq_cgtab's (alpha, beta) slots
-    bool gq_cgtab = true;         // FOTO_GQ_CGTAB=0: k_gq_cg, then k_gq_qtab
     // bin-ordered histogram (k_gq_hist_perm): the box's voxels grouped by bin, chunked
     unsigned* gq_permv = nullptr;
     GqChunk* gq_chunks = nullptr;
@@ -1637,7 +1634,8 @@ static int reset_s2(SpecImpl* P, hipStream_t s);
 
 static int gq_build_perm(SpecImpl* P, hipStream_t s);
 
-int SpectralPlan::init(const Geo& g, int rank, int world, double r, double eps, int sstep, hipStream_t s) {
+int SpectralPlan::init(const Geo& g, int rank, int world, double r, double eps, int sstep, const Tuning& tn,
+                       hipStream_t s) {
     // cg_mode 3: the Gauss-compressed CG, with the s-step machinery kept for the (rare) redo
     const bool gauss = (sstep == 3);
     if (gauss) sstep = 2;
@@ -1660,6 +1658,7 @@ int SpectralPlan::init(const Geo& g, int rank, int world, double r, double eps, 
     auto* P = new SpecImpl();
     impl = P;
     P->sstep = sstep;
+    P->tn = tn;
     P->g = g;
     P->rank = rank;
     P->world = world;
@@ -1682,7 +1681,7 @@ int SpectralPlan::init(const Geo& g, int rank, int world, double r, double eps, 
     // 2 x 3.3 MB of host cosines and blocking copies per 640-axis saved at context creation
     auto up = [&](int n, double** Cd, double** CTd, double** mud) -> int {
         int m1, m2;
-        const bool fft = dct_fft_enabled() && n >= 64 && fft_factors(n, &m1, &m2);
+        const bool fft = tn.dct_fft && n >= 64 && fft_factors(n, &m1, &m2);
         if (fft) dct_eigen(n, mu);
         else dct_matrix(n, C, CT, mu);
         void* p;
@@ -1704,7 +1703,7 @@ int SpectralPlan::init(const Geo& g, int rank, int world, double r, double eps, 
     const double mt_max = mu.back();
     auto upf = [&](int n, double** Fd) -> int {
         int m1, m2;
-        if (!fft_factors(n, &m1, &m2)) return 0;
+        if (!tn.dct_fft || !fft_factors(n, &m1, &m2)) return 0;   // (no table: dct_pass takes the GEMM kernels)
         const std::vector<double> t = fft_table(n);
         void* p;
         FOTO_TRY(P->alloc(t.size() * 8, &p));
@@ -1732,15 +1731,12 @@ int SpectralPlan::init(const Geo& g, int rank, int world, double r, double eps, 
         P->nblocks2 = std::min(ntiles2, std::max(1, per_cu) * cus);
         // ring-fed pass (k_spec_s2r): one 1024-thread block per CU (its LDS ring), at most one
         // block per 16 wave tiles; FOTO_RING=0 selects the register-fed pass (A/B runs)
-        const char* er = getenv("FOTO_RING");
-        P->ring = ring_ok(P->tab()) && !(er && atoi(er) == 0);
+        P->ring = ring_ok(P->tab()) && tn.ring;
         const int nwt = ((g.Nx + 127) / 128) * rows;
         P->nb_ring = std::max(1, std::min({P->nblocks2, cus, (nwt + RING_NW - 1) / RING_NW}));
     }
-    {
-        const char* e = getenv("FOTO_TCOL");   // 0: t axis by dct_pass + separate INIT / xhat passes (A/B runs)
-        P->tcol = sstep == 2 && tcol_supported(g.Nt) && !(e && atoi(e) == 0);
-    }
+    // FOTO_TCOL=0: t axis by dct_pass + separate INIT / xhat passes (A/B runs)
+    P->tcol = sstep == 2 && tcol_supported(g.Nt) && tn.tcol;
     if (P->tcol) {
         const int H = g.Nt / 2;
         dct_matrix(g.Nt, C, CT, mu);
@@ -1771,15 +1767,6 @@ int SpectralPlan::init(const Geo& g, int rank, int world, double r, double eps, 
     // the Gauss-compressed CG needs the bin-ordered voxel list; boxes its packing does not
     // cover run the s-step CG (decided on the whole grid, so every rank agrees)
     P->gauss = gauss && gq_perm_ok(g.Nx, g.Nt * g.Ny);
-    {   // (x, t) / (t, x) in one pass: single shard, the column kernels' t sizes, an FFT x plan.
-        // Opt-in (FOTO_DCT_XT=1): correct (the whole GPU suite passes with it) but measured 2.2x
-        // slower than the two passes it replaces -- 151 / 165 us against 69 / 72 us at the bench
-        // grid (profiles/r05_xt_ab.txt): a row slab's t-sums (164 KB) pin one 512-thread block
-        // per CU, whose load / FFT / accumulate phases then run without overlap.
-        const char* e = getenv("FOTO_DCT_XT");
-        P->xt = P->gauss && P->tcol && world == 1 && P->Fx && dct_fft_enabled() && xt_supported(g.Nx, g.Nt) &&
-                (e && atoi(e) == 1);
-    }
     if (P->gauss) {
         FOTO_TRY(P->alloc(sizeof(GqState), &b)); P->gq = (GqState*)b;
         FOTO_HIP_CHECK(hipMemsetAsync(P->gq, 0, sizeof(GqState), s));
@@ -1790,10 +1777,6 @@ int SpectralPlan::init(const Geo& g, int rank, int world, double r, double eps, 
         }
         FOTO_TRY(P->alloc(sizeof(GqNodes), &b)); P->gqn = (GqNodes*)b;
         FOTO_TRY(P->alloc(sizeof(double) * GQ_HIST * world, &b)); P->gq_hist = (double*)b;
-        const char* gn = getenv("FOTO_GQ_NODES");
-        P->gq_nodes_wave = !(gn && std::strcmp(gn, "thread") == 0);
-        const char* tf = getenv("FOTO_GQ_TFUSE");
-        P->gq_tfuse = tf && atoi(tf) != 0;
         FOTO_TRY(P->alloc(GQ_TAB_BYTES, &b)); P->gq_tab = (double*)b;
         // k_gq_xhat holds the whole table (128 KB) in dynamic LDS, beside its 10 KB bin tables
         FOTO_HIP_CHECK(hipFuncSetAttribute((const void*)k_gq_xhat, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1804,8 +1787,6 @@ int SpectralPlan::init(const Geo& g, int rank, int world, double r, double eps, 
         k_gq_qcos<<<1, 256, 0, s>>>(P->gq_qcos);
         FOTO_TRY(P->alloc(sizeof(GqPub), &b)); P->gq_pub = (GqPub*)b;
         FOTO_TRY(gq_pub_clear(P, s));
-        const char* ct = getenv("FOTO_GQ_CGTAB");
-        P->gq_cgtab = !(ct && atoi(ct) == 0);
         FOTO_HIP_CHECK(hipGetLastError());
         FOTO_TRY(P->alloc(sizeof(GqExact), &b)); P->gq_exact = (GqExact*)b;
         FOTO_TRY(gq_build_perm(P, s));
@@ -1864,13 +1845,12 @@ static int gq_perm_lists(SpecImpl* P, const SpecTab& T, unsigned* perm, double* 
 // of all bins over the same rows read the same lines at about the same time -- from the same L2
 // only if they run on the same XCD.  Workgroups go round-robin to the 8 XCDs (block k to XCD
 // k % 8) and a block's 4 waves take slots 4k .. 4k + 3: slot lists are filled so that XCD x
-// gets the chunks whose first row lies in the x-th eighth of the rows (FOTO_GQ_XCD=0: bin order).
+// gets the chunks whose first row lies in the x-th eighth of the rows (lists too short keep bin order).
 // The sums go to part[chunk id] either way, so the histogram is bit-identical.
 static int gq_order_chunks(SpecImpl* P, std::vector<GqChunk>& ch, int rows, hipStream_t s) {
-    const char* e = getenv("FOTO_GQ_XCD");
     const int nx = 8;
     const int n = (int)ch.size();
-    if ((e && atoi(e) == 0) || n < 4 * nx) return 0;
+    if (n < 4 * nx) return 0;
     void* b = nullptr;
     GqChunk* dch = nullptr;
     int* drow = nullptr;
@@ -1921,8 +1901,7 @@ static int gq_build_perm(SpecImpl* P, hipStream_t s) {
     // none; up to GQ_XS = 16 also takes bins of 9-16 points through the Stieltjes procedure --
     // measured less accurate (the 5-step iterate of an 8x24x20 grid 1.6e-10 from scipy's against
     // 2.3e-12; the node / weight solve loses digits on clustered points), not the default
-    const char* ex = getenv("FOTO_GQ_EXACT");
-    const int xmax = ex ? std::min(atoi(ex), GQ_XS) : GQ_M;
+    const int xmax = P->tn.gq_exact != Tuning::AUTO ? std::min(P->tn.gq_exact, GQ_XS) : GQ_M;
     const int rows = P->g.Nt * P->nyl;
     const int64_t N = (int64_t)rows * P->g.Nx;
     void* b = nullptr;
@@ -2052,10 +2031,7 @@ static int reset_s2(SpecImpl* P, hipStream_t s) {
     h.gc1 = P->c1;
     h.ic0 = P->c0;   // the first solve's INIT moments: the whole spectrum
     h.ic1 = P->c1;
-    {
-        const char* e = getenv("FOTO_SADAPT");   // 0: whole-spectrum interval for every pass (A/B runs)
-        h.flags = (e && atoi(e) == 0) ? 1 : 0;
-    }
+    h.flags = P->tn.sadapt ? 0 : 1;   // FOTO_SADAPT=0: whole-spectrum interval for every pass (A/B runs)
     *P->hS2 = h;
     FOTO_HIP_CHECK(hipMemcpyAsync(P->S2, P->hS2, sizeof(SStep), hipMemcpyHostToDevice, s));
     FOTO_HIP_CHECK(hipStreamSynchronize(s));   // hS2 is reused by polling
@@ -2114,18 +2090,15 @@ static hipError_t launch_xhat(SpecImpl* P, hipStream_t s) {
 // moments in gath for the all-gather
 // x^ = Q(lam) b^ (the Gauss-compressed CG's solution table) into a box buffer: persistent
 // 1024-thread blocks, the table in LDS.  Sized for the whole table (32 rows, 128 KB) one block
-// fits a CU; sized for the first FOTO_GQ_XQL rows (default 17: 68 KB, what K <= ~200 needs;
-// the table kernel's qn is not known when this launch is enqueued) two fit, and any rows beyond
-// are read from the global table.  (FOTO_GQ_XQL=0: the whole table, one block per CU.)
+// fits a CU; sized for the first GQ_XQL = 17 rows (68 KB, what K <= ~200 needs; the table
+// kernel's qn is not known when this launch is enqueued) two fit, and any rows beyond are read
+// from the global table.
 static hipError_t gq_xhat(SpecImpl* P, double* out, hipStream_t s) {
     const SpecTab T = P->tab();
     const int rows = P->g.Nt * P->nyl;
-    static const int xql = [] {
-        const char* e = getenv("FOTO_GQ_XQL");
-        return e ? atoi(e) : 17;
-    }();
-    const int ql = (xql > 0 && xql < GQ_QN) ? xql : GQ_QN;
-    const int per_cu = (ql < GQ_QN) ? 2 : 1;
+    constexpr int ql = GQ_XQL;
+    static_assert(ql > 0 && ql < GQ_QN, "the LDS part of the table: two blocks per CU");
+    const int per_cu = 2;
     const int nb = std::max(1, std::min(per_cu * cus_count(), (rows + GQ_XNTH / 64 - 1) / (GQ_XNTH / 64)));
     k_gq_xhat<<<nb, GQ_XNTH, (size_t)ql * GQ_QB * sizeof(double), s>>>(T, P->bh, P->gq_tab, P->gq, P->gq_bins,
                                                                        1.0 / P->c1, out, ql);
@@ -2138,28 +2111,9 @@ static hipError_t launch_tcol(SpecImpl* P, bool inv, const double* in, double* o
     const SpecTab T = P->tab();
     const int nb = P->tcol_nb;
     const bool gq = inv && P->gauss_active;
-    // one thread per column with the table in LDS: x^ = Q(lam) b^ inside the inverse t-DCT
-    bool tfuse = false;
-#define FOTO_TFUSE_NT(NN) tfuse = tfuse || P->g.Nt == NN;
-    FOTO_TCOL_SIZES(FOTO_TFUSE_NT)   // (one thread per column: Nt <= 32)
-#undef FOTO_TFUSE_NT
-    tfuse = tfuse && gq && P->gq_tfuse;
-    if (gq && !tfuse) {   // x^ -> rh, then the plain inverse below
+    if (gq) {   // x^ -> rh, then the plain inverse below
         const hipError_t e = gq_xhat(P, P->rh, s);
         if (e != hipSuccess) return e;
-    }
-    if (tfuse) {
-        const int ql = 17;   // 2 blocks of 512 per CU (<= 80 KB of LDS each); rows beyond from the global table
-        const int nbf = (int)(((int64_t)P->nyl * P->g.Nx + GQ_TFNTH - 1) / GQ_TFNTH);
-#define FOTO_TFUSE_LAUNCH(NN)                                                                                      \
-        if (P->g.Nt == NN) {                                                                                       \
-            k_dct_t_inv_gq<NN><<<nbf, GQ_TFNTH, (size_t)ql * GQ_QB * sizeof(double), s>>>(                         \
-                    T, P->Cth, P->bh, P->gq_tab, P->gq, P->gq_bins, 1.0 / P->c1, out, ql);                       \
-            return hipGetLastError();                                                                              \
-        }
-        FOTO_TCOL_SIZES(FOTO_TFUSE_LAUNCH)
-#undef FOTO_TFUSE_LAUNCH
-        return hipErrorNotSupported;
     }
 #define FOTO_TCOL_FWD(NN, K, M) K<NN, M><<<nb, TC_NTH, 0, s>>>(T, P->Cth, in, P->bh, P->S2, P->rb, rtol, maxiter, \
                                                                 P->gath, P->rank)
@@ -2202,8 +2156,8 @@ static int tcol_inverse(SpecImpl* P, double* b, double* x, double rtol, int maxi
 }
 
 // ---------------------------------------------------------------------------- Gauss-compressed CG (host)
-// one shard, wave-per-bin nodes: k_gq_nodes_w sums the chunk sums itself (no histogram pass)
-static bool gq_fused_reduce(const SpecImpl* P) { return P->gq_nodes_wave && P->world == 1; }
+// one shard: k_gq_nodes_w sums the chunk sums itself (no histogram pass)
+static bool gq_fused_reduce(const SpecImpl* P) { return P->world == 1; }
 
 // b^ -> this box's histogram (slot rank of gq_hist)
 static int gq_measure(SpecImpl* P, KTimer* kt, hipStream_t s) {
@@ -2213,7 +2167,7 @@ static int gq_measure(SpecImpl* P, KTimer* kt, hipStream_t s) {
     k_gq_hist_perm<<<nbk, 256, 0, s>>>(T, P->bh, P->gq_permv, P->gq_chunks, P->gq_nch, P->gq_bins, P->gq_exact,
                                        P->gq_rowmu, 1.0 / P->c1, P->gq_ppart);
     FOTO_HIP_CHECK(hipGetLastError());
-    // (one shard with the wave-per-bin node kernel: the bin sums are taken there, from the chunk sums)
+    // (one shard: the node kernel takes the bin sums itself, from the chunk sums)
     if (!gq_fused_reduce(P)) {
         k_gq_perm_reduce<<<GQ_HIST / 4, 256, 0, s>>>(P->gq_ppart, P->gq_cfirst, P->gq_hist + (size_t)P->rank * GQ_HIST);
         FOTO_HIP_CHECK(hipGetLastError());
@@ -2233,23 +2187,21 @@ static int gq_pub_clear(SpecImpl* P, hipStream_t s) {
 // the world histograms -> Gauss nodes -> CG coefficients -> solution table; header to host
 static int gq_solve(SpecImpl* P, double rtol, int maxiter, KTimer* kt, hipStream_t s) {
     hipEvent_t e = kt ? kt->start(s) : nullptr;
-    if (!P->gq_nodes_wave)
-        k_gq_nodes<<<GQ_NODES / 64, 64, 0, s>>>(P->gq_hist, P->gq_bins, P->gq_exact, P->world, P->r * P->eps, P->c1, P->gqn);
-    else if (gq_fused_reduce(P))
+    if (gq_fused_reduce(P))
         k_gq_nodes_w<<<GQ_NB / 4, 256, 0, s>>>(nullptr, P->gq_ppart, P->gq_cfirst, P->gq_bins, P->gq_exact, 1,
                                                P->r * P->eps, P->c1, P->gqn);
     else
         k_gq_nodes_w<<<GQ_NB / 4, 256, 0, s>>>(P->gq_hist, nullptr, nullptr, P->gq_bins, P->gq_exact, P->world,
                                                P->r * P->eps, P->c1, P->gqn);
     FOTO_HIP_CHECK(hipGetLastError());
-    const char* kl = getenv("FOTO_GQ_KLIM");   // (tests: force the s-step redo path)
-    const int klim = kl ? std::max(0, std::min(GQ_KMAX, atoi(kl))) : GQ_KMAX;
+    // FOTO_GQ_KLIM forces the s-step redo path.  The one knob read per solve, not through Tuning:
+    // it is a test hook that tests/test_gpu_batch.py sets under a live context.
+    const int klim = std::max(0, std::min(GQ_KMAX, (int)env_int("FOTO_GQ_KLIM", GQ_KMAX)));
     // the header to the host slot: stored by the CG kernel itself (FOTO_HOST_CRIT=0: a copy)
     P->hlast = P->hslot;
     P->hslot ^= 1;
-    const char* hc = getenv("FOTO_HOST_CRIT");
-    const bool direct = !(hc && atoi(hc) == 0);
-    if (P->gq_cgtab) {
+    const bool direct = P->tn.host_crit;
+    if (P->tn.gq_cgtab) {
         k_gq_cgtab<<<1 + GQ_TAB / 256, 256, 0, s>>>(P->gqn, rtol, maxiter, klim, P->gq,
                                                     direct ? P->dgq2[P->hlast] : nullptr, P->gq_pub, P->gq_bins,
                                                     P->gq_qcos, P->r * P->eps, P->c1, P->gq_tab);
@@ -2282,27 +2234,14 @@ static int gq_enqueue(SpecImpl* P, const double* b, double* x, double rtol, int 
     const Geo& g = P->g;
     const double N = (double)g.Nt * (double)g.nxy;
     hipEvent_t e = kt ? kt->start(s) : nullptr;
-    if (P->xt) {   // b -(x, t)-> tmp -y-> b^: two passes (k_dct_xt_fwd)
-        FOTO_HIP_CHECK(dct_xt(g.Nt, g.Ny, g.Nx, false, P->Fx, P->Cth, b, P->tmp, s));
-        FOTO_HIP_CHECK(dct_pass(P, 1, false, g.Nt, g.Nx, P->tmp, P->bh, s));
-        if (kt) kt->stop(e, s, FOTO_K_DCT, 4.0 * 8.0 * N);
-    } else {
-        FOTO_HIP_CHECK(dct_pass(P, 0, false, g.Nt * g.Ny, 1, b, P->tmp, s));
-        FOTO_HIP_CHECK(dct_pass(P, 1, false, g.Nt, g.Nx, P->tmp, P->rh, s));
-        if (P->tcol) FOTO_HIP_CHECK(launch_tcol(P, false, P->rh, nullptr, rtol, maxiter, s, TC_PLAIN));
-        else FOTO_HIP_CHECK(dct_pass(P, 2, false, 1, (int)g.nxy, P->rh, P->bh, s));
-        if (kt) kt->stop(e, s, FOTO_K_DCT, 6.0 * 8.0 * N);
-    }
+    FOTO_HIP_CHECK(dct_pass(P, 0, false, g.Nt * g.Ny, 1, b, P->tmp, s));
+    FOTO_HIP_CHECK(dct_pass(P, 1, false, g.Nt, g.Nx, P->tmp, P->rh, s));
+    if (P->tcol) FOTO_HIP_CHECK(launch_tcol(P, false, P->rh, nullptr, rtol, maxiter, s, TC_PLAIN));
+    else FOTO_HIP_CHECK(dct_pass(P, 2, false, 1, (int)g.nxy, P->rh, P->bh, s));
+    if (kt) kt->stop(e, s, FOTO_K_DCT, 6.0 * 8.0 * N);
     FOTO_TRY(gq_measure(P, kt, s));
     FOTO_TRY(gq_solve(P, rtol, maxiter, kt, s));
     e = kt ? kt->start(s) : nullptr;
-    if (P->xt) {   // x^ -> rh -y-> tmp -(t, x)-> x (k_dct_tx_inv)
-        FOTO_HIP_CHECK(gq_xhat(P, P->rh, s));
-        FOTO_HIP_CHECK(dct_pass(P, 1, true, g.Nt, g.Nx, P->rh, P->tmp, s));
-        FOTO_HIP_CHECK(dct_xt(g.Nt, g.Ny, g.Nx, true, P->Fx, P->Cth, P->tmp, x, s));
-        if (kt) kt->stop(e, s, FOTO_K_DCT, 6.0 * 8.0 * N);
-        return 0;
-    }
     if (P->tcol) {
         FOTO_HIP_CHECK(launch_tcol(P, true, nullptr, P->tmp, rtol, maxiter, s));   // x^ -> rh, t^-1 -> tmp
     } else {
@@ -2389,9 +2328,7 @@ int SpectralPlan::solve_deferred(double* b, double* x, double rtol, int maxiter,
     if (kt) kt->stop(e, s, FOTO_K_DCT, 6.0 * 8.0 * N);
     // the previous solve's pass count + margin (passes past the end exit at once);
     // FOTO_CG_MARGIN overrides the default 2 (tests force the redo path with a negative one)
-    const char* me = getenv("FOTO_CG_MARGIN");
-    const int margin = me ? atoi(me) : 2;
-    const int n = std::max(1, P->last_passes + margin);
+    const int n = std::max(1, P->last_passes + P->tn.cg_margin);
     for (int j = 0; j < n; ++j) {
         hipEvent_t ep = kt ? kt->start(s) : nullptr;
         FOTO_HIP_CHECK(launch_s2(P, false, rtol, maxiter, nullptr, s));

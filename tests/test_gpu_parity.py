@@ -680,8 +680,7 @@ def test_gn_solve_multilevel(pair, monkeypatch):
 def test_gn_round5_forms_bit_identical(w, h, monkeypatch):
     """Round 5's GN launch structures -- the PCG update folded into the level-0 down leg and the
     last level above the coarsest solved with it in one LDS-resident block (k_mg_ltail; both
-    default), the small levels in one persistent launch with grid barriers (k_mg_ptail, opt-in
-    FOTO_MG_PTAIL=1) -- against the separate kernels (FOTO_GN_FOLD=0 ...): every cell's
+    default) -- against the separate kernels (FOTO_GN_FOLD=0, FOTO_MG_LTAIL=0): every cell's
     arithmetic is the same in the same order, so the iterates are bit-identical (only the stop
     test's r.r is summed per tile), and the PCG counts match.  The separate form also builds the
     multigrid coefficients the round-5 way (B per level, then the block inverses per level:
@@ -691,15 +690,14 @@ def test_gn_round5_forms_bit_identical(w, h, monkeypatch):
     f1, f2 = sinusoid_pair(w, h)
     monkeypatch.setenv("FOTO_GN_PLAN_CACHE", "0")
     out = {}
-    forms = (("sep", "0", "0", "0"), ("fold", "1", "0", "0"), ("ltail", "1", "0", "1"), ("ptail", "1", "1", "0"))
-    for key, fold, pt, lt in forms:
+    forms = (("sep", "0", "0"), ("fold", "1", "0"), ("ltail", "1", "1"))
+    for key, fold, lt in forms:
         monkeypatch.setenv("FOTO_GN_SETUP_FUSE", "0" if key == "sep" else "1")
         monkeypatch.setenv("FOTO_GN_RECOMP", "0" if key == "sep" else "1")
         monkeypatch.setenv("FOTO_GN_FOLD", fold)
-        monkeypatch.setenv("FOTO_MG_PTAIL", pt)
         monkeypatch.setenv("FOTO_MG_LTAIL", lt)
         out[key] = gn.solve(f1, f2, w, h, 0.1, 0.2)
-    for key in ("fold", "ltail", "ptail"):
+    for key in ("fold", "ltail"):
         u, v, m, info, its = out[key]
         print(f"{w}x{h} {key}: {its} PCG its (separate kernels: {out['sep'][4]})")
         assert info == 0 and its == out["sep"][4]

@@ -193,3 +193,44 @@ def test_callback_sees_its_own_iteration(gold, monkeypatch):
         s.iterate(3, 0.0, False, callback=cb0)
         s.phi()   # after the call: fine
     assert errs == [0, 1]   # (the last callback runs with nothing in flight)
+
+
+def test_tuning_is_fixed_when_the_context_is_built(gold, monkeypatch):
+    """The FOTO_* tuning variables are read once, when a context is built (csrc/foto_tuning.h):
+    what the environment holds later does not reach a live context.  The probe is
+    FOTO_CG_MARGIN=-6 on test_bb_deferred_cg's run (C1 golden, cg_mode 2, the stop rules on),
+    which under-predicts the s-step pass count so that deferred solves are redone (cg_redo).
+    (a) built with the variable, iterated without it: redone as if it were still set;
+    (b) built without it, iterated with it: no redo, crit and flow bit-identical to a run that
+    never saw the variable."""
+    d = gold("bb_c1.npz")
+    Nt, Ny, Nx = (int(v) for v in d["shape"])
+    r, tol, eps, max_it = d["params"]
+    monkeypatch.delenv("FOTO_CG_MARGIN", raising=False)
+
+    def margin(val):
+        if val is None:
+            monkeypatch.delenv("FOTO_CG_MARGIN", raising=False)
+        else:
+            monkeypatch.setenv("FOTO_CG_MARGIN", val)
+
+    def run(at_build, at_iterate):
+        margin(at_build)
+        with BBSolver(d["rho0"], d["rhoT"], Nt, Nx, Ny, r=r, reg_epsilon=eps, cg_mode=2) as s:
+            margin(at_iterate)
+            s.iterate(int(max_it), tol, True)
+            out = np.array(s.crit), s.flow(), s.stats()["cg_redo"]
+        margin(None)
+        return out
+
+    crit0, flow0, redo0 = run(None, None)
+    assert redo0 == 0
+    crit_a, _, redo_a = run("-6", None)
+    print("built with FOTO_CG_MARGIN=-6, iterated without: cg_redo", redo_a, "of", len(crit_a))
+    assert redo_a >= len(crit_a) // 2   # (test_bb_deferred_cg's bound)
+    crit_b, flow_b, redo_b = run(None, "-6")
+    print("built without, iterated with FOTO_CG_MARGIN=-6: cg_redo", redo_b)
+    assert redo_b == 0
+    assert np.array_equal(crit_b, crit0)
+    for x, y in zip(flow_b, flow0):
+        assert np.array_equal(x, y)
