@@ -441,6 +441,73 @@ int foto_dev_malloc(size_t bytes, void** out);
 int foto_dev_free(void* p);
 int foto_dev_memcpy(void* dst, const void* src, size_t bytes, int kind);
 
+/* ------------------------------------------------------------------ rendering
+ * The last stage of a device pipeline: what main.py:107-146 and run.sh:104,115 do with a flow --
+ * the clipped 8-bit reconstruction, the luminosity map, the colour code -- on the flow buffers
+ * the *_dev entries above write, for one or many records at once, without leaving HBM.  Additive.
+ * Every entry obeys the stream contract of the device-buffer section, unchanged; every device
+ * pointer is checked for the CURRENT device before anything is enqueued; an argument error leaves
+ * `out` untouched.  None of them synchronises with the host.
+ *
+ * FOTO_ERR_ARG before any device call: a null pointer, w or h < 1, channels < 1, stride_c <= 0,
+ * anything foto_image_check rejects for any channel, a flow dtype outside {F32, F64}, a layout
+ * outside {0, 1}, records < 1, flow data not aligned to its element, use_m = 1 or the luminosity
+ * with layout 1 (it carries no m), an out_dtype outside 0..2, a non-finite maxmotion, a misaligned
+ * out / maxrad.  FOTO_ERR_ARG after the pointer queries: a pointer that is not device memory of the
+ * current device, an `out` (or maxrad) whose byte range overlaps the frame or the flow (the warp
+ * gathers, as in foto_warp_dev).  All index arithmetic is int64_t: records * h * w * channels may
+ * pass 2^31.                                                                                  */
+/* A flow buffer exactly as foto_bb_flow_dev / foto_bb_flow_path_dev / foto_gn_plan_solve_dev
+ * write it (utils.saveFlo's payload, utils.py:273-292, for layout 1)                          */
+typedef struct {
+    const void* data;   /* DEVICE pointer                                                      */
+    int dtype;          /* FOTO_F32 | FOTO_F64                                                  */
+    int layout;         /* 0: [records][3][h][w] = u, v, m;  1: [records][h][w][2] = (u, v)     */
+    int records;        /* >= 1                                                                */
+} foto_flow;
+
+/* Host-only validation of a flow descriptor for w x h records (no HIP call): the flow rules of
+ * the list above.  Every entry below calls it first (utils.openFlo, utils.py:250-271, checks only
+ * the file's magic number).                                                                   */
+int foto_flow_check(const foto_flow* fl, int w, int h);
+
+/* main.py:109-110,142 on utils.apply_opticalflow (utils.py:186-248): for record k, channel c,
+ *   x = clip(apply_opticalflow(src_c / divisor, u_k, v_k, w, h, m_k), 0, 1).
+ * `src` describes channel 0; channel c starts c * stride_c ELEMENTS further on (interleaved HWC:
+ * stride_x = C, stride_c = 1; planar CHW: stride_c = the plane pitch; row-padded and transposed
+ * views are strides).  Flow values widen to double exactly and the arithmetic is foto_warp's,
+ * operation for operation; the weights and the four clamped taps are computed once per pixel and
+ * record and reused for every channel.  use_m = 0 leaves the frame unscaled (foto_warp with m =
+ * NULL); use_m = 1 needs layout 0.  out: C-contiguous [records][h][w][channels] of out_dtype:
+ * FOTO_U8 is the reference's TRUNCATING np.uint8(255 * x) (main.py:142) -- not the rounding to
+ * nearest of foto_bb_frames, which serves another purpose (a u8 frame surviving ingest and
+ * export); FOTO_F32 is (float)x; FOTO_F64 is x.  Deviation: a NaN x gives 0 in a uint8 output and
+ * stays NaN in a float output (np.clip keeps NaN; np.uint8(nan) is platform-defined); the taps of
+ * a pixel with a NaN displacement are pixel (0, 0)'s row / column, never out of range (the
+ * reference's int(nan) index raises).  One launch for all records and channels.               */
+int foto_render_warp_dev(const foto_image* src, int channels, int64_t stride_c, const foto_flow* fl, int use_m,
+                         int w, int h, void* out, int out_dtype, void* stream);
+/* main.py:146: out = uint8 [records][h][w] = np.uint8(255 * np.clip((m + 1) / 2, 0, 1)), truncating,
+ * NaN -> 0.  Needs layout 0.                                                                  */
+int foto_render_lum_dev(const foto_flow* fl, int w, int h, void* out, void* stream);
+/* run.sh:104,115 (the prebuilt bin/color_flow), by the algorithm bin/color_flow.py:23-63 restates:
+ * out = uint8 [records][h][w][3], RGB.  Unknown flow (|u| > 1e9, |v| > 1e9 or NaN) is black; rad =
+ * sqrt(u u + v v); maxrad = the maximum of rad over the known pixels of the record, replaced by
+ * maxmotion when maxmotion > 0, and 1 when it is <= 0; fx, fy = u, v / maxrad; the 55-entry wheel;
+ * hue from atan2(-fy, -fx) / pi; k0 = (int)fk, k1 = (k0 + 1) % 55, f = fk - k0; col = (1 - f) col0 +
+ * f col1; r <= 1 ? 1 - r (1 - col) : 0.75 col; (int)(255 col).  The arithmetic is FLOAT64 on the
+ * widened flow, in flow_to_color's order -- not the tool's float32: everything in this library is
+ * float64, and the image then depends on the device's atan2 at the last-ulp level only (sqrt and
+ * the divisions are correctly rounded).  Against the float32 tool, measured on the CPU with numpy
+ * on a 37x29 and a 64x48 random flow: maxmotion = 0 gave the same image from the float32 and the
+ * float64 restatement; maxmotion = 2 differed by one level on 1 sample of 3219 and 1 of 9216.
+ * The maximum is order-independent, hence deterministic: a block reduction, then one vector atomic
+ * max per block on the bit pattern of the non-negative double.  maxrad_or_null: a DEVICE
+ * double[records] that receives the value actually used; NULL: a grow-only per-device scratch of
+ * the library holds it.                                                                       */
+int foto_render_color_dev(const foto_flow* fl, int w, int h, double maxmotion, void* out, double* maxrad_or_null,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

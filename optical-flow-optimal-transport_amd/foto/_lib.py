@@ -106,6 +106,16 @@ class Image(ctypes.Structure):
     ]
 
 
+class Flow(ctypes.Structure):
+    """foto_flow (include/foto.h): a device flow buffer as the *_dev entries write it."""
+    _fields_ = [
+        ("data", ctypes.c_void_p),
+        ("dtype", ctypes.c_int),
+        ("layout", ctypes.c_int),
+        ("records", ctypes.c_int),
+    ]
+
+
 ITER_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int)
 
 _D = ctypes.POINTER(ctypes.c_double)
@@ -187,6 +197,12 @@ SIGNATURES = {
     "foto_dev_malloc": (_I, [ctypes.c_size_t, ctypes.POINTER(_P)]),
     "foto_dev_free": (_I, [_P]),
     "foto_dev_memcpy": (_I, [_P, _P, ctypes.c_size_t, _I]),
+    # rendering: flow buffers -> images on the device
+    "foto_flow_check": (_I, [ctypes.POINTER(Flow), _I, _I]),
+    "foto_render_warp_dev": (_I, [ctypes.POINTER(Image), _I, ctypes.c_int64, ctypes.POINTER(Flow), _I, _I, _I, _P, _I,
+                                  _P]),
+    "foto_render_lum_dev": (_I, [ctypes.POINTER(Flow), _I, _I, _P, _P]),
+    "foto_render_color_dev": (_I, [ctypes.POINTER(Flow), _I, _I, _Dbl, _P, _P, _P]),
 }
 
 _lib = None
