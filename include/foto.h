@@ -303,7 +303,9 @@ void foto_gn_plan_destroy(foto_gn_plan* p);
 /* ------------------------------------------------------------------ evaluation
  * the warp and the error metrics of utils.py on the GPU.      */
 /* utils.apply_opticalflow(f1, u, v, w, h, m) (utils.py:186-248): backward bilinear
- * warp of (1 + m) f1 (m may be NULL: f1 unscaled).  Bit-identical to the reference. */
+ * warp of (1 + m) f1 (m may be NULL: f1 unscaled).  Bit-identical to the reference.
+ * Deviation: a pixel with a NaN displacement is NaN, read from in-frame taps (pixel (0, 0)'s
+ * row / column); the reference's int(nan) index raises.                              */
 int foto_warp(const double* f1, const double* u, const double* v, const double* m, int w, int h, double* out);
 /* utils.EE and utils.AE (utils.py:294-338): out4 = {AEE, SDEE, AAE, SDAE}; EE > 50 and
  * NaN angular errors are ignored as in the reference.                               */

@@ -232,13 +232,12 @@ struct foto_bb_ctx {
     // points [M][2] and records [R][M][2], and the running float64 positions [M][2] that travel
     // between the launches of a path whose planes lie in several shards (virtual ranks)
     enum { TRK_PTS = 0, TRK_OUT = 1, TRK_POS = 2 };
-    double* trk[3] = {nullptr, nullptr, nullptr};
-    size_t trk_cap[3] = {0, 0, 0};   // in doubles
+    DevScratch trk[3];
     ~foto_bb_ctx() {
         if (sc) (void)hipStreamSynchronize(sc);
         if (s) (void)hipStreamSynchronize(s);   // (before the shards free their buffers)
         sh.clear();
-        for (double* b : trk) if (b) (void)hipFree(b);
+        for (DevScratch& b : trk) if (b.p) (void)hipFree(b.p);
         if (nc) (void)ncclCommDestroy(nc);
         if (hS) (void)hipHostFree(hS);
         for (double* h : hgath) if (h) (void)hipHostFree(h);
@@ -382,7 +381,7 @@ static int load_rho(foto_bb_ctx* c, Shard& s, const RhoSrc& src) {
     if (src.normalize) {   // each frame over its own sum (main.py:71-74), the sum in a fixed order
         if (!c->nrm) {
             void* b = nullptr;
-            FOTO_TRY(s.alloc(sizeof(double) * (2 + (size_t)sum_blocks(nxy)), &b));
+            FOTO_TRY(s.alloc(sizeof(double) * (2 + (size_t)capped_blocks(nxy, SUM_MAX_BLOCKS)), &b));
             c->nrm = (double*)b;
         }
         double* const rho[2] = {s.rho0, s.rhoT};
@@ -1144,7 +1143,8 @@ struct FlowDev {
     hipStream_t user;
 };
 
-static int flow(foto_bb_ctx* c, double* u, double* v, double* m, const FlowDev* dv = nullptr) {
+// (shard 0 reads the completed iteration's phi, k.phi: an export writes no solver state)
+static int flow(foto_bb_ctx* c, const Completed& k, double* u, double* v, double* m, const FlowDev* dv = nullptr) {
     if (!c->have_phi) {
         set_error("foto_bb_flow: no outer iteration has run yet (reference: UnboundLocalError for max_it=0)");
         return FOTO_ERR_STATE;
@@ -1163,8 +1163,10 @@ static int flow(foto_bb_ctx* c, double* u, double* v, double* m, const FlowDev* 
     for (int j = 0; j < W; ++j) {
         if (Shard* s = local(j)) {
             const int n_lo = s->g.t0, n_hi = std::min(s->g.t0 + s->g.nloc, c->Nt - 1);
-            FOTO_HIP_CHECK(launch_traj(s->g, s->phi, n_lo, std::max(n_lo, n_hi), s->px, s->py, j == 0, c->s));
-            if (j == W - 1) FOTO_HIP_CHECK(launch_flow_finish(c->Nx, c->Ny, s->px, s->py, s->fu, s->fv, s->fm, c->s));
+            const double* phi = (s == c->sh[0].get()) ? k.phi : s->phi;
+            FOTO_HIP_CHECK(launch_traj(s->g, phi, n_lo, std::max(n_lo, n_hi), s->px, s->py, j == 0, c->s));
+            if (j == W - 1)
+                FOTO_HIP_CHECK(launch_flow_record(c->Nx, c->Ny, s->px, s->py, s->fu, s->fv, s->fm, FOTO_F64, 0, c->s));
         }
         if (j + 1 < W) {
             const std::vector<Xfer> xs = relay_xfers(nxy, j);
@@ -1237,15 +1239,32 @@ static int flow_path(foto_bb_ctx* c, const Completed& k, double* hu, double* hv,
     return 0;
 }
 
-// The argument rules of foto_bb_frames / _dev (before anything is enqueued or written).
-static int frames_check(foto_bb_ctx* c, const double* s, int count, double scale, const void* out, int dtype,
-                        const char* who) {
+// The state rules of the one-device exports, before any argument is looked at ...
+static int export_state_check(foto_bb_ctx* c, const char* who) {
     if (!c) { set_error("%s: null ctx", who); return FOTO_ERR_ARG; }
     if (c->rccl) { set_error("%s: not supported on RCCL-sharded contexts", who); return FOTO_ERR_STATE; }
     if (c->broken) {
         set_error("%s: a failed foto_bb_iterate left the context inconsistent; foto_bb_reset it", who);
         return FOTO_ERR_STATE;
     }
+    return 0;
+}
+
+// ... and of those that read phi (the device flow, the flow path, point tracking; the frames read
+// mu, which a context has from the start)
+static int path_state_check(foto_bb_ctx* c, const char* who) {
+    FOTO_TRY(export_state_check(c, who));
+    if (!c->have_phi) {   // (before the output is looked at: the reference's UnboundLocalError)
+        set_error("%s: no outer iteration has run yet", who);
+        return FOTO_ERR_STATE;
+    }
+    return 0;
+}
+
+// The argument rules of foto_bb_frames / _dev (before anything is enqueued or written).
+static int frames_check(foto_bb_ctx* c, const double* s, int count, double scale, const void* out, int dtype,
+                        const char* who) {
+    FOTO_TRY(export_state_check(c, who));
     if (!s || !out) { set_error("%s: null pointer", who); return FOTO_ERR_ARG; }
     if (count <= 0) { set_error("%s: count = %d must be > 0", who, count); return FOTO_ERR_ARG; }
     if (!std::isfinite(scale) || !(scale > 0.0)) {
@@ -1626,52 +1645,21 @@ int foto_bb_flow_dev(foto_bb_ctx* c, void* out, int dtype, int layout, void* str
         set_error("foto_bb_flow_dev: device buffers are not supported on RCCL-sharded contexts");
         return FOTO_ERR_STATE;
     }
-    if (c->broken) { set_error("foto_bb_flow_dev: a failed foto_bb_iterate left the context inconsistent; foto_bb_reset it"); return FOTO_ERR_STATE; }
-    if (!c->have_phi) {   // (before the output is looked at: the reference's UnboundLocalError)
-        set_error("foto_bb_flow_dev: no outer iteration has run yet");
-        return FOTO_ERR_STATE;
-    }
+    FOTO_TRY(path_state_check(c, "foto_bb_flow_dev"));   // (the two above: this entry's own wording)
     FOTO_TRY(export_check(out, dtype, layout, (int64_t)c->Nx * c->Ny, stream_device(c->s), "foto_bb_flow_dev"));
     Completed k;
     FOTO_TRY(completed_state(c, "foto_bb_flow_dev", &k));
-    Shard& s0 = *c->sh[0];
-    double* keep = s0.phi;
-    s0.phi = k.phi;
     const FlowDev dv{out, dtype, layout, (hipStream_t)stream};
-    int rc = flow(c, nullptr, nullptr, nullptr, &dv);
-    s0.phi = keep;
-    if (rc >= 0) rc = c->link.leave(c->s, dv.user);
-    return rc;
+    FOTO_TRY(flow(c, k, nullptr, nullptr, nullptr, &dv));
+    return c->link.leave(c->s, dv.user);
 }
 
 int foto_bb_flow(foto_bb_ctx* c, double* u, double* v, double* m) {
     if (!c) { set_error("null ctx"); return FOTO_ERR_ARG; }
     if (c->broken) { set_error("foto_bb_flow: a failed foto_bb_iterate left the context inconsistent; foto_bb_reset it"); return FOTO_ERR_STATE; }
-    Completed k;
+    Completed k;   // (pipelined loop, from the callback: the completed iteration's phi)
     FOTO_TRY(completed_state(c, "foto_bb_flow", &k));
-    // (pipelined loop, from the callback: the completed iteration's phi, then the one in flight's back)
-    Shard& s0 = *c->sh[0];
-    double* keep = s0.phi;
-    s0.phi = k.phi;
-    const int rc = flow(c, u, v, m);
-    s0.phi = keep;
-    return rc;
-}
-
-// The state rules of the exports that read phi (flow path, point tracking), before any argument
-// is looked at.
-static int path_state_check(foto_bb_ctx* c, const char* who) {
-    if (!c) { set_error("%s: null ctx", who); return FOTO_ERR_ARG; }
-    if (c->rccl) { set_error("%s: not supported on RCCL-sharded contexts", who); return FOTO_ERR_STATE; }
-    if (c->broken) {
-        set_error("%s: a failed foto_bb_iterate left the context inconsistent; foto_bb_reset it", who);
-        return FOTO_ERR_STATE;
-    }
-    if (!c->have_phi) {   // (before the output is looked at, as foto_bb_flow_dev)
-        set_error("%s: no outer iteration has run yet", who);
-        return FOTO_ERR_STATE;
-    }
-    return 0;
+    return flow(c, k, u, v, m);
 }
 
 static int flow_path_entry(foto_bb_ctx* c, double* u, double* v, double* m, const FlowDev* dv, const char* who) {
@@ -1698,21 +1686,6 @@ int foto_bb_flow_path_dev(foto_bb_ctx* c, void* out, int dtype, int layout, void
 }
 
 // ------------------------------------------------------------------ point tracking
-// Grow-only device scratch of the context (freed with it).  Growing waits for the stream first:
-// an earlier call's launches may still read the buffer being replaced.
-static int track_scratch(foto_bb_ctx* c, int which, size_t n_doubles) {
-    if (c->trk_cap[which] >= n_doubles) return 0;
-    FOTO_HIP_CHECK(hipStreamSynchronize(c->s));
-    if (c->trk[which]) FOTO_HIP_CHECK(hipFree(c->trk[which]));
-    c->trk[which] = nullptr;
-    c->trk_cap[which] = 0;
-    void* b = nullptr;
-    FOTO_HIP_CHECK(hipMalloc(&b, n_doubles * sizeof(double)));
-    c->trk[which] = (double*)b;
-    c->trk_cap[which] = n_doubles;
-    return 0;
-}
-
 // Plane n's trajectory step reads phi plane n of the shard that owns it (shard 0: the completed
 // iteration's phi, as flow_path): one launch per run of planes in one buffer, so one launch on a
 // one-shard context.  Between launches the float64 positions travel through the TRK_POS scratch
@@ -1726,7 +1699,7 @@ static int track_run(foto_bb_ctx* c, const Completed& k, const void* pts, int pt
                      void* out, int dtype) {
     Shard& s0 = *c->sh[0];
     const int last = c->Nt - 1;
-    double* const pos = c->trk[foto_bb_ctx::TRK_POS];
+    double* const pos = (double*)c->trk[foto_bb_ctx::TRK_POS].p;
     for (int n = 0; n < last;) {
         Shard* sp = plane_owner(c, n);
         if (!sp) { set_error("point tracking: no local shard owns plane %d", n); return FOTO_ERR_STATE; }
@@ -1746,11 +1719,11 @@ int foto_bb_track(foto_bb_ctx* c, const double* pts, int64_t M, int all_steps, d
     Completed k;
     FOTO_TRY(completed_state(c, who, &k));
     const size_t np = 2 * (size_t)M, nr = np * (size_t)(all_steps ? c->Nt - 1 : 1);
-    FOTO_TRY(track_scratch(c, foto_bb_ctx::TRK_PTS, np));
-    FOTO_TRY(track_scratch(c, foto_bb_ctx::TRK_OUT, nr));
-    if (track_needs_pos(c)) FOTO_TRY(track_scratch(c, foto_bb_ctx::TRK_POS, np));
-    double* dp = c->trk[foto_bb_ctx::TRK_PTS];
-    double* dout = c->trk[foto_bb_ctx::TRK_OUT];
+    FOTO_TRY(c->trk[foto_bb_ctx::TRK_PTS].reserve(np * sizeof(double), c->s));
+    FOTO_TRY(c->trk[foto_bb_ctx::TRK_OUT].reserve(nr * sizeof(double), c->s));
+    if (track_needs_pos(c)) FOTO_TRY(c->trk[foto_bb_ctx::TRK_POS].reserve(np * sizeof(double), c->s));
+    double* dp = (double*)c->trk[foto_bb_ctx::TRK_PTS].p;
+    double* dout = (double*)c->trk[foto_bb_ctx::TRK_OUT].p;
     FOTO_HIP_CHECK(hipMemcpyAsync(dp, pts, np * sizeof(double), hipMemcpyHostToDevice, c->s));
     FOTO_TRY(track_run(c, k, dp, FOTO_F64, M, all_steps, dout, FOTO_F64));
     FOTO_HIP_CHECK(hipMemcpyAsync(out, dout, nr * sizeof(double), hipMemcpyDeviceToHost, c->s));
@@ -1771,7 +1744,8 @@ int foto_bb_track_dev(foto_bb_ctx* c, const void* pts, int pts_dtype, int64_t M,
     FOTO_TRY(dev_ptr_check(out, nr * dtype_bytes(dtype), dev, who, "out"));
     Completed k;
     FOTO_TRY(completed_state(c, who, &k));
-    if (track_needs_pos(c)) FOTO_TRY(track_scratch(c, foto_bb_ctx::TRK_POS, np));   // (virtual ranks only)
+    if (track_needs_pos(c))   // (virtual ranks only)
+        FOTO_TRY(c->trk[foto_bb_ctx::TRK_POS].reserve(np * sizeof(double), c->s));
     FOTO_TRY(c->link.enter((hipStream_t)stream, c->s));   // (before the first read of `pts` / write of `out`)
     FOTO_TRY(track_run(c, k, pts, pts_dtype, M, all_steps, out, dtype));
     return c->link.leave(c->s, (hipStream_t)stream);

@@ -226,7 +226,7 @@ int foto_flow_from_phi(const double* phi, int Nt, int Nx, int Ny, double* u, dou
     FOTO_TRY(S.dev(n, &dv));
     FOTO_TRY(S.dev(n, &dm));
     FOTO_HIP_CHECK(launch_traj(g, d, 0, Nt - 1, px, py, 1, S.s));
-    FOTO_HIP_CHECK(launch_flow_finish(Nx, Ny, px, py, du, dv, dm, S.s));
+    FOTO_HIP_CHECK(launch_flow_record(Nx, Ny, px, py, du, dv, dm, FOTO_F64, 0, S.s));
     FOTO_TRY(S.down(u, du, n));
     FOTO_TRY(S.down(v, dv, n));
     FOTO_TRY(S.down(m, dm, n));

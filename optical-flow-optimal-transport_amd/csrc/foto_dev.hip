@@ -14,13 +14,12 @@
 #include <cmath>
 #include <cstring>
 
+#include "foto_devutil.h"
 #include "foto_internal.h"
 
 namespace foto {
 
 namespace {
-
-constexpr int SUM_MAX_BLOCKS = 2048;
 
 template <class T> struct Vec16;   // the 16-byte load of the vector path
 template <> struct Vec16<unsigned char> { typedef unsigned int type __attribute__((ext_vector_type(4))); };
@@ -57,32 +56,22 @@ __global__ __launch_bounds__(NT) void k_ingest(const T* __restrict__ src, int64_
 }
 
 // fixed-order sum: a grid that depends on n only, per-thread strided partial sums, the block
-// tree of ev_block_sum (foto_eval.hip), then one block over the block partials
-__device__ __forceinline__ double block_sum(double v, double* sh /* NT */) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int st = NT / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
+// tree (block_tree_sum), then one block over the block partials
 __global__ __launch_bounds__(NT) void k_sum_partial(int64_t n, const double* __restrict__ x,
                                                     double* __restrict__ part) {
     __shared__ double sh[NT];
-    double acc = 0.0;
-    for (int64_t p = (int64_t)blockIdx.x * NT + threadIdx.x; p < n; p += (int64_t)gridDim.x * NT) acc += x[p];
-    const double s = block_sum(acc, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = s;
+    double acc[1] = {0.0};
+    for (int64_t p = (int64_t)blockIdx.x * NT + threadIdx.x; p < n; p += (int64_t)gridDim.x * NT) acc[0] += x[p];
+    block_tree_sum<NT>(acc, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
 }
 
 __global__ __launch_bounds__(NT) void k_sum_final(int nb, const double* __restrict__ part, double* __restrict__ tot) {
     __shared__ double sh[NT];
-    double acc = 0.0;
-    for (int b = threadIdx.x; b < nb; b += NT) acc += part[b];
-    const double s = block_sum(acc, sh);
-    if (threadIdx.x == 0) tot[0] = s;
+    double acc[1] = {0.0};
+    for (int b = threadIdx.x; b < nb; b += NT) acc[0] += part[b];
+    block_tree_sum<NT>(acc, sh);
+    if (threadIdx.x == 0) tot[0] = sh[0];
 }
 
 __global__ __launch_bounds__(NT) void k_div_scalar(int64_t n, double* __restrict__ x, const double* __restrict__ S) {
@@ -165,10 +154,6 @@ hipError_t frames_t(const FrameArgs& fa, int count, int64_t n, double scale, voi
     return hipGetLastError();
 }
 
-int stream_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(flat_blocks(n), 1 << 16)); }
-
-size_t dtype_size(int dtype) { return dtype == FOTO_U8 ? 1 : dtype == FOTO_F32 ? 4 : 8; }
-
 template <class T>
 hipError_t ingest_t(const foto_image& im, int w, int h, double* dst, hipStream_t s) {
     constexpr int VE = 16 / (int)sizeof(T);
@@ -176,7 +161,7 @@ hipError_t ingest_t(const foto_image& im, int w, int h, double* dst, hipStream_t
     const T* src = (const T*)im.data;
     const bool vec = im.stride_x == 1 && ((uintptr_t)im.data % 16) == 0 &&
                      (((uint64_t)im.stride_y * sizeof(T)) % 16) == 0;
-    const int nb = stream_blocks((int64_t)h * cpr);
+    const int nb = capped_blocks((int64_t)h * cpr, STREAM_MAX_BLOCKS);
     if (vec) k_ingest<T, true><<<nb, NT, 0, s>>>(src, im.stride_y, im.stride_x, w, h, cpr, im.divisor, dst);
     else k_ingest<T, false><<<nb, NT, 0, s>>>(src, im.stride_y, im.stride_x, w, h, cpr, im.divisor, dst);
     return hipGetLastError();
@@ -185,7 +170,7 @@ hipError_t ingest_t(const foto_image& im, int w, int h, double* dst, hipStream_t
 template <class T>
 hipError_t export_t(int64_t n, const double* a, const double* b, const double* c, void* out, int layout,
                     hipStream_t s) {
-    const int nb = stream_blocks(n);
+    const int nb = capped_blocks(n, STREAM_MAX_BLOCKS);
     if (layout == 0) k_export<T, 0><<<nb, NT, 0, s>>>(n, a, b, c, (T*)out);
     else k_export<T, 1><<<nb, NT, 0, s>>>(n, a, b, c, (T*)out);
     return hipGetLastError();
@@ -212,8 +197,8 @@ int image_check(const foto_image* im, int w, int h, const char* who) {
         set_error("%s: divisor %g must be finite and non-zero", who, im->divisor);
         return FOTO_ERR_ARG;
     }
-    if ((uintptr_t)im->data % dtype_size(im->dtype) != 0) {
-        set_error("%s: data %p is not aligned to its %zu-byte element", who, im->data, dtype_size(im->dtype));
+    if ((uintptr_t)im->data % dtype_bytes(im->dtype) != 0) {
+        set_error("%s: data %p is not aligned to its %zu-byte element", who, im->data, dtype_bytes(im->dtype));
         return FOTO_ERR_ARG;
     }
     // the w x h pixels must be distinct elements: the lines along the minor stride may not
@@ -268,7 +253,7 @@ int dev_ptr_check(const void* p, size_t bytes, int device, const char* who, cons
 int image_dev_check(const foto_image* im, int w, int h, int device, const char* who) {
     FOTO_TRY(image_check(im, w, h, who));
     const size_t last = (size_t)(h - 1) * (size_t)im->stride_y + (size_t)(w - 1) * (size_t)im->stride_x;
-    return dev_ptr_check(im->data, (last + 1) * dtype_size(im->dtype), device, who, "image data");
+    return dev_ptr_check(im->data, (last + 1) * dtype_bytes(im->dtype), device, who, "image data");
 }
 
 int export_check(const void* out, int dtype, int layout, int64_t n, int device, const char* who) {
@@ -280,11 +265,11 @@ int export_check(const void* out, int dtype, int layout, int64_t n, int device, 
         set_error("%s: layout %d is not 0 (planar u, v, m) / 1 (interleaved (u, v))", who, layout);
         return FOTO_ERR_ARG;
     }
-    if (out && (uintptr_t)out % dtype_size(dtype) != 0) {
-        set_error("%s: out %p is not aligned to its %zu-byte element", who, out, dtype_size(dtype));
+    if (out && (uintptr_t)out % dtype_bytes(dtype) != 0) {
+        set_error("%s: out %p is not aligned to its %zu-byte element", who, out, dtype_bytes(dtype));
         return FOTO_ERR_ARG;
     }
-    return dev_ptr_check(out, (size_t)n * (layout == 0 ? 3 : 2) * dtype_size(dtype), device, who, "out");
+    return dev_ptr_check(out, (size_t)n * (layout == 0 ? 3 : 2) * dtype_bytes(dtype), device, who, "out");
 }
 
 int track_arg_check(const void* pts, const void* out, int64_t M, int all_steps, const char* who) {
@@ -305,8 +290,8 @@ int track_dtype_check(const void* p, int dtype, const char* who, const char* wha
         set_error("%s: %s dtype %d is not FOTO_F32 / FOTO_F64", who, what, dtype);
         return FOTO_ERR_ARG;
     }
-    if ((uintptr_t)p % (2 * dtype_size(dtype)) != 0) {   // one (x, y) pair is one vector load / store
-        set_error("%s: %s %p is not aligned to its %zu-byte (x, y) pair", who, what, p, 2 * dtype_size(dtype));
+    if ((uintptr_t)p % (2 * dtype_bytes(dtype)) != 0) {   // one (x, y) pair is one vector load / store
+        set_error("%s: %s %p is not aligned to its %zu-byte (x, y) pair", who, what, p, 2 * dtype_bytes(dtype));
         return FOTO_ERR_ARG;
     }
     return 0;
@@ -323,17 +308,15 @@ hipError_t launch_ingest(const foto_image& im, int w, int h, double* dst, hipStr
     return hipErrorInvalidValue;
 }
 
-int sum_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(flat_blocks(n), SUM_MAX_BLOCKS)); }
-
 hipError_t launch_sum(int64_t n, const double* x, double* part, double* tot, hipStream_t s) {
-    const int nb = sum_blocks(n);
+    const int nb = capped_blocks(n, SUM_MAX_BLOCKS);
     k_sum_partial<<<nb, NT, 0, s>>>(n, x, part);
     k_sum_final<<<1, NT, 0, s>>>(nb, part, tot);
     return hipGetLastError();
 }
 
 hipError_t launch_div_scalar(int64_t n, double* x, const double* S, hipStream_t s) {
-    k_div_scalar<<<stream_blocks(n), NT, 0, s>>>(n, x, S);
+    k_div_scalar<<<capped_blocks(n, STREAM_MAX_BLOCKS), NT, 0, s>>>(n, x, S);
     return hipGetLastError();
 }
 
@@ -343,8 +326,6 @@ hipError_t launch_export(int64_t n, const double* a, const double* b, const doub
     if (dtype == FOTO_F64) return export_t<double>(n, a, b, c, out, layout, s);
     return hipErrorInvalidValue;
 }
-
-size_t dtype_bytes(int dtype) { return dtype_size(dtype); }
 
 hipError_t launch_frames(const FrameArgs& fa, int count, int64_t n, double scale, void* out, int dtype,
                          hipStream_t s) {

@@ -1,7 +1,13 @@
-// Device helpers shared by the spectral units (foto_spectral.hip, foto_dct.hip, foto_probe.hip).
+// Device helpers shared between units: the spectral units' stores and loads (foto_spectral.hip,
+// foto_dct.hip, foto_probe.hip), the fixed-order block sum (foto_dev.hip, foto_eval.hip), the
+// trajectory step (k_traj, k_track: foto_kernels.hip) and the backward warp (k_warp:
+// foto_eval.hip, k_render_warp: foto_render.hip).  Outputs that are documented as bit-identical
+// to each other are so because they run the one definition here.
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <cstdint>
 
 namespace foto {
 
@@ -27,6 +33,106 @@ __device__ __forceinline__ void st_wt16(__amdgpu_buffer_rsrc_t rs, int off_bytes
 template <class V>
 __device__ __forceinline__ V ld_dead(const V* p) {
     return __builtin_nontemporal_load(p);
+}
+
+// Fixed-order block sum of Q quantities per thread over N threads (N a power of two): v[q] of
+// thread t goes to sh[q * N + t], a halving tree leaves the totals in sh[q * N].  The order
+// depends on N alone, so a sum keeps its bits from launch to launch.
+template <int N, int Q>
+__device__ __forceinline__ void block_tree_sum(const double (&v)[Q], double* sh /* Q * N */) {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) sh[q * N + threadIdx.x] = v[q];
+    __syncthreads();
+    for (int st = N / 2; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st)
+#pragma unroll
+            for (int q = 0; q < Q; ++q) sh[q * N + threadIdx.x] += sh[q * N + threadIdx.x + st];
+        __syncthreads();
+    }
+}
+
+// ----------------------------------------------------------------------------- trajectory step
+__device__ __forceinline__ int trunc_clamp(double v, int hi) {
+    double t = trunc(v);               // int() truncates toward zero
+    if (!(t >= 0.0)) t = 0.0;          // also maps NaN to 0
+    if (t > (double)hi) t = (double)hi;
+    return (int)t;
+}
+
+// One step of reconstructTrajectory (utils.py:44-99): (x, y) += the bilinear sample at (x, y) of
+// un = G_x P, vn = G_y P (central differences, bc 'N': zero on the edge columns / rows) of the
+// Ny x Nx plane P, Nx, Ny >= 2.  The 12 values of P it needs (the 4 x 4 neighbourhood of
+// (tx, ty) without its corners) are loaded together from indices clamped into the plane, and
+// the edge zeros selected afterwards: tx in [0, Nx-2] and ty in [0, Ny-2] for every x, y
+// (trunc_clamp maps NaN to 0 and clamps +-inf), so every load is inside the plane whatever the
+// position -- a non-finite position gives a non-finite position and nothing else.
+__device__ __forceinline__ void traj_step(const double* __restrict__ P, int Nx, int Ny, double& x, double& y) {
+    const int tx = trunc_clamp(x, Nx - 2), ty = trunc_clamp(y, Ny - 2);
+    const int xm = tx > 0 ? tx - 1 : 0, xp = tx + 2 < Nx ? tx + 2 : Nx - 1;
+    const int ym = ty > 0 ? ty - 1 : 0, yp = ty + 2 < Ny ? ty + 2 : Ny - 1;
+    const double* r0 = P + (int64_t)ty * Nx;
+    const double* r1 = r0 + Nx;
+    const double* rm = P + (int64_t)ym * Nx;
+    const double* rp = P + (int64_t)yp * Nx;
+    // the 12 loads, ahead of their first use
+    const double a0 = r0[xm], b0 = r0[tx], c0 = r0[tx + 1], d0 = r0[xp];
+    const double a1 = r1[xm], b1 = r1[tx], c1 = r1[tx + 1], d1 = r1[xp];
+    const double bm = rm[tx], cm = rm[tx + 1];
+    const double bp = rp[tx], cp = rp[tx + 1];
+    const double dX = x - tx, dY = y - ty;
+    const double w1 = (1 - dY) * (1 - dX), w2 = dX * (1 - dY), w3 = dY * dX, w4 = (1 - dX) * dY;
+    const bool xl = tx == 0, xr = tx + 1 == Nx - 1;   // un is 0 on columns 0 and Nx-1
+    const bool yl = ty == 0, yr = ty + 1 == Ny - 1;   // vn is 0 on rows 0 and Ny-1
+    const double u00 = xl ? 0.0 : 0.5 * (c0 - a0), u01 = xr ? 0.0 : 0.5 * (d0 - b0);
+    const double u11 = xr ? 0.0 : 0.5 * (d1 - b1), u10 = xl ? 0.0 : 0.5 * (c1 - a1);
+    const double v00 = yl ? 0.0 : 0.5 * (b1 - bm), v01 = yl ? 0.0 : 0.5 * (c1 - cm);
+    const double v11 = yr ? 0.0 : 0.5 * (cp - c0), v10 = yr ? 0.0 : 0.5 * (bp - b0);
+    x += w1 * u00 + w2 * u01 + w3 * u11 + w4 * u10;
+    y += w1 * v00 + w2 * v01 + w3 * v11 + w4 * v10;
+}
+
+// ----------------------------------------------------------------------------- backward warp
+// One output pixel (row i, column j) of utils.apply_opticalflow (utils.py:186-248) in a w x h
+// frame, displacement (u, v): the four bilinear weights and the clamped taps, rows a, a1 and
+// columns b, b1.  A NaN displacement gives NaN weights, so a NaN pixel; its taps stay in the frame.
+struct WarpTaps {
+    double w1, w2, w3, w4;
+    int64_t a, b, a1, b1;
+};
+
+__device__ __forceinline__ WarpTaps warp_taps(int i, int j, double u, double v, int w, int h) {
+    double ti = (double)i - v, tj = (double)j - u;
+    const double dI = ti - trunc(ti), dJ = tj - trunc(tj);
+    WarpTaps T;
+    T.w1 = (1 - dI) * (1 - dJ);
+    T.w2 = dJ * (1 - dI);
+    T.w3 = dI * dJ;
+    T.w4 = (1 - dJ) * dI;
+    if (ti >= h) ti = h - 1;
+    if (tj >= w) tj = w - 1;
+    if (ti < 0) ti = 0;
+    if (tj < 0) tj = 0;
+    if (ti != ti) ti = 0;
+    if (tj != tj) tj = 0;
+    T.a = (int64_t)ti;
+    T.b = (int64_t)tj;
+    T.a1 = (T.a < h - 1) ? T.a + 1 : T.a;
+    T.b1 = (T.b < w - 1) ? T.b + 1 : T.b;
+    return T;
+}
+
+// w1 F(a, b) + w2 F(a, b1) + w3 F(a1, b1) + w4 F(a1, b) in the reference's order; F = g f with
+// g = 1 + m at the tap, or f alone
+__device__ __forceinline__ double warp_sum(const WarpTaps& T, double f1, double f2, double f3, double f4) {
+    double x = T.w1 * f1;
+    x = x + T.w2 * f2;
+    x = x + T.w3 * f3;
+    x = x + T.w4 * f4;
+    return x;
+}
+__device__ __forceinline__ double warp_sum(const WarpTaps& T, double g1, double g2, double g3, double g4, double f1,
+                                           double f2, double f3, double f4) {
+    return warp_sum(T, g1 * f1, g2 * f2, g3 * f3, g4 * f4);
 }
 
 }  // namespace foto

@@ -13,6 +13,7 @@
 #include <mutex>
 #include <vector>
 
+#include "foto_devutil.h"
 #include "foto_internal.h"
 
 
@@ -20,6 +21,8 @@ namespace foto {
 
 constexpr int EV_NT = 256;
 constexpr int EV_Q = 6;   // quantities per block partial
+constexpr int EV_MAX_BLOCKS = 2048;
+static_assert(EV_NT == NT, "capped_blocks counts blocks of NT threads");
 
 __global__ __launch_bounds__(EV_NT) void k_warp(const double* __restrict__ f1, const double* __restrict__ m,
                                                 const double* __restrict__ u, const double* __restrict__ v, int w,
@@ -27,33 +30,10 @@ __global__ __launch_bounds__(EV_NT) void k_warp(const double* __restrict__ f1, c
     const int64_t n = (int64_t)w * h;
     for (int64_t p = (int64_t)blockIdx.x * EV_NT + threadIdx.x; p < n; p += (int64_t)gridDim.x * EV_NT) {
         const int i = (int)(p / w), j = (int)(p - (p / w) * w);   // row, column
-        double ti = (double)i - v[p], tj = (double)j - u[p];
-        const double dI = ti - trunc(ti), dJ = tj - trunc(tj);
-        const double w1 = (1 - dI) * (1 - dJ), w2 = dJ * (1 - dI), w3 = dI * dJ, w4 = (1 - dJ) * dI;
-        if (ti >= h) ti = h - 1;
-        if (tj >= w) tj = w - 1;
-        if (ti < 0) ti = 0;
-        if (tj < 0) tj = 0;
-        const int64_t a = (int64_t)ti, b = (int64_t)tj;
-        const int64_t a1 = (a < h - 1) ? a + 1 : a, b1 = (b < w - 1) ? b + 1 : b;
-        auto F = [&](int64_t q) { return m ? (1 + m[q]) * f1[q] : f1[q]; };   // (1 + m) f1
-        double x = w1 * F(a * w + b);
-        x = x + w2 * F(a * w + b1);
-        x = x + w3 * F(a1 * w + b1);
-        x = x + w4 * F(a1 * w + b);
-        out[p] = x;
-    }
-}
-
-__device__ __forceinline__ void ev_block_sum(double (&v)[EV_Q], double* sh /* EV_Q * EV_NT */) {
-#pragma unroll
-    for (int q = 0; q < EV_Q; ++q) sh[q * EV_NT + threadIdx.x] = v[q];
-    __syncthreads();
-    for (int st = EV_NT / 2; st > 0; st >>= 1) {
-        if (threadIdx.x < st)
-#pragma unroll
-            for (int q = 0; q < EV_Q; ++q) sh[q * EV_NT + threadIdx.x] += sh[q * EV_NT + threadIdx.x + st];
-        __syncthreads();
+        const WarpTaps T = warp_taps(i, j, u[p], v[p], w, h);
+        const int64_t q1 = T.a * w + T.b, q2 = T.a * w + T.b1, q3 = T.a1 * w + T.b1, q4 = T.a1 * w + T.b;
+        out[p] = m ? warp_sum(T, 1 + m[q1], 1 + m[q2], 1 + m[q3], 1 + m[q4], f1[q1], f1[q2], f1[q3], f1[q4])
+                   : warp_sum(T, f1[q1], f1[q2], f1[q3], f1[q4]);
     }
 }
 
@@ -86,7 +66,7 @@ __global__ __launch_bounds__(EV_NT) void k_err_partial(int64_t n, const double* 
             acc[4] += d * d;
         }
     }
-    ev_block_sum(acc, sh);
+    block_tree_sum<EV_NT>(acc, sh);
     if (threadIdx.x < EV_Q) part[(int64_t)blockIdx.x * EV_Q + threadIdx.x] = sh[threadIdx.x * EV_NT];
 }
 
@@ -98,7 +78,7 @@ __global__ __launch_bounds__(EV_NT) void k_err_final(int nb, const double* __res
     for (int b = threadIdx.x; b < nb; b += EV_NT)
 #pragma unroll
         for (int q = 0; q < EV_Q; ++q) acc[q] += part[(int64_t)b * EV_Q + q];
-    ev_block_sum(acc, sh);
+    block_tree_sum<EV_NT>(acc, sh);
     if (threadIdx.x < EV_Q) tot[threadIdx.x] = sh[threadIdx.x * EV_NT];
 }
 
@@ -109,8 +89,7 @@ namespace {
 // and cost more than the kernels).  One call at a time holds them.
 constexpr int EV_SLOTS = 8;
 struct EvSlots {
-    void* p[EV_SLOTS] = {};
-    size_t cap[EV_SLOTS] = {};
+    DevScratch buf[EV_SLOTS];
     StreamLink* link = nullptr;   // the *_dev entries: the caller's stream <-> the call's (kept, like the slots)
 };
 std::mutex ev_mu;
@@ -153,22 +132,12 @@ struct EvScope {
         return dev_ptr_check(p, n * sizeof(double), device, who, what);
     }
     int slot(size_t n, double** d) {
-        const size_t bytes = std::max<size_t>(n, 1) * sizeof(double);
         if (used >= EV_SLOTS) {
             set_error("evaluation: out of scratch slots");
             return FOTO_ERR_STATE;
         }
-        if (sl->cap[used] < bytes) {
-            if (sl->p[used]) {
-                FOTO_HIP_CHECK(hipStreamSynchronize(s));
-                FOTO_HIP_CHECK(hipFree(sl->p[used]));
-                sl->p[used] = nullptr;
-                sl->cap[used] = 0;
-            }
-            FOTO_HIP_CHECK(hipMalloc(&sl->p[used], bytes));
-            sl->cap[used] = bytes;
-        }
-        *d = (double*)sl->p[used++];
+        FOTO_TRY(sl->buf[used].reserve(std::max<size_t>(n, 1) * sizeof(double), s));
+        *d = (double*)sl->buf[used++].p;
         return 0;
     }
     int up(const double* h, size_t n, double** d) {
@@ -184,8 +153,6 @@ struct EvScope {
         stream_release(s);
     }
 };
-
-int ev_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + EV_NT - 1) / EV_NT, 2048)); }
 
 // the two passes; out: mean EE, std EE, mean AE, std AE, IE (any of the inputs may be absent)
 // (on_dev: the six inputs are device arrays, used in place -- the *_dev entries)
@@ -214,7 +181,7 @@ int ev_errors(const double* u, const double* v, const double* uG, const double* 
     FOTO_TRY(S.up(vG, n, &dvG));
     FOTO_TRY(S.up(I, n, &dI));
     FOTO_TRY(S.up(IG, n, &dIG));
-    const int nb = ev_blocks(n);
+    const int nb = capped_blocks(n, EV_MAX_BLOCKS);
     FOTO_TRY(S.dev((size_t)nb * EV_Q, &part));
     FOTO_TRY(S.dev(EV_Q, &tot));
     double h0[EV_Q], h1[EV_Q];
@@ -261,7 +228,7 @@ int foto_warp(const double* f1, const double* u, const double* v, const double* 
     FOTO_TRY(S.up(u, n, &du));
     FOTO_TRY(S.up(v, n, &dv));
     FOTO_TRY(S.dev(n, &dout));
-    k_warp<<<ev_blocks(n), EV_NT, 0, S.s>>>(df, dm, du, dv, w, h, dout);
+    k_warp<<<capped_blocks(n, EV_MAX_BLOCKS), EV_NT, 0, S.s>>>(df, dm, du, dv, w, h, dout);
     FOTO_HIP_CHECK(hipGetLastError());
     FOTO_HIP_CHECK(hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, S.s));
     FOTO_HIP_CHECK(hipStreamSynchronize(S.s));
@@ -287,7 +254,7 @@ int foto_warp_dev(const double* f1, const double* u, const double* v, const doub
         return FOTO_ERR_ARG;
     }
     FOTO_TRY(S.init_dev((hipStream_t)stream));
-    k_warp<<<ev_blocks((int64_t)n), EV_NT, 0, S.s>>>(f1, m, u, v, w, h, out);
+    k_warp<<<capped_blocks((int64_t)n, EV_MAX_BLOCKS), EV_NT, 0, S.s>>>(f1, m, u, v, w, h, out);
     FOTO_HIP_CHECK(hipGetLastError());
     return S.leave((hipStream_t)stream);
 }

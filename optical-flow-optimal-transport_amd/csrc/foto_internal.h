@@ -58,6 +58,14 @@ constexpr int NT = 256;  // threads per block for every kernel
 
 inline int march_blocks(const Geo& g) { return ((g.Nx + TX - 1) / TX) * ((g.Ny + TY - 1) / TY); }
 inline int flat_blocks(int64_t n) { return (int)((n + NT - 1) / NT); }
+// at least one block and at most `cap`: the kernel's grid-stride loop takes the rest
+inline int capped_blocks(int64_t items, int cap) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((items + NT - 1) / NT, cap));
+}
+constexpr int STREAM_MAX_BLOCKS = 1 << 16;   // the streaming kernels (ingest, export, render)
+constexpr int SUM_MAX_BLOCKS = 2048;         // launch_sum's partials
+
+inline size_t dtype_bytes(int dtype) { return dtype == FOTO_U8 ? 1 : dtype == FOTO_F32 ? 4 : 8; }
 
 inline int cus_count() {   // CUs of the current device (cached per device ordinal)
     static int cache[64] = {0};
@@ -258,16 +266,14 @@ hipError_t launch_q_from_phi(const Geo& g, const double* phi, const double* mut,
 // trajectory steps n in [n_lo, n_hi) using phi planes (local plane index l = n - t0)
 hipError_t launch_traj(const Geo& g, const double* phi, int n_lo, int n_hi, double* px, double* py,
                        int init, hipStream_t s);
-hipError_t launch_flow_finish(int Nx, int Ny, const double* px, const double* py, double* u, double* v,
-                              double* m, hipStream_t s);
-// One record of the flow path straight from the running positions: k_flow_uv, the -div('D') of
-// launch_flow_finish (same operation order, same -1.0 scale; m from the float64 u, v) and the
-// export in one kernel.  dtype FOTO_F32 | FOTO_F64; layout 0: ou[i], ov[i], om[i] (three planes,
-// anywhere); layout 1: ou[2 i], ou[2 i + 1] = (u, v) (ov, om unused).
+// The flow record of the positions px, py (the final flow and every record of the flow path):
+// u = px - x, v = py - y, m = -div(bc 'D') [u; v] from the float64 u, v, and the export, in one
+// kernel.  dtype FOTO_F32 | FOTO_F64; layout 0: ou[i], ov[i], om[i] (three planes, anywhere);
+// layout 1: ou[2 i], ou[2 i + 1] = (u, v) (ov, om unused).
 hipError_t launch_flow_record(int Nx, int Ny, const double* px, const double* py, void* ou, void* ov, void* om,
                               int dtype, int layout, hipStream_t s);
 
-// Point tracking: trajectory steps n in [n_lo, n_hi) (within g's planes and below Nt - 1) for M
+// Point tracking: launch_traj's steps n in [n_lo, n_hi) (within g's planes and below Nt - 1) for M
 // start points pts[M][2] of FOTO_F32 | FOTO_F64, one launch.  all_steps = 1: record n -> out[n][M][2]
 // (global n: `out` is the base of the whole [Nt-1][M][2] array); 0: the record of step Nt-2 ->
 // out[M][2], stored by the launch that runs that step.  pos_in (null: start at pts) and pos_out
@@ -312,8 +318,7 @@ int track_arg_check(const void* pts, const void* out, int64_t M, int all_steps, 
 int track_dtype_check(const void* p, int dtype, const char* who, const char* what);
 // dst[row * w + col] = (double)pixel(row, col) / divisor
 hipError_t launch_ingest(const foto_image& im, int w, int h, double* dst, hipStream_t s);
-// tot[0] = sum of x[0..n) in a fixed order; part holds sum_blocks(n) doubles
-int sum_blocks(int64_t n);
+// tot[0] = sum of x[0..n) in a fixed order; part holds capped_blocks(n, SUM_MAX_BLOCKS) doubles
 hipError_t launch_sum(int64_t n, const double* x, double* part, double* tot, hipStream_t s);
 hipError_t launch_div_scalar(int64_t n, double* x, const double* S, hipStream_t s);   // x /= S[0]
 // layout 0: out[3][n] = a, b, c; 1: out[n][2] = (a, b); dtype FOTO_F32 | FOTO_F64
@@ -330,7 +335,23 @@ struct FrameArgs {
 // out[count][n] of dtype FOTO_U8 | FOTO_F32 | FOTO_F64, count <= FRAMES_MAX, one launch
 hipError_t launch_frames(const FrameArgs& fa, int count, int64_t n, double scale, void* out, int dtype,
                          hipStream_t s);
-size_t dtype_bytes(int dtype);
+
+// A grow-only device scratch (the holder frees p).  Growing waits for `s` first: an earlier
+// call's launches there may still read the buffer being replaced.
+struct DevScratch {
+    void* p = nullptr;
+    size_t cap = 0;   // bytes
+    int reserve(size_t bytes, hipStream_t s) {
+        if (cap >= bytes) return 0;
+        FOTO_HIP_CHECK(hipStreamSynchronize(s));
+        if (p) FOTO_HIP_CHECK(hipFree(p));
+        p = nullptr;
+        cap = 0;
+        FOTO_HIP_CHECK(hipMalloc(&p, bytes));
+        cap = bytes;
+        return 0;
+    }
+};
 
 // The stream contract of every *_dev call: libfoto's streams are non-blocking, so the caller's
 // stream (NULL: the legacy null stream) and the own one are ordered by two events, made once per

@@ -16,6 +16,7 @@
 //              and re-reading q), r.r partials.
 // Both finish with a last-block reduction (write-through partials + agent-scope ticket,
 // MI355X_MICROARCH.md "Valid forms" row 1): no extra launch per dot product.
+#include "foto_devutil.h"
 #include "foto_internal.h"
 
 namespace foto {
@@ -1162,23 +1163,6 @@ hipError_t launch_grad2_forward(int Nx, int Ny, const double* f, double* gx, dou
 
 // ============================================================================ flow extraction (A13/A14)
 
-// un[n] = G_x phi_n, vn[n] = G_y phi_n (bc 'N': zero on the edge columns / rows).
-__device__ __forceinline__ double un_at(const double* P, int Nx, int yy, int xx) {
-    if (xx == 0 || xx == Nx - 1) return 0.0;
-    return 0.5 * (P[(int64_t)yy * Nx + xx + 1] - P[(int64_t)yy * Nx + xx - 1]);
-}
-__device__ __forceinline__ double vn_at(const double* P, int Nx, int Ny, int yy, int xx) {
-    if (yy == 0 || yy == Ny - 1) return 0.0;
-    return 0.5 * (P[(int64_t)(yy + 1) * Nx + xx] - P[(int64_t)(yy - 1) * Nx + xx]);
-}
-
-__device__ __forceinline__ int trunc_clamp(double v, int hi) {
-    double t = trunc(v);               // int() truncates toward zero
-    if (!(t >= 0.0)) t = 0.0;          // also maps NaN to 0
-    if (t > (double)hi) t = (double)hi;
-    return (int)t;
-}
-
 // reconstructTrajectory (utils.py:44-99) for steps n in [n_lo, n_hi), one thread per pixel.
 __global__ __launch_bounds__(NT) void k_traj(Geo g, const double* __restrict__ phi, int n_lo, int n_hi,
                                              double* __restrict__ px, double* __restrict__ py, int init) {
@@ -1188,18 +1172,7 @@ __global__ __launch_bounds__(NT) void k_traj(Geo g, const double* __restrict__ p
     const int j = (int)(i / Nx), ii = (int)(i - (int64_t)j * Nx);
     double x = init ? (double)ii : px[i];
     double y = init ? (double)j : py[i];
-    for (int n = n_lo; n < n_hi; ++n) {
-        const double* P = phi + (int64_t)(n - g.t0) * g.nxy;
-        const int tx = trunc_clamp(x, Nx - 2), ty = trunc_clamp(y, Ny - 2);
-        const double dX = x - tx, dY = y - ty;
-        const double w1 = (1 - dY) * (1 - dX), w2 = dX * (1 - dY), w3 = dY * dX, w4 = (1 - dX) * dY;
-        const double u00 = un_at(P, Nx, ty, tx), u01 = un_at(P, Nx, ty, tx + 1);
-        const double u11 = un_at(P, Nx, ty + 1, tx + 1), u10 = un_at(P, Nx, ty + 1, tx);
-        const double v00 = vn_at(P, Nx, Ny, ty, tx), v01 = vn_at(P, Nx, Ny, ty, tx + 1);
-        const double v11 = vn_at(P, Nx, Ny, ty + 1, tx + 1), v10 = vn_at(P, Nx, Ny, ty + 1, tx);
-        x += w1 * u00 + w2 * u01 + w3 * u11 + w4 * u10;
-        y += w1 * v00 + w2 * v01 + w3 * v11 + w4 * v10;
-    }
+    for (int n = n_lo; n < n_hi; ++n) traj_step(phi + (int64_t)(n - g.t0) * g.nxy, Nx, Ny, x, y);
     px[i] = x;
     py[i] = y;
 }
@@ -1210,27 +1183,8 @@ hipError_t launch_traj(const Geo& g, const double* phi, int n_lo, int n_hi, doub
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(NT) void k_flow_uv(int Nx, int Ny, const double* __restrict__ px,
-                                                const double* __restrict__ py, double* __restrict__ u,
-                                                double* __restrict__ v) {
-    const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
-    if (i >= (int64_t)Nx * Ny) return;
-    const int j = (int)(i / Nx), ii = (int)(i - (int64_t)j * Nx);
-    u[i] = px[i] - (double)ii;
-    v[i] = py[i] - (double)j;
-}
-
-hipError_t launch_flow_finish(int Nx, int Ny, const double* px, const double* py, double* u, double* v, double* m,
-                              hipStream_t s) {
-    k_flow_uv<<<flat_blocks((int64_t)Nx * Ny), NT, 0, s>>>(Nx, Ny, px, py, u, v);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_div2(Nx, Ny, u, v, m, 1, -1.0, s);   // m = -div(bc 'D') [u; v]
-}
-
-// One record of the flow path: k_flow_uv + k_div2(bc 'D', sign -1.0) + the export.  u, v of the
-// pixel and of its four neighbours are the same subtraction k_flow_uv stores, and the sum runs
-// in k_div2's order, so (u, v, m) carry the bits launch_flow_finish gives for these positions;
+// One flow record from the positions: u = px - x, v = py - y, m = -div(bc 'D') [u; v] (k_div2's
+// sum, sign -1.0; the neighbours' u, v are the same subtractions) and the export, in float64;
 // only the stores round (float32).  LAYOUT 0: three planes; 1: interleaved (u, v).
 template <class T, int LAYOUT>
 __global__ __launch_bounds__(NT) void k_flow_record(int Nx, int Ny, const double* __restrict__ px,
@@ -1274,13 +1228,8 @@ hipError_t launch_flow_record(int Nx, int Ny, const double* px, const double* py
 // ---------------------------------------------------------------------------- point tracking
 // reconstructTrajectory (utils.py:44-99) from arbitrary start points, one thread per point, for
 // the steps n in [n_lo, n_hi) of one base pointer; the position stays in registers (float64)
-// from step to step.  A step is k_traj's: the same trunc_clamp, weights and sum order, and each
-// un / vn the same single subtraction and multiply -- but the 12 distinct phi values it needs
-// (the 4 x 4 neighbourhood of (tx, ty) without its corners; un_at / vn_at issue 16 loads) are
-// loaded once, unconditionally and together, from indices clamped into the plane; what un_at /
-// vn_at return as 0 on an edge column / row is selected afterwards.  tx in [0, Nx-2] and ty in
-// [0, Ny-2] for every x, y (trunc_clamp maps NaN to 0 and clamps +-inf), so every index is inside
-// the plane whatever the point: a non-finite point gives a non-finite record and nothing else.
+// from step to step.  A step is k_traj's (traj_step, foto_devutil.h): every load is inside the
+// plane whatever the point, a non-finite point gives a non-finite record and nothing else.
 // Record n (after step n) is the displacement from the start point, one 16-byte (float64) or
 // 8-byte (float32) store per thread, contiguous across the wave; ALL = 0 stores the record of
 // step Nt-2 only.  pos_in (may be null: the start points) / pos_out (may be null) carry the
@@ -1309,29 +1258,7 @@ __global__ __launch_bounds__(NT) void k_track(Geo g, const double* __restrict__ 
     }
     VO* const rec = reinterpret_cast<VO*>(out);
     for (int n = n_lo; n < n_hi; ++n) {
-        const double* P = phi + (int64_t)(n - g.t0) * g.nxy;
-        const int tx = trunc_clamp(x, Nx - 2), ty = trunc_clamp(y, Ny - 2);
-        const int xm = tx > 0 ? tx - 1 : 0, xp = tx + 2 < Nx ? tx + 2 : Nx - 1;
-        const int ym = ty > 0 ? ty - 1 : 0, yp = ty + 2 < Ny ? ty + 2 : Ny - 1;
-        const double* r0 = P + (int64_t)ty * Nx;
-        const double* r1 = r0 + Nx;
-        const double* rm = P + (int64_t)ym * Nx;
-        const double* rp = P + (int64_t)yp * Nx;
-        // the 12 loads, ahead of their first use
-        const double a0 = r0[xm], b0 = r0[tx], c0 = r0[tx + 1], d0 = r0[xp];
-        const double a1 = r1[xm], b1 = r1[tx], c1 = r1[tx + 1], d1 = r1[xp];
-        const double bm = rm[tx], cm = rm[tx + 1];
-        const double bp = rp[tx], cp = rp[tx + 1];
-        const double dX = x - tx, dY = y - ty;
-        const double w1 = (1 - dY) * (1 - dX), w2 = dX * (1 - dY), w3 = dY * dX, w4 = (1 - dX) * dY;
-        const bool xl = tx == 0, xr = tx + 1 == Nx - 1;   // un is 0 on columns 0 and Nx-1
-        const bool yl = ty == 0, yr = ty + 1 == Ny - 1;   // vn is 0 on rows 0 and Ny-1
-        const double u00 = xl ? 0.0 : 0.5 * (c0 - a0), u01 = xr ? 0.0 : 0.5 * (d0 - b0);
-        const double u11 = xr ? 0.0 : 0.5 * (d1 - b1), u10 = xl ? 0.0 : 0.5 * (c1 - a1);
-        const double v00 = yl ? 0.0 : 0.5 * (b1 - bm), v01 = yl ? 0.0 : 0.5 * (c1 - cm);
-        const double v11 = yr ? 0.0 : 0.5 * (cp - c0), v10 = yr ? 0.0 : 0.5 * (bp - b0);
-        x += w1 * u00 + w2 * u01 + w3 * u11 + w4 * u10;
-        y += w1 * v00 + w2 * v01 + w3 * v11 + w4 * v10;
+        traj_step(phi + (int64_t)(n - g.t0) * g.nxy, Nx, Ny, x, y);
         if (ALL || n == g.Nt - 2) {
             VO r;
             r.x = (TO)(x - x0);

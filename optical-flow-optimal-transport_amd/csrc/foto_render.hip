@@ -11,9 +11,9 @@
 //                   float64, the per-record maximum radius by a block reduction and one vector
 //                   atomic max per block on the bit pattern of the non-negative double.
 //
-// The warp arithmetic is k_warp's (foto_eval.hip), operation for operation, on flow values
-// widened exactly to double and on (double)pixel / divisor; built with -ffp-contract=off like
-// every other unit.  A thread owns one output pixel of one record and loops over the channels: the
+// The warp arithmetic is k_warp's (foto_eval.hip): both call warp_taps and warp_sum of
+// foto_devutil.h, here on flow values widened exactly to double and on (double)pixel / divisor;
+// built with -ffp-contract=off like every other unit.  A thread owns one output pixel of one record and loops over the channels: the
 // weights and the four clamped taps are computed once per pixel and record.  Flow loads are
 // coalesced along x, the source taps are gathers, a wave's stores cover one contiguous span.  (Two
 // forms of a packed uint8 store, 4 pixels per thread into 32-bit words, measured slower than this
@@ -30,16 +30,12 @@
 #include <mutex>
 #include <vector>
 
+#include "foto_devutil.h"
 #include "foto_internal.h"
 
 namespace foto {
 
 namespace {
-
-// capped like stream_blocks (foto_dev.hip); the grid-stride loops take the rest
-int render_blocks(int64_t items) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((items + NT - 1) / NT, 1 << 16));
-}
 
 // a / b for 0 <= a, 0 < b; small (uniform): both fit 32 bits, where the division is a fraction
 // of the 64-bit one
@@ -108,70 +104,39 @@ template <> struct SrcValue<unsigned char> {
 };
 static_assert(NT == 256, "the uint8 table has one entry per thread");
 
-// One output pixel's share of k_warp (foto_eval.hip) that does not depend on the channel: the
-// four weights, the four clamped taps as element offsets into a channel, and 1 + m at the taps.
-struct Taps {
-    double w1, w2, w3, w4;
+// One output pixel's share of the warp that does not depend on the channel: the shared weights
+// and clamped taps (warp_taps, foto_devutil.h: k_warp's), the taps as element offsets into a
+// channel, and 1 + m at the taps.
+struct PixelTaps {
+    WarpTaps T;
     int64_t q1, q2, q3, q4;
-    double f1, f2, f3, f4;
+    double g1, g2, g3, g4;
 };
 
 template <class Tf, int LAYOUT>
-__device__ __forceinline__ Taps warp_taps(const Tf* __restrict__ flow, int64_t n, int w, int h, int64_t t, bool small,
-                                          int64_t sy, int64_t sx, bool scale) {
+__device__ __forceinline__ PixelTaps pixel_taps(const Tf* __restrict__ flow, int64_t n, int w, int h, int64_t t,
+                                                bool small, int64_t sy, int64_t sx, bool scale) {
     const int64_t k = idiv(t, n, small), p = t - k * n;
     const Tf* __restrict__ rec = flow + k * (LAYOUT == 0 ? 3 : 2) * n;
     double u, v;
     load_uv<Tf, LAYOUT>(rec, n, p, u, v);
-    // k_warp, operation for operation
     const int64_t row = idiv(p, w, small);
-    const int i = (int)row, j = (int)(p - row * w);   // row, column
-    double ti = (double)i - v, tj = (double)j - u;
-    const double dI = ti - trunc(ti), dJ = tj - trunc(tj);
-    Taps T;
-    T.w1 = (1 - dI) * (1 - dJ);
-    T.w2 = dJ * (1 - dI);
-    T.w3 = dI * dJ;
-    T.w4 = (1 - dJ) * dI;
-    if (ti >= h) ti = h - 1;
-    if (tj >= w) tj = w - 1;
-    if (ti < 0) ti = 0;
-    if (tj < 0) tj = 0;
-    // a NaN displacement: the weights are NaN, so is the pixel; its taps stay in the frame
-    if (ti != ti) ti = 0;
-    if (tj != tj) tj = 0;
-    const int64_t a = (int64_t)ti, b = (int64_t)tj;
-    const int64_t a1 = (a < h - 1) ? a + 1 : a, b1 = (b < w - 1) ? b + 1 : b;
-    T.q1 = a * sy + b * sx;
-    T.q2 = a * sy + b1 * sx;
-    T.q3 = a1 * sy + b1 * sx;
-    T.q4 = a1 * sy + b * sx;
-    T.f1 = T.f2 = T.f3 = T.f4 = 1;
+    PixelTaps P;
+    P.T = warp_taps((int)row, (int)(p - row * w), u, v, w, h);
+    const int64_t a = P.T.a, b = P.T.b, a1 = P.T.a1, b1 = P.T.b1;
+    P.q1 = a * sy + b * sx;
+    P.q2 = a * sy + b1 * sx;
+    P.q3 = a1 * sy + b1 * sx;
+    P.q4 = a1 * sy + b * sx;
+    P.g1 = P.g2 = P.g3 = P.g4 = 1;
     if (LAYOUT == 0 && scale) {
         const Tf* __restrict__ m = rec + 2 * n;
-        T.f1 = 1 + (double)m[a * w + b];
-        T.f2 = 1 + (double)m[a * w + b1];
-        T.f3 = 1 + (double)m[a1 * w + b1];
-        T.f4 = 1 + (double)m[a1 * w + b];
+        P.g1 = 1 + (double)m[a * w + b];
+        P.g2 = 1 + (double)m[a * w + b1];
+        P.g3 = 1 + (double)m[a1 * w + b1];
+        P.g4 = 1 + (double)m[a1 * w + b];
     }
-    return T;
-}
-
-// clip(w1 F1 + w2 F2 + w3 F3 + w4 F4, 0, 1), F = (1 + m) f1 or f1, in k_warp's order
-__device__ __forceinline__ double warp_sum(const Taps& T, double s1, double s2, double s3, double s4, bool scale) {
-    double x;
-    if (scale) {
-        x = T.w1 * (T.f1 * s1);
-        x = x + T.w2 * (T.f2 * s2);
-        x = x + T.w3 * (T.f3 * s3);
-        x = x + T.w4 * (T.f4 * s4);
-    } else {
-        x = T.w1 * s1;
-        x = x + T.w2 * s2;
-        x = x + T.w3 * s3;
-        x = x + T.w4 * s4;
-    }
-    return clip01(x);
+    return P;
 }
 
 // out[records][h][w][C] = cast(clip(apply_opticalflow(src_c / divisor, u_k, v_k, w, h, m_k), 0, 1))
@@ -185,11 +150,13 @@ __global__ __launch_bounds__(NT) void k_render_warp(const Ts* __restrict__ src, 
     const int64_t n = (int64_t)w * h, T = R * n;
     const bool small = T <= 0xffffffffLL, scale = LAYOUT == 0 && use_m;
     for (int64_t t = (int64_t)blockIdx.x * NT + threadIdx.x; t < T; t += (int64_t)gridDim.x * NT) {
-        const Taps tp = warp_taps<Tf, LAYOUT>(flow, n, w, h, t, small, sy, sx, scale);
+        const PixelTaps tp = pixel_taps<Tf, LAYOUT>(flow, n, w, h, t, small, sy, sx, scale);
         for (int c = 0; c < C; ++c) {
             const Ts* __restrict__ sp = src + (int64_t)c * sc;
-            const double x = warp_sum(tp, val(sp[tp.q1]), val(sp[tp.q2]), val(sp[tp.q3]), val(sp[tp.q4]), scale);
-            out[t * C + c] = out_cast<To>(x);
+            const double s1 = val(sp[tp.q1]), s2 = val(sp[tp.q2]), s3 = val(sp[tp.q3]), s4 = val(sp[tp.q4]);
+            const double x = scale ? warp_sum(tp.T, tp.g1, tp.g2, tp.g3, tp.g4, s1, s2, s3, s4)
+                                   : warp_sum(tp.T, s1, s2, s3, s4);
+            out[t * C + c] = out_cast<To>(clip01(x));
         }
     }
 }
@@ -318,8 +285,6 @@ __global__ __launch_bounds__(NT) void k_render_color(const Tf* __restrict__ flow
 
 // ----------------------------------------------------------------------------- host side
 
-size_t esize(int dtype) { return dtype_bytes(dtype); }
-
 int flow_check(const foto_flow* fl, int w, int h, const char* who) {
     if (!fl) { set_error("%s: null flow descriptor", who); return FOTO_ERR_ARG; }
     if (w < 1 || h < 1) { set_error("%s: w = %d, h = %d: both must be >= 1", who, w, h); return FOTO_ERR_ARG; }
@@ -333,15 +298,15 @@ int flow_check(const foto_flow* fl, int w, int h, const char* who) {
         return FOTO_ERR_ARG;
     }
     if (fl->records < 1) { set_error("%s: flow records = %d must be >= 1", who, fl->records); return FOTO_ERR_ARG; }
-    if ((uintptr_t)fl->data % esize(fl->dtype) != 0) {
-        set_error("%s: flow data %p is not aligned to its %zu-byte element", who, fl->data, esize(fl->dtype));
+    if ((uintptr_t)fl->data % dtype_bytes(fl->dtype) != 0) {
+        set_error("%s: flow data %p is not aligned to its %zu-byte element", who, fl->data, dtype_bytes(fl->dtype));
         return FOTO_ERR_ARG;
     }
     return 0;
 }
 
 size_t flow_bytes(const foto_flow* fl, int w, int h) {
-    return (size_t)fl->records * (fl->layout == 0 ? 3 : 2) * (size_t)w * (size_t)h * esize(fl->dtype);
+    return (size_t)fl->records * (fl->layout == 0 ? 3 : 2) * (size_t)w * (size_t)h * dtype_bytes(fl->dtype);
 }
 
 bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
@@ -351,13 +316,11 @@ bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
 
 // One stream, link and maxrad scratch per device, kept for the process like the EvSlots of
 // foto_eval.hip.  The calls only enqueue: the stream is never handed back to the pool, so nothing
-// waits on the host.  The scratch grows only; hipFree waits for the launches that still read the
-// old one.
+// waits on the host (but a scratch that has to grow).
 struct RenderDev {
     hipStream_t s = nullptr;
     StreamLink link;
-    double* mr = nullptr;
-    size_t cap = 0;   // doubles
+    DevScratch mr;   // one double per record
 };
 std::mutex rd_mu;
 std::vector<RenderDev*> rd_dev;
@@ -378,18 +341,6 @@ int render_dev(int* device, RenderDev** out) {
     return 0;
 }
 
-int maxrad_scratch(RenderDev* rd, size_t n) {
-    if (rd->cap >= n) return 0;
-    if (rd->mr) FOTO_HIP_CHECK(hipFree(rd->mr));
-    rd->mr = nullptr;
-    rd->cap = 0;
-    void* b = nullptr;
-    FOTO_HIP_CHECK(hipMalloc(&b, n * sizeof(double)));
-    rd->mr = (double*)b;
-    rd->cap = n;
-    return 0;
-}
-
 struct WarpArgs {
     const foto_image* src;
     int C;
@@ -403,7 +354,7 @@ struct WarpArgs {
 
 template <class Ts, class Tf, class To, int LAYOUT>
 void warp1_launch(const WarpArgs& a, int64_t T) {
-    k_render_warp<Ts, Tf, To, LAYOUT><<<render_blocks(T), NT, 0, a.s>>>(
+    k_render_warp<Ts, Tf, To, LAYOUT><<<capped_blocks(T, STREAM_MAX_BLOCKS), NT, 0, a.s>>>(
         (const Ts*)a.src->data, a.src->stride_y, a.src->stride_x, a.sc, a.src->divisor, a.C, (const Tf*)a.fl->data,
         a.fl->records, a.w, a.h, a.use_m, (To*)a.out);
 }
@@ -432,11 +383,12 @@ void warp_launch(const WarpArgs& a) {
 template <class Tf>
 void lum_launch(const foto_flow* fl, int64_t n, void* out, hipStream_t s) {
     const int64_t T = (int64_t)fl->records * n;
+    const Tf* f = (const Tf*)fl->data;
+    unsigned char* o = (unsigned char*)out;
     if ((uintptr_t)out % 4 == 0)
-        k_render_lum<Tf, 4><<<render_blocks((T + 3) / 4), NT, 0, s>>>((const Tf*)fl->data, fl->records, n,
-                                                                     (unsigned char*)out);
+        k_render_lum<Tf, 4><<<capped_blocks((T + 3) / 4, STREAM_MAX_BLOCKS), NT, 0, s>>>(f, fl->records, n, o);
     else
-        k_render_lum<Tf, 1><<<render_blocks(T), NT, 0, s>>>((const Tf*)fl->data, fl->records, n, (unsigned char*)out);
+        k_render_lum<Tf, 1><<<capped_blocks(T, STREAM_MAX_BLOCKS), NT, 0, s>>>(f, fl->records, n, o);
 }
 
 template <class Tf, int LAYOUT>
@@ -452,7 +404,8 @@ void color_launch(const foto_flow* fl, int64_t n, double maxmotion, double* mr, 
         }
     }
     k_maxrad_final<<<(unsigned)((R + NT - 1) / NT), NT, 0, s>>>(R, maxmotion, mr);
-    k_render_color<Tf, LAYOUT><<<render_blocks(T), NT, 0, s>>>((const Tf*)fl->data, R, n, mr, (unsigned char*)out);
+    k_render_color<Tf, LAYOUT><<<capped_blocks(T, STREAM_MAX_BLOCKS), NT, 0, s>>>((const Tf*)fl->data, R, n, mr,
+                                                                                  (unsigned char*)out);
 }
 
 }  // namespace
@@ -475,7 +428,7 @@ int foto_render_warp_dev(const foto_image* src, int channels, int64_t stride_c, 
         return FOTO_ERR_ARG;
     }
     FOTO_TRY(image_check(src, w, h, who));
-    const size_t es = esize(src->dtype);
+    const size_t es = dtype_bytes(src->dtype);
     for (int c = 1; c < channels; ++c) {   // (the alignment and the strides are those of channel 0)
         foto_image ch = *src;
         ch.data = (const char*)src->data + (size_t)c * (size_t)stride_c * es;
@@ -491,8 +444,8 @@ int foto_render_warp_dev(const foto_image* src, int channels, int64_t stride_c, 
         set_error("%s: out_dtype %d is not FOTO_U8 / FOTO_F32 / FOTO_F64", who, out_dtype);
         return FOTO_ERR_ARG;
     }
-    if ((uintptr_t)out % esize(out_dtype) != 0) {
-        set_error("%s: out %p is not aligned to its %zu-byte element", who, out, esize(out_dtype));
+    if ((uintptr_t)out % dtype_bytes(out_dtype) != 0) {
+        set_error("%s: out %p is not aligned to its %zu-byte element", who, out, dtype_bytes(out_dtype));
         return FOTO_ERR_ARG;
     }
     // ---- the pointer queries, before anything is enqueued
@@ -503,7 +456,7 @@ int foto_render_warp_dev(const foto_image* src, int channels, int64_t stride_c, 
     const size_t last = (size_t)(h - 1) * (size_t)src->stride_y + (size_t)(w - 1) * (size_t)src->stride_x +
                         (size_t)(channels - 1) * (size_t)stride_c;
     const size_t src_bytes = (last + 1) * es, fl_bytes = flow_bytes(fl, w, h);
-    const size_t out_bytes = (size_t)fl->records * (size_t)w * (size_t)h * (size_t)channels * esize(out_dtype);
+    const size_t out_bytes = (size_t)fl->records * (size_t)w * (size_t)h * (size_t)channels * dtype_bytes(out_dtype);
     FOTO_TRY(image_dev_check(src, w, h, device, who));
     FOTO_TRY(dev_ptr_check(src->data, src_bytes, device, who, "image data (all channels)"));
     FOTO_TRY(dev_ptr_check(fl->data, fl_bytes, device, who, "flow data"));
@@ -577,8 +530,8 @@ int foto_render_color_dev(const foto_flow* fl, int w, int h, double maxmotion, v
     }
     double* mr = maxrad_or_null;
     if (!mr) {
-        FOTO_TRY(maxrad_scratch(rd, (size_t)fl->records));
-        mr = rd->mr;
+        FOTO_TRY(rd->mr.reserve(mr_bytes, rd->s));
+        mr = (double*)rd->mr.p;
     }
     FOTO_TRY(rd->link.enter((hipStream_t)stream, rd->s));
     FOTO_HIP_CHECK(hipMemsetAsync(mr, 0, mr_bytes, rd->s));

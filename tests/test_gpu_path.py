@@ -4,9 +4,9 @@ foto_flow_path_from_phi; BBSolver.frames / frames_device / flow_path / flow_path
 Bars.  Against the reference (the CPU oracle's flow_from_phi on the first n + 1 planes of the
 golden phi): test_flow's rtol 1e-13 / atol 1e-12.  Everything else compares entries of this build
 with each other and is bit for bit (np.array_equal on the integer view): the path runs k_traj one
-step at a time from the stored positions and finishes each record with k_flow_uv's subtraction and
-k_div2's sum, so its last record has foto_bb_flow's bits by construction; an integer frame
-position with scale 1 copies the plane.  A fractional position is one rounding of 1 - w, two
+step at a time from the stored positions and finishes each record with k_flow_record, the kernel
+that finishes foto_bb_flow's, so its last record has foto_bb_flow's bits by construction; an
+integer frame position with scale 1 copies the plane.  A fractional position is one rounding of 1 - w, two
 products and one sum, at most 4 half-ulps of the largest term with or without FMA contraction:
 |got - ((1 - w) a + w b)| <= 2^-50 max(|a|, |b|).
 
@@ -107,26 +107,45 @@ def solved(name):
 
 # ------------------------------------------------------------------ 1. the reference's fixture
 
+def _records_match_oracle(phi, Nt, Nx, Ny, label):
+    """Record n - 1 of foto_flow_path_from_phi against the oracle's flow of the first n + 1
+    planes; the last record has foto_flow_from_phi's bits.  Returns the records."""
+    u, v, m = ops.flow_path_from_phi(phi, Nt, Nx, Ny)
+    assert u.shape == v.shape == m.shape == (Nt - 1, Nx * Ny)
+    for n in range(1, Nt):
+        ref = O.flow_from_phi(phi[:(n + 1) * Nx * Ny], n + 1, Nx, Ny)
+        for got, want, name in zip((u, v, m), ref, "uvm"):
+            assert np.isfinite(want).all()
+            err = np.abs(got[n - 1] - want).max()
+            print(f"{label} ({Nt}x{Ny}x{Nx}) record {n - 1} {name}: max |diff| {err:.3e}")
+            np.testing.assert_allclose(got[n - 1], want, rtol=1e-13, atol=1e-12)
+    for got, want in zip((u, v, m), ops.flow_from_phi(phi, Nt, Nx, Ny)):
+        assert same(got[-1], want)
+    return u, v, m
+
+
 def test_path_from_phi_golden(gold):
-    """Record n - 1 of foto_flow_path_from_phi against the oracle's flow of the first n + 1 planes
-    (every intermediate step of the four cases has positions outside the frame: truncation, clamp
-    and extrapolation); the last record has foto_flow_from_phi's bits.  Case 2 has one record."""
+    """Every intermediate step of the four cases has positions outside the frame: truncation,
+    clamp and extrapolation.  Case 2 has one record."""
     d = gold("flow.npz")
     for f in range(4):
         Nt, Ny, Nx = (int(s) for s in d[f"f{f}_shape"])
-        phi = d[f"f{f}_phi"]
-        u, v, m = ops.flow_path_from_phi(phi, Nt, Nx, Ny)
-        assert u.shape == v.shape == m.shape == (Nt - 1, Nx * Ny)
-        for n in range(1, Nt):
-            ref = O.flow_from_phi(phi[:(n + 1) * Nx * Ny], n + 1, Nx, Ny)
-            for got, want, name in zip((u, v, m), ref, "uvm"):
-                err = np.abs(got[n - 1] - want).max()
-                print(f"case {f} ({Nt}x{Ny}x{Nx}) record {n - 1} {name}: max |diff| {err:.3e}")
-                np.testing.assert_allclose(got[n - 1], want, rtol=1e-13, atol=1e-12)
-        for got, want in zip((u, v, m), ops.flow_from_phi(phi, Nt, Nx, Ny)):
-            assert same(got[-1], want)
-        for got, want, key in zip((u, v, m), "uvm", "uvm"):
+        uvm = _records_match_oracle(d[f"f{f}_phi"], Nt, Nx, Ny, f"case {f}")
+        for got, key in zip(uvm, "uvm"):
             np.testing.assert_allclose(got[-1], d[f"f{f}_{key}"], rtol=1e-13, atol=1e-12)
+
+
+# (Nt, Nx, Ny): two columns / two rows -- every un / vn tap is an edge zero on that axis, both
+# edge selections fall on adjacent taps and both extra loads of the step are clamped
+NARROW = [(3, 2, 5), (3, 5, 2), (4, 3, 2)]
+
+
+@pytest.mark.parametrize("Nt,Nx,Ny", NARROW)
+def test_path_from_phi_narrow(Nt, Nx, Ny):
+    """The trajectory step on the narrowest grids, anchored to the reference (random-normal phi:
+    positions leave the frame at once)."""
+    phi = np.random.default_rng(1000 * Nt + 10 * Nx + Ny).standard_normal(Nt * Nx * Ny)
+    _records_match_oracle(phi, Nt, Nx, Ny, "narrow")
 
 
 # ------------------------------------------------------------------ 2. the path on a context

@@ -276,9 +276,10 @@ def test_warp_other_channel_counts(w, h, C):
 @pytest.mark.parametrize("w,h", GRIDS)
 def test_warp_equals_warp_dev(w, h):
     """float64 output with one channel = np.clip(foto_warp_dev) on the same float64 data, value for
-    value.  (Without the NaN displacement: k_warp has no in-frame tap for it.)"""
+    value, the NaN displacement included: both kernels call one tap function, which keeps its
+    taps in the frame, and both give a NaN pixel there."""
     R = 4
-    f = np.nan_to_num(warp_flow(w, h, R), nan=0.25)
+    f = warp_flow(w, h, R)
     src, vals, kw, _ = source("padded_f64", 1, w, h)
     f1 = DeviceArray.from_numpy(np.ascontiguousarray(vals[:, :, 0]))
     fl = flow_device(f, w, h, "float64", "planar")

@@ -14,7 +14,8 @@ itself is nan in the checker and here alike).  For those records the library mus
 non-finite record; every record the checker does produce is compared at the bar above.
 
 Everything else compares entries of this build with each other, bit for bit (np.array_equal on
-the integer view): the step of k_track is k_traj's operation for operation.
+the integer view): k_track and k_traj call one step function (traj_step, foto_devutil.h), so
+these comparisons hold by construction and guard against the two being separated again.
 """
 import ctypes
 import importlib.util
@@ -143,6 +144,13 @@ def test_pixel_centres_equal_flow_path(gold):
         _centres_equal_flow_path(d[f"f{f}_phi"], Nt, Nx, Ny)
     # 2 x 2 x 2: tx and ty clamp to 0, every un / vn is an edge zero
     _centres_equal_flow_path(np.random.default_rng(5).standard_normal(8), 2, 2, 2)
+
+
+# test_gpu_path.NARROW: both edge selections on adjacent taps, both extra loads clamped
+@pytest.mark.parametrize("Nt,Nx,Ny", [(3, 2, 5), (3, 5, 2), (4, 3, 2)])
+def test_pixel_centres_equal_flow_path_narrow(Nt, Nx, Ny):
+    phi = np.random.default_rng(1000 * Nt + 10 * Nx + Ny).standard_normal(Nt * Nx * Ny)
+    _centres_equal_flow_path(phi, Nt, Nx, Ny)
 
 
 # ------------------------------------------------------------------ 3. block edges

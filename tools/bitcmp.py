@@ -11,13 +11,33 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "optical-flow-optimal-transport_amd"))
 if sys.argv[1] == "cmp":
     a, b = np.load(sys.argv[2]), np.load(sys.argv[3])
-    same = all(np.array_equal(a[k], b[k]) for k in a.files)
-    print("bit-identical" if same else "DIFFERENT", {k: float(np.max(np.abs(a[k] - b[k]))) for k in a.files})
+    same = sorted(a.files) == sorted(b.files) and all(np.array_equal(a[k], b[k]) for k in a.files)
+    print("bit-identical" if same else "DIFFERENT",
+          {k: float(np.max(np.abs(a[k].astype(np.float64) - b[k]))) for k in a.files if k in b.files})
     sys.exit(0 if same else 1)
+from foto import evaluate, render  # noqa: E402
 from foto.bb import BBSolver  # noqa: E402
+from foto.device import DeviceArray  # noqa: E402
 from foto.synthetic import translating_gaussian  # noqa: E402
 Nt, Nx, Ny, iters, vr = (int(v) for v in (sys.argv[3:8] + ["32", "640", "480", "6", "1"][len(sys.argv[3:8]):]))
 rho0, rhoT = translating_gaussian(Nx, Ny)
 with BBSolver(rho0, rhoT, Nt, Nx, Ny, r=1.0, reg_epsilon=1e-2, cg_mode=3, virtual_ranks=vr) as s:
     s.iterate(iters, 0.0, stop_rules=False)
-    np.savez(sys.argv[2], cg=np.array(s.cg_its), crit=np.array(s.crit), phi=s.phi())
+    out = dict(cg=np.array(s.cg_its), crit=np.array(s.crit), phi=s.phi())
+    # the flow outputs of the solved context (finite flows, finite starts in and around the frame)
+    u, v, m = s.flow()
+    assert all(np.isfinite(x).all() for x in (u, v, m))
+    out.update(u=u, v=v, m=m)
+    out["path_f32_interleaved"] = s.flow_path_device(dtype="float32", layout="interleaved").to_numpy()
+    out["path_f64_planar"] = s.flow_path_device(dtype="float64", layout="planar").to_numpy()
+    rng = np.random.default_rng(7)
+    pts = np.stack([rng.uniform(-3, Nx + 2, 4096), rng.uniform(-3, Ny + 2, 4096)], axis=1)
+    out["track_f64"] = s.track_device(DeviceArray.from_numpy(pts), dtype="float64").to_numpy()
+    out["track_f32"] = s.track_device(DeviceArray.from_numpy(pts.astype(np.float32)), dtype="float32").to_numpy()
+    frame = rng.uniform(0, 1, Nx * Ny)
+    out["warp_m"] = evaluate.warp(frame, u, v, Nx, Ny, m)
+    out["warp"] = evaluate.warp(frame, u, v, Nx, Ny)
+    src, fl = DeviceArray.from_numpy(frame.reshape(Ny, Nx)), s.flow_device(dtype="float64")
+    out["render_u8"] = render.reconstruct(src, fl, dtype="uint8").to_numpy()
+    out["render_f64"] = render.reconstruct(src, fl, dtype="float64").to_numpy()
+    np.savez(sys.argv[2], **out)

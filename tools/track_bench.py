@@ -2,8 +2,9 @@
 
 Dense:  M = Nx * Ny pixel centres, all steps, float32 -- against flow_path_device(layout=
         "interleaved", dtype="float32") of the same context, which produces the same numbers with
-        two launches (k_traj + k_flow_record) and 16 loads per step.  The two results are compared
-        bit for bit before anything is timed.
+        two launches per step (k_traj + k_flow_record) and the positions through memory between
+        them; the step itself, 12 loads, is the one function both kernels call.  The two results
+        are compared bit for bit before anything is timed.
 Sparse: M = 1 (what a call costs before its points do), M = 1024 and M = 10^6 random in-frame
         points, and the 10^6 sorted by the pixel they start in; all steps and last-only,
         microseconds per call; at 10^6 the effective bytes as well: per step one 8 B / point
