@@ -87,12 +87,13 @@ int stream_device(hipStream_t s) {
 
 // ----------------------------------------------------------------------------- shards
 
-struct Shard {
-    Geo g{};
-    int rank = 0;
-    // fields: halo-padded planes (l = -1 .. nloc), pointers at local plane 0
+// The pointers an outer iteration rotates: which buffer holds the current mu, phi and the fused
+// prox's pair.  One record, so the snapshot an enqueued iteration keeps (foto_bb_ctx::Enq), the
+// rollback that restores it and the completed iteration's state the exports read (Completed) are
+// whole-record assignments: a pointer added here is in all of them.
+// (fields: halo-padded planes (l = -1 .. nloc), pointers at local plane 0)
+struct Rot {
     double* mu[3] = {nullptr, nullptr, nullptr};
-    double* q[3] = {nullptr, nullptr, nullptr};
     double* nu[3] = {nullptr, nullptr, nullptr};   // second mu buffer of the fused prox + RHS
     double* xi[3] = {nullptr, nullptr, nullptr};   // third mu buffer (two outer iterations in flight)
     double* phi = nullptr;   // CG iterate x (two halo planes per side: the fused prox reads them)
@@ -100,6 +101,13 @@ struct Shard {
     // the last fused prox + RHS launch's mu in / out (fz_src is the mu stepB of phi used)
     double* fz_src[3] = {nullptr, nullptr, nullptr};
     double* fz_dst[3] = {nullptr, nullptr, nullptr};
+};
+
+struct Shard : Rot {
+    Geo g{};
+    int rank = 0;
+    Rot& rot() { return *this; }
+    double* q[3] = {nullptr, nullptr, nullptr};
     // sharded fused prox with deferred edges: w_t next to the slab edges (halo-padded) and the
     // edge planes' (w_x, w_y, mu'_t, q_t), slot 0 = plane 0, slot 1 = plane nloc - 1
     double* wt = nullptr;
@@ -117,26 +125,38 @@ struct Shard {
     double* gath = nullptr;  // [0,W) rr | [W,2W) pap | [2W,4W) crit num/den
     CGScal* S = nullptr;
     std::vector<void*> allocs;
+    // the buffers a new context starts from zero in, as allocated: foto_bb_reset zeroes this list
+    // again (rezero), so it cannot miss one
+    std::vector<std::pair<void*, size_t>> zeroed;   // (base, bytes)
     std::unique_ptr<SpectralPlan> spec;
 
     double* gath_rr() { return gath; }
     double* gath_pap(int W) { return gath + W; }
     double* gath_crit(int W) { return gath + 2 * W; }
 
-    int alloc(size_t bytes, void** out) {
-        FOTO_HIP_CHECK(hipMalloc(out, bytes));
+    template <class T>
+    int alloc(size_t bytes, T** out) {
+        FOTO_HIP_CHECK(hipMalloc((void**)out, bytes));
         allocs.push_back(*out);
         return 0;
     }
-    // (nloc + 2 h) planes (h halo planes per side), zeroed on the context's stream: a hipMemset
-    // (null stream) is not ordered with the non-blocking stream the kernels run on -- it raced
-    // with k_init_mu
+    // zeroed on the context's stream: a hipMemset (null stream) is not ordered with the
+    // non-blocking stream the kernels run on -- it raced with k_init_mu
+    template <class T>
+    int alloc_zeroed(size_t bytes, T** out, hipStream_t st) {
+        FOTO_TRY(alloc(bytes, out));
+        FOTO_HIP_CHECK(hipMemsetAsync(*out, 0, bytes, st));
+        zeroed.push_back({*out, bytes});
+        return 0;
+    }
+    // (nloc + 2 h) planes (h halo planes per side)
     int alloc_field(double** out, hipStream_t st, int h = 1) {
-        void* b = nullptr;
-        const size_t n = (size_t)(g.nloc + 2 * h) * (size_t)g.nxy;
-        FOTO_TRY(alloc(n * sizeof(double), &b));
-        FOTO_HIP_CHECK(hipMemsetAsync(b, 0, n * sizeof(double), st));
-        *out = (double*)b + (size_t)h * g.nxy;
+        FOTO_TRY(alloc_zeroed((size_t)(g.nloc + 2 * h) * (size_t)g.nxy * sizeof(double), out, st));
+        *out += (size_t)h * g.nxy;
+        return 0;
+    }
+    int rezero(hipStream_t st) {
+        for (const auto& z : zeroed) FOTO_HIP_CHECK(hipMemsetAsync(z.first, 0, z.second, st));
         return 0;
     }
     ~Shard() {
@@ -193,13 +213,7 @@ struct foto_bb_ctx {
         int its = 0, info = 0;         // a synchronous solve's result
         size_t kmark = 0;              // KTimer mark before its launches
         // host state before it (restored by a rollback)
-        double* mu[3];
-        double* nu[3];
-        double* xi[3];
-        double* phi;
-        double* phi_alt;
-        double* fz_src[3];
-        double* fz_dst[3];
+        Rot before;                    // shard 0's rotating pointers
         bool f_ready;
         int hpar;
         bool pev;                      // phase events recorded (ph[par][0..3])
@@ -380,9 +394,7 @@ static int load_rho(foto_bb_ctx* c, Shard& s, const RhoSrc& src) {
     FOTO_HIP_CHECK(launch_ingest(*src.iT, c->Nx, c->Ny, s.rhoT, c->s));
     if (src.normalize) {   // each frame over its own sum (main.py:71-74), the sum in a fixed order
         if (!c->nrm) {
-            void* b = nullptr;
-            FOTO_TRY(s.alloc(sizeof(double) * (2 + (size_t)capped_blocks(nxy, SUM_MAX_BLOCKS)), &b));
-            c->nrm = (double*)b;
+            FOTO_TRY(s.alloc(sizeof(double) * (2 + (size_t)capped_blocks(nxy, SUM_MAX_BLOCKS)), &c->nrm));
         }
         double* const rho[2] = {s.rho0, s.rhoT};
         for (int k = 0; k < 2; ++k) {
@@ -390,6 +402,32 @@ static int load_rho(foto_bb_ctx* c, Shard& s, const RhoSrc& src) {
             FOTO_HIP_CHECK(launch_div_scalar(nxy, rho[k], c->nrm + k, c->s));
         }
         FOTO_HIP_CHECK(hipMemcpyAsync(c->hsum, c->nrm, 2 * sizeof(double), hipMemcpyDeviceToHost, c->s));
+    }
+    return 0;
+}
+
+// what ctx_init and bb_reset end a shard's setup with: the densities, then mu and q from them
+static int init_fields(foto_bb_ctx* c, Shard& s, const RhoSrc& src) {
+    FOTO_TRY(load_rho(c, s, src));
+    FOTO_HIP_CHECK(launch_init_mu(s.g, s.rho0, s.rhoT, s.mu[0], s.mu[1], s.mu[2], s.q[0], s.q[1], s.q[2], c->s));
+    return 0;
+}
+
+// the _dev entries' source, and what they do once the context's stream has read it (create and
+// reset both end with a stream synchronise: the sums are on the host)
+static RhoSrc dev_src(const foto_image* f0, const foto_image* f1, int normalize, void* stream) {
+    RhoSrc src;
+    src.i0 = f0;
+    src.iT = f1;
+    src.normalize = normalize != 0;
+    src.user = (hipStream_t)stream;
+    return src;
+}
+static int dev_src_done(foto_bb_ctx* c, const RhoSrc& src, double* sums2_or_null) {
+    FOTO_TRY(c->link.leave(c->s, src.user));
+    if (sums2_or_null) {
+        sums2_or_null[0] = src.normalize ? c->hsum[0] : 1.0;
+        sums2_or_null[1] = src.normalize ? c->hsum[1] : 1.0;
     }
     return 0;
 }
@@ -457,33 +495,21 @@ static int ctx_init(foto_bb_ctx* c, const RhoSrc& src) {
         }
         if (c->fuse && W > 1) {
             FOTO_TRY(s.alloc_field(&s.wt, c->s));
-            void* eb = nullptr;
-            FOTO_TRY(s.alloc(sizeof(double) * 8 * nxy, &eb));
-            FOTO_HIP_CHECK(hipMemsetAsync(eb, 0, sizeof(double) * 8 * nxy, c->s));
-            s.edge = (double*)eb;
+            FOTO_TRY(s.alloc_zeroed(sizeof(double) * 8 * nxy, &s.edge, c->s));
         }
         FOTO_TRY(s.alloc_field(&s.phi, c->s, 2));
         FOTO_TRY(s.alloc_field(&s.rv, c->s));
         FOTO_TRY(s.alloc_field(&s.p[0], c->s));
         FOTO_TRY(s.alloc_field(&s.p[1], c->s));
-        void* b;
-        FOTO_TRY(s.alloc(nxy * sizeof(double), &b)); s.rho0 = (double*)b;
-        FOTO_TRY(s.alloc(nxy * sizeof(double), &b)); s.rhoT = (double*)b;
-        FOTO_TRY(s.alloc(nxy * sizeof(double), &b)); s.px = (double*)b;
-        FOTO_TRY(s.alloc(nxy * sizeof(double), &b)); s.py = (double*)b;
-        FOTO_TRY(s.alloc(nxy * sizeof(double), &b)); s.fu = (double*)b;
-        FOTO_TRY(s.alloc(nxy * sizeof(double), &b)); s.fv = (double*)b;
-        FOTO_TRY(s.alloc(nxy * sizeof(double), &b)); s.fm = (double*)b;
+        for (double** plane : {&s.rho0, &s.rhoT, &s.px, &s.py, &s.fu, &s.fv, &s.fm})
+            FOTO_TRY(s.alloc(nxy * sizeof(double), plane));
         const int64_t nb = std::max<int64_t>(march_blocks(s.g), flat_blocks((int64_t)s.g.nloc * nxy));
         s.rb.cap = (int)std::max<int64_t>(2 * nb, 3 * (int64_t)prox_rhs_blocks(s.g, c->tn.pr_tch));
-        FOTO_TRY(s.alloc(sizeof(double) * s.rb.cap, &b)); s.rb.partials = (double*)b;
-        FOTO_TRY(s.alloc(sizeof(unsigned) * 64, &b)); s.rb.ticket = (unsigned*)b;
-        FOTO_HIP_CHECK(hipMemsetAsync(s.rb.ticket, 0, sizeof(unsigned) * 64, c->s));
-        FOTO_TRY(s.alloc(sizeof(double) * 4 * W, &b)); s.gath = (double*)b;
-        FOTO_HIP_CHECK(hipMemsetAsync(s.gath, 0, sizeof(double) * 4 * W, c->s));
-        FOTO_TRY(s.alloc(sizeof(CGScal), &b)); s.S = (CGScal*)b;
-        FOTO_TRY(load_rho(c, s, src));
-        FOTO_HIP_CHECK(launch_init_mu(s.g, s.rho0, s.rhoT, s.mu[0], s.mu[1], s.mu[2], s.q[0], s.q[1], s.q[2], c->s));
+        FOTO_TRY(s.alloc(sizeof(double) * s.rb.cap, &s.rb.partials));
+        FOTO_TRY(s.alloc_zeroed(sizeof(unsigned) * 64, &s.rb.ticket, c->s));
+        FOTO_TRY(s.alloc_zeroed(sizeof(double) * 4 * W, &s.gath, c->s));
+        FOTO_TRY(s.alloc_zeroed(sizeof(CGScal), &s.S, c->s));
+        FOTO_TRY(init_fields(c, s, src));
         if (c->o.cg_mode >= 1 && c->o.cg_mode <= 3) {
             s.spec.reset(new SpectralPlan());
             FOTO_TRY(s.spec->init(s.g, s.rank, W, c->r, c->eps, c->o.cg_mode, c->tn, c->s));
@@ -511,15 +537,12 @@ static CGArgs cg_args(foto_bb_ctx* c, const Shard& s) {
 static int cg_iteration(foto_bb_ctx* c, int k) {
     const int W = c->W;
     const bool fused = (W == 1);
-    for (auto& sp : c->sh) {
-        Shard& s = *sp;
-        double* pold = s.p[k & 1];
-        double* pnew = s.p[(k + 1) & 1];
-        const CGArgs a = cg_args(c, s);
-        const double nv = (double)s.g.nloc * (double)s.g.nxy;
-        if (!fused) FOTO_HIP_CHECK(launch_cg_pupd(s.g, k, s.rv, pold, pnew, s.S, s.gath_rr(), a, c->s));
-        (void)nv;
-    }
+    if (!fused)
+        for (auto& sp : c->sh) {
+            Shard& s = *sp;
+            FOTO_HIP_CHECK(launch_cg_pupd(s.g, k, s.rv, s.p[k & 1], s.p[(k + 1) & 1], s.S, s.gath_rr(), cg_args(c, s),
+                                          c->s));
+        }
     if (!fused) FOTO_TRY(halo(c, [k](Shard& s) { return s.p[(k + 1) & 1]; }));
     for (auto& sp : c->sh) {
         Shard& s = *sp;
@@ -875,6 +898,35 @@ static int prox_rhs(foto_bb_ctx* c, bool guarded, int par) {
     return 0;
 }
 
+// The prox of every local shard on its current phi and the crit readback into slot `par`: the
+// fused prox_rhs (on the pair in fz_src -> fz_dst), or phi's halo and k_prox; the crit all-gather;
+// its copy to the slot's host mirror unless the kernel stored it there; the iteration's `done`
+// event.  outer_tail enqueues it behind a deferred solve (guarded); a redo runs it unguarded on
+// the final phi and waits for the event.
+static int prox_crit(foto_bb_ctx* c, bool guarded, int par, hipEvent_t done) {
+    const int W = c->W;
+    if (c->fuse) {
+        FOTO_TRY(prox_rhs(c, guarded, par));
+    } else {
+        if (!c->phi_halo) FOTO_TRY(halo(c, [](Shard& s) { return s.phi; }));
+        c->phi_halo = false;
+        for (auto& sp : c->sh) {
+            Shard& s = *sp;
+            const double nv = (double)s.g.nloc * (double)s.g.nxy;
+            hipEvent_t t = c->kt.start(c->s);
+            FOTO_HIP_CHECK(launch_prox(s.g, s.phi, s.mu[0], s.mu[1], s.mu[2], s.q[0], s.q[1], s.q[2], c->r, s.rb,
+                                       s.gath_crit(W), s.rank, c->s, guarded ? s.spec->done_flag() : nullptr));
+            c->kt.stop(t, c->s, FOTO_K_PROX, 80.0 * nv);
+        }
+    }
+    FOTO_TRY(allgather(c, [W](Shard& s) { return s.gath_crit(W); }, 2));
+    if (!c->hcrit)
+        FOTO_HIP_CHECK(hipMemcpyAsync(c->hgath[par], c->sh[0]->gath, sizeof(double) * 4 * W, hipMemcpyDeviceToHost,
+                                      c->s));
+    FOTO_HIP_CHECK(hipEventRecord(done, c->s));
+    return 0;
+}
+
 // kmark: the KTimer mark taken before this iteration's head
 static int outer_tail(foto_bb_ctx* c, size_t kmark) {
     const int W = c->W;
@@ -882,12 +934,7 @@ static int outer_tail(foto_bb_ctx* c, size_t kmark) {
     foto_bb_ctx::Enq e;
     e.par = c->hpar;
     e.kmark = kmark;
-    for (int f = 0; f < 3; ++f) {
-        e.mu[f] = s0.mu[f]; e.nu[f] = s0.nu[f]; e.xi[f] = s0.xi[f];
-        e.fz_src[f] = s0.fz_src[f]; e.fz_dst[f] = s0.fz_dst[f];
-    }
-    e.phi = s0.phi;
-    e.phi_alt = s0.phi_alt;
+    e.before = s0.rot();
     e.f_ready = c->f_ready;
     e.hpar = c->hpar ^ 1;   // (before this iteration's head)
     hipEvent_t* ph = c->ph[e.par];
@@ -926,12 +973,13 @@ static int outer_tail(foto_bb_ctx* c, size_t kmark) {
     if (e.pev) FOTO_HIP_CHECK(hipEventRecord(ph[2], c->s));
     c->have_phi = 1;
 
-    if (c->fuse) {
-        // prox + the next iteration's RHS: mu -> nu, F -> rv; then nu is the current mu
-        // (pipelined: mu -> nu -> xi -> mu rotate, so the mu before this iteration survives it)
+    // fused: prox + the next iteration's RHS: mu -> nu, F -> rv; then nu is the current mu
+    // (pipelined: mu -> nu -> xi -> mu rotate, so the mu before this iteration survives it)
+    if (c->fuse)
         for (auto& sp : c->sh)
             for (int f = 0; f < 3; ++f) { sp->fz_src[f] = sp->mu[f]; sp->fz_dst[f] = sp->nu[f]; }
-        FOTO_TRY(prox_rhs(c, guarded, e.par));
+    FOTO_TRY(prox_crit(c, guarded, e.par, e.pev ? ph[3] : c->fin[e.par]));
+    if (c->fuse) {
         for (auto& sp : c->sh)
             for (int f = 0; f < 3; ++f) {
                 if (c->pipe) {
@@ -944,22 +992,7 @@ static int outer_tail(foto_bb_ctx* c, size_t kmark) {
                 }
             }
         c->f_ready = true;
-    } else {
-        if (!c->phi_halo) FOTO_TRY(halo(c, [](Shard& s) { return s.phi; }));
-        c->phi_halo = false;
-        for (auto& sp : c->sh) {
-            Shard& s = *sp;
-            const double nv = (double)s.g.nloc * (double)s.g.nxy;
-            hipEvent_t t = c->kt.start(c->s);
-            FOTO_HIP_CHECK(launch_prox(s.g, s.phi, s.mu[0], s.mu[1], s.mu[2], s.q[0], s.q[1], s.q[2], c->r, s.rb,
-                                       s.gath_crit(W), s.rank, c->s, guarded ? s.spec->done_flag() : nullptr));
-            c->kt.stop(t, c->s, FOTO_K_PROX, 80.0 * nv);
-        }
     }
-    FOTO_TRY(allgather(c, [W](Shard& s) { return s.gath_crit(W); }, 2));
-    if (!c->hcrit)
-        FOTO_HIP_CHECK(hipMemcpyAsync(c->hgath[e.par], s0.gath, sizeof(double) * 4 * W, hipMemcpyDeviceToHost, c->s));
-    FOTO_HIP_CHECK(hipEventRecord(e.pev ? ph[3] : c->fin[e.par], c->s));
     e.dsp = dsp;
     e.sdefer = sdefer;
     c->inflight.push_back(e);
@@ -979,12 +1012,7 @@ static int rollback(foto_bb_ctx* c) {
     Shard& s0 = *c->sh[0];
     if (e.dsp) FOTO_TRY(e.dsp->drop_newest(c->s));
     c->kt.discard_from(e.kmark);
-    for (int f = 0; f < 3; ++f) {
-        s0.mu[f] = e.mu[f]; s0.nu[f] = e.nu[f]; s0.xi[f] = e.xi[f];
-        s0.fz_src[f] = e.fz_src[f]; s0.fz_dst[f] = e.fz_dst[f];
-    }
-    s0.phi = e.phi;
-    s0.phi_alt = e.phi_alt;
+    s0.rot() = e.before;
     c->hpar = e.hpar;
     if (e.f_ready && s0.fz_src[0]) {
         // q of the kept iteration (stepB of its phi and the mu before it), for the next head's RHS
@@ -1016,28 +1044,24 @@ static void drain_inflight(foto_bb_ctx* c) {
 // next iteration is already on the stream and the shard's pointers are its own; the pipelined
 // loop keeps the completed iteration's phi and mu intact (the record of the one in flight holds
 // them), the one-in-flight loop does not (its next solve overwrites phi), so there a call from
-// the callback is refused.
+// the callback is refused.  Only shard 0 has such a record (the pipelined loop is single-shard):
+// of() gives every reader the pointers to use for a shard.
 struct Completed {
-    double* phi;
-    double* mu[3];
-    double* fz_src[3];
+    const Shard* s0 = nullptr;
+    const Rot* k0 = nullptr;   // shard 0's own pointers, or the record of the iteration in flight
+    const Rot& of(const Shard& s) const { return &s == s0 ? *k0 : s; }
 };
 static int completed_state(foto_bb_ctx* c, const char* who, Completed* out) {
-    Shard& s0 = *c->sh[0];
-    if (c->inflight.empty()) {
-        out->phi = s0.phi;
-        for (int f = 0; f < 3; ++f) { out->mu[f] = s0.mu[f]; out->fz_src[f] = s0.fz_src[f]; }
-        return 0;
-    }
+    out->s0 = c->sh[0].get();
+    out->k0 = out->s0;
+    if (c->inflight.empty()) return 0;
     if (!c->pipe) {
         set_error("%s: called while the next outer iteration is on the stream (from the iteration callback of "
                   "the one-in-flight loop, whose next solve overwrites phi); call it after foto_bb_iterate returns",
                   who);
         return FOTO_ERR_STATE;
     }
-    const foto_bb_ctx::Enq& e = c->inflight.front();
-    out->phi = e.phi;
-    for (int f = 0; f < 3; ++f) { out->mu[f] = e.mu[f]; out->fz_src[f] = e.fz_src[f]; }
+    out->k0 = &c->inflight.front().before;   // (stays put: an export enqueues and drops no iteration)
     return 0;
 }
 
@@ -1063,22 +1087,9 @@ static int outer_complete(foto_bb_ctx* c, double* crit, int* cg_iters, int* cg_i
         FOTO_TRY(dsp->finish(cg_iters, cg_info, &redo, &c->kt, c->s));
         c->last_cg = *cg_iters;
         if (redo) {   // the guarded prox returned at once: drop its timing, run it on the final phi
-            Shard& s = *c->sh[0];
-            const double nv = (double)s.g.nloc * (double)s.g.nxy;
             c->kt.discard_last(FOTO_K_PROX, 1);
-            if (c->fuse) {
-                FOTO_TRY(prox_rhs(c, false, e.par));
-                c->f_ready = true;   // (a rollback before the redo had cleared it)
-            } else {
-                hipEvent_t t = c->kt.start(c->s);
-                FOTO_HIP_CHECK(launch_prox(s.g, s.phi, s.mu[0], s.mu[1], s.mu[2], s.q[0], s.q[1], s.q[2], c->r,
-                                           s.rb, s.gath_crit(W), s.rank, c->s));
-                c->kt.stop(t, c->s, FOTO_K_PROX, 80.0 * nv);
-            }
-            if (!c->hcrit)
-                FOTO_HIP_CHECK(hipMemcpyAsync(c->hgath[e.par], s.gath, sizeof(double) * 4 * W, hipMemcpyDeviceToHost,
-                                              c->s));
-            FOTO_HIP_CHECK(hipEventRecord(done, c->s));
+            FOTO_TRY(prox_crit(c, false, e.par, done));
+            if (c->fuse) c->f_ready = true;   // (a rollback before the redo had cleared it)
             FOTO_HIP_CHECK(hipEventSynchronize(done));
             c->st.cg_redo += 1;
         }
@@ -1096,21 +1107,7 @@ static int outer_complete(foto_bb_ctx* c, double* crit, int* cg_iters, int* cg_i
             c->kt.discard_last(FOTO_K_PROX, (int)c->sh.size());
             FOTO_TRY(sharded_sstep(c, cg_iters, cg_info));
             FOTO_TRY(sharded_inv(c));
-            if (c->fuse) {
-                FOTO_TRY(prox_rhs(c, false, e.par));
-            } else {
-                if (!c->phi_halo) FOTO_TRY(halo(c, [](Shard& s) { return s.phi; }));
-                c->phi_halo = false;
-                for (auto& sp : c->sh) {
-                    Shard& s = *sp;
-                    FOTO_HIP_CHECK(launch_prox(s.g, s.phi, s.mu[0], s.mu[1], s.mu[2], s.q[0], s.q[1], s.q[2], c->r,
-                                               s.rb, s.gath_crit(W), s.rank, c->s));
-                }
-            }
-            FOTO_TRY(allgather(c, [W](Shard& s) { return s.gath_crit(W); }, 2));
-            FOTO_HIP_CHECK(hipMemcpyAsync(c->hgath[e.par], c->sh[0]->gath, sizeof(double) * 4 * W,
-                                          hipMemcpyDeviceToHost, c->s));
-            FOTO_HIP_CHECK(hipEventRecord(done, c->s));
+            FOTO_TRY(prox_crit(c, false, e.par, done));
             FOTO_HIP_CHECK(hipEventSynchronize(done));
             c->st.cg_redo += 1;
         }
@@ -1143,7 +1140,16 @@ struct FlowDev {
     hipStream_t user;
 };
 
-// (shard 0 reads the completed iteration's phi, k.phi: an export writes no solver state)
+// a shard's flow record (fu, fv, fm: one plane of float64 each) into three host arrays
+static int download_flow(foto_bb_ctx* c, const Shard& s, double* u, double* v, double* m) {
+    const size_t bytes = (size_t)c->Nx * c->Ny * sizeof(double);
+    FOTO_HIP_CHECK(hipMemcpyAsync(u, s.fu, bytes, hipMemcpyDeviceToHost, c->s));
+    FOTO_HIP_CHECK(hipMemcpyAsync(v, s.fv, bytes, hipMemcpyDeviceToHost, c->s));
+    FOTO_HIP_CHECK(hipMemcpyAsync(m, s.fm, bytes, hipMemcpyDeviceToHost, c->s));
+    return 0;
+}
+
+// (shard 0 reads the completed iteration's phi, k.of(): an export writes no solver state)
 static int flow(foto_bb_ctx* c, const Completed& k, double* u, double* v, double* m, const FlowDev* dv = nullptr) {
     if (!c->have_phi) {
         set_error("foto_bb_flow: no outer iteration has run yet (reference: UnboundLocalError for max_it=0)");
@@ -1163,8 +1169,7 @@ static int flow(foto_bb_ctx* c, const Completed& k, double* u, double* v, double
     for (int j = 0; j < W; ++j) {
         if (Shard* s = local(j)) {
             const int n_lo = s->g.t0, n_hi = std::min(s->g.t0 + s->g.nloc, c->Nt - 1);
-            const double* phi = (s == c->sh[0].get()) ? k.phi : s->phi;
-            FOTO_HIP_CHECK(launch_traj(s->g, phi, n_lo, std::max(n_lo, n_hi), s->px, s->py, j == 0, c->s));
+            FOTO_HIP_CHECK(launch_traj(s->g, k.of(*s).phi, n_lo, std::max(n_lo, n_hi), s->px, s->py, j == 0, c->s));
             if (j == W - 1)
                 FOTO_HIP_CHECK(launch_flow_record(c->Nx, c->Ny, s->px, s->py, s->fu, s->fv, s->fm, FOTO_F64, 0, c->s));
         }
@@ -1181,11 +1186,7 @@ static int flow(foto_bb_ctx* c, const Completed& k, double* u, double* v, double
         FOTO_TRY(exchange(c, xs, [](Shard& s) { return s.fm; }, [](Shard& s) { return s.fm; }));
     }
     if (Shard* s0 = local(0)) {
-        if (u && v && m) {
-            FOTO_HIP_CHECK(hipMemcpyAsync(u, s0->fu, nxy * sizeof(double), hipMemcpyDeviceToHost, c->s));
-            FOTO_HIP_CHECK(hipMemcpyAsync(v, s0->fv, nxy * sizeof(double), hipMemcpyDeviceToHost, c->s));
-            FOTO_HIP_CHECK(hipMemcpyAsync(m, s0->fm, nxy * sizeof(double), hipMemcpyDeviceToHost, c->s));
-        }
+        if (u && v && m) FOTO_TRY(download_flow(c, *s0, u, v, m));
         if (dv) {   // (the caller's earlier work on `out` first; the trajectories above did not touch it)
             FOTO_TRY(c->link.enter(dv->user, c->s));
             FOTO_HIP_CHECK(launch_export(nxy, s0->fu, s0->fv, s0->fm, dv->out, dv->dtype, dv->layout, c->s));
@@ -1219,8 +1220,7 @@ static int flow_path(foto_bb_ctx* c, const Completed& k, double* hu, double* hv,
     for (int n = 0; n + 1 < c->Nt; ++n) {
         Shard* sp = plane_owner(c, n);
         if (!sp) { set_error("flow path: no local shard owns plane %d", n); return FOTO_ERR_STATE; }
-        const double* phi = (sp == &s0) ? k.phi : sp->phi;
-        FOTO_HIP_CHECK(launch_traj(sp->g, phi, n, n + 1, s0.px, s0.py, n == 0, c->s));
+        FOTO_HIP_CHECK(launch_traj(sp->g, k.of(*sp).phi, n, n + 1, s0.px, s0.py, n == 0, c->s));
         if (dv) {
             const size_t rec = (size_t)nxy * (dv->layout == 0 ? 3 : 2) * dtype_bytes(dv->dtype);
             char* o = (char*)dv->out + (size_t)n * rec;
@@ -1229,9 +1229,7 @@ static int flow_path(foto_bb_ctx* c, const Completed& k, double* hu, double* hv,
                                               dv->layout, c->s));
         } else {
             FOTO_HIP_CHECK(launch_flow_record(c->Nx, c->Ny, s0.px, s0.py, s0.fu, s0.fv, s0.fm, FOTO_F64, 0, c->s));
-            FOTO_HIP_CHECK(hipMemcpyAsync(hu + n * nxy, s0.fu, nxy * sizeof(double), hipMemcpyDeviceToHost, c->s));
-            FOTO_HIP_CHECK(hipMemcpyAsync(hv + n * nxy, s0.fv, nxy * sizeof(double), hipMemcpyDeviceToHost, c->s));
-            FOTO_HIP_CHECK(hipMemcpyAsync(hm + n * nxy, s0.fm, nxy * sizeof(double), hipMemcpyDeviceToHost, c->s));
+            FOTO_TRY(download_flow(c, s0, hu + n * nxy, hv + n * nxy, hm + n * nxy));
         }
     }
     if (dv) return c->link.leave(c->s, dv->user);
@@ -1288,7 +1286,6 @@ static int frames_check(foto_bb_ctx* c, const double* s, int count, double scale
 // planes are mu's t-part of the completed iteration, in whichever shard owns them.
 static int frames_launch(foto_bb_ctx* c, const Completed& k, const double* s, int cnt, double scale, void* out,
                          int dtype) {
-    Shard& s0 = *c->sh[0];
     const int64_t nxy = (int64_t)c->Nx * c->Ny;
     FrameArgs fa;
     for (int i = 0; i < cnt; ++i) {
@@ -1297,10 +1294,8 @@ static int frames_launch(foto_bb_ctx* c, const Completed& k, const double* s, in
         Shard* pa = plane_owner(c, n);
         Shard* pb = plane_owner(c, n + 1);
         if (!pa || !pb) { set_error("frames: no local shard owns plane %d / %d", n, n + 1); return FOTO_ERR_STATE; }
-        const double* ma = (pa == &s0) ? k.mu[0] : pa->mu[0];
-        const double* mb = (pb == &s0) ? k.mu[0] : pb->mu[0];
-        fa.a[i] = ma + (int64_t)(n - pa->g.t0) * nxy;
-        fa.b[i] = mb + (int64_t)(n + 1 - pb->g.t0) * nxy;
+        fa.a[i] = k.of(*pa).mu[0] + (int64_t)(n - pa->g.t0) * nxy;
+        fa.b[i] = k.of(*pb).mu[0] + (int64_t)(n + 1 - pb->g.t0) * nxy;
         fa.w[i] = w;
     }
     FOTO_HIP_CHECK(launch_frames(fa, cnt, nxy, scale, out, dtype, c->s));
@@ -1449,20 +1444,11 @@ int foto_bb_create_dev(const foto_image* f0, const foto_image* f1, int normalize
                        double r, double reg_epsilon, const foto_bb_opts* opts, double* sums2_or_null,
                        foto_bb_ctx** out) {
     if (!f0 || !f1 || !out) { set_error("foto_bb_create_dev: null argument"); return FOTO_ERR_ARG; }
-    RhoSrc src;
-    src.i0 = f0;
-    src.iT = f1;
-    src.normalize = normalize != 0;
-    src.user = (hipStream_t)stream;
+    const RhoSrc src = dev_src(f0, f1, normalize, stream);
     foto_bb_ctx* c = nullptr;
     FOTO_TRY(bb_create(src, Nt, Nx, Ny, r, reg_epsilon, opts, &c));
     std::unique_ptr<foto_bb_ctx> guard(c);
-    // (ctx_init ends with a stream synchronise: the inputs are read, the sums are on the host)
-    FOTO_TRY(c->link.leave(c->s, src.user));
-    if (sums2_or_null) {
-        sums2_or_null[0] = src.normalize ? c->hsum[0] : 1.0;
-        sums2_or_null[1] = src.normalize ? c->hsum[1] : 1.0;
-    }
+    FOTO_TRY(dev_src_done(c, src, sums2_or_null));
     *out = guard.release();
     return 0;
 }
@@ -1545,6 +1531,9 @@ static int iterate_loop(foto_bb_ctx* c, int max_iters, double tol, int use_stop_
         if (head_early) FOTO_TRY(outer_head(c));
         const int redo0 = c->st.cg_redo;
         FOTO_TRY(outer_complete(c, &crit, &its, &info));
+        // (a redo waited for the stream after its re-run: its timing records are complete as well,
+        // and count now, as in the pipelined loop, not in the next call)
+        const size_t complete = c->st.cg_redo != redo0 ? c->kt.mark() : mark;
         ++done;
         stopped = stop_test(crit);
         // the next iteration goes on the stream before the host's bookkeeping for this one
@@ -1553,7 +1542,7 @@ static int iterate_loop(foto_bb_ctx* c, int max_iters, double tol, int use_stop_
             if (!head_early || c->st.cg_redo != redo0) FOTO_TRY(outer_head(c));
             FOTO_TRY(outer_tail(c, mark));
         }
-        c->kt.resolve_upto(mark);
+        c->kt.resolve_upto(complete);
         if (cb) cb(user, c->st.outer_iters - 1, crit, its, info);
         if (stopped) break;
     }
@@ -1571,26 +1560,14 @@ static int bb_reset(foto_bb_ctx* c, const RhoSrc& src) {
     }
     drain_inflight(c);   // (outside foto_bb_iterate nothing is in flight: a no-op unless a call failed)
     c->broken = false;
-    const int64_t nxy = (int64_t)c->Nx * c->Ny;
     FOTO_HIP_CHECK(hipStreamSynchronize(c->s));
     for (auto& sp : c->sh) {
         Shard& s = *sp;
-        const size_t bytes = (size_t)(s.g.nloc + 2) * (size_t)nxy * sizeof(double);
-        double* fields[] = {s.mu[0], s.mu[1], s.mu[2], s.q[0], s.q[1], s.q[2], s.nu[0], s.nu[1], s.nu[2],
-                            s.xi[0], s.xi[1], s.xi[2], s.rv, s.p[0], s.p[1]};
-        for (double* f : fields)   // as ctx_init leaves them: zero, halo planes included
-            if (f) FOTO_HIP_CHECK(hipMemsetAsync(f - nxy, 0, bytes, c->s));
-        if (s.wt) FOTO_HIP_CHECK(hipMemsetAsync(s.wt - nxy, 0, bytes, c->s));
-        if (s.edge) FOTO_HIP_CHECK(hipMemsetAsync(s.edge, 0, sizeof(double) * 8 * nxy, c->s));
-        for (double* f : {s.phi, s.phi_alt})   // (two halo planes per side)
-            if (f) FOTO_HIP_CHECK(hipMemsetAsync(f - 2 * nxy, 0, bytes + 2 * nxy * sizeof(double), c->s));
-        FOTO_HIP_CHECK(hipMemsetAsync(s.gath, 0, sizeof(double) * 4 * c->W, c->s));
-        FOTO_HIP_CHECK(hipMemsetAsync(s.rb.ticket, 0, sizeof(unsigned) * 64, c->s));
-        FOTO_HIP_CHECK(hipMemsetAsync(s.S, 0, sizeof(CGScal), c->s));
-        FOTO_TRY(load_rho(c, s, src));
-        FOTO_HIP_CHECK(launch_init_mu(s.g, s.rho0, s.rhoT, s.mu[0], s.mu[1], s.mu[2], s.q[0], s.q[1], s.q[2], c->s));
+        FOTO_TRY(s.rezero(c->s));   // as ctx_init leaves them: zero, halo planes included
+        FOTO_TRY(init_fields(c, s, src));
         if (s.spec) FOTO_TRY(s.spec->reset(c->s));
     }
+    // the host side of the loop state, as a new context has it
     c->last_cg = 0;
     c->last_passes = 0;
     c->have_phi = 0;
@@ -1625,18 +1602,9 @@ int foto_bb_reset_dev(foto_bb_ctx* c, const foto_image* f0, const foto_image* f1
     const int dev = stream_device(c->s);
     FOTO_TRY(image_dev_check(f0, c->Nx, c->Ny, dev, "foto_bb_reset_dev (f0)"));
     FOTO_TRY(image_dev_check(f1, c->Nx, c->Ny, dev, "foto_bb_reset_dev (f1)"));
-    RhoSrc src;
-    src.i0 = f0;
-    src.iT = f1;
-    src.normalize = normalize != 0;
-    src.user = (hipStream_t)stream;
+    const RhoSrc src = dev_src(f0, f1, normalize, stream);
     FOTO_TRY(bb_reset(c, src));
-    FOTO_TRY(c->link.leave(c->s, src.user));
-    if (sums2_or_null) {
-        sums2_or_null[0] = src.normalize ? c->hsum[0] : 1.0;
-        sums2_or_null[1] = src.normalize ? c->hsum[1] : 1.0;
-    }
-    return 0;
+    return dev_src_done(c, src, sums2_or_null);
 }
 
 int foto_bb_flow_dev(foto_bb_ctx* c, void* out, int dtype, int layout, void* stream) {
@@ -1697,15 +1665,13 @@ static bool track_needs_pos(foto_bb_ctx* c) {
 
 static int track_run(foto_bb_ctx* c, const Completed& k, const void* pts, int pts_dtype, int64_t M, int all_steps,
                      void* out, int dtype) {
-    Shard& s0 = *c->sh[0];
     const int last = c->Nt - 1;
     double* const pos = (double*)c->trk[foto_bb_ctx::TRK_POS].p;
     for (int n = 0; n < last;) {
         Shard* sp = plane_owner(c, n);
         if (!sp) { set_error("point tracking: no local shard owns plane %d", n); return FOTO_ERR_STATE; }
         const int n_hi = std::min(sp->g.t0 + sp->g.nloc, last);
-        const double* phi = (sp == &s0) ? k.phi : sp->phi;
-        FOTO_HIP_CHECK(launch_track(sp->g, phi, n, n_hi, pts, pts_dtype, n == 0 ? nullptr : pos,
+        FOTO_HIP_CHECK(launch_track(sp->g, k.of(*sp).phi, n, n_hi, pts, pts_dtype, n == 0 ? nullptr : pos,
                                     n_hi == last ? nullptr : pos, out, dtype, M, all_steps, c->s));
         n = n_hi;
     }
@@ -1809,8 +1775,7 @@ int foto_bb_get_phi(foto_bb_ctx* c, double* phi) {
     size_t off = 0;
     for (auto& sp : c->sh) {
         const size_t n = (size_t)sp->g.nloc * sp->g.nxy;
-        const double* src = (sp.get() == c->sh[0].get()) ? k.phi : sp->phi;
-        FOTO_HIP_CHECK(hipMemcpyAsync(phi + off, src, n * sizeof(double), hipMemcpyDeviceToHost, c->s));
+        FOTO_HIP_CHECK(hipMemcpyAsync(phi + off, k.of(*sp).phi, n * sizeof(double), hipMemcpyDeviceToHost, c->s));
         off += n;
     }
     FOTO_HIP_CHECK(hipStreamSynchronize(c->s));
@@ -1821,13 +1786,13 @@ int foto_bb_get_state(foto_bb_ctx* c, double* mu3, double* q3) {
     if (!c) return FOTO_ERR_ARG;
     Completed k;
     FOTO_TRY(completed_state(c, "foto_bb_get_state", &k));
-    auto is0 = [&](const Shard& s) { return &s == c->sh[0].get(); };
     if (q3 && c->fuse && c->have_phi) {   // the fused kernel never stores q: recompute it (bit-identical)
         for (auto& sp : c->sh) {   // (phi's halo planes are the ones the last prox read)
             Shard& s = *sp;
-            double* const* src = is0(s) ? k.fz_src : s.fz_src;
+            const Rot& ks = k.of(s);
+            double* const* src = ks.fz_src;
             if (!src[0]) continue;
-            FOTO_HIP_CHECK(launch_q_from_phi(s.g, is0(s) ? k.phi : s.phi, src[0], src[1], src[2], s.q[0], s.q[1],
+            FOTO_HIP_CHECK(launch_q_from_phi(s.g, ks.phi, src[0], src[1], src[2], s.q[0], s.q[1],
                                              s.q[2], c->r, c->s));
         }
     }
@@ -1837,8 +1802,8 @@ int foto_bb_get_state(foto_bb_ctx* c, double* mu3, double* q3) {
         size_t off = 0;
         for (auto& sp : c->sh) {
             const size_t n = (size_t)sp->g.nloc * sp->g.nxy;
-            const double* mu = is0(*sp) ? k.mu[f] : sp->mu[f];
-            if (mu3) FOTO_HIP_CHECK(hipMemcpyAsync(mu3 + f * tot + off, mu, n * 8, hipMemcpyDeviceToHost, c->s));
+            if (mu3)
+                FOTO_HIP_CHECK(hipMemcpyAsync(mu3 + f * tot + off, k.of(*sp).mu[f], n * 8, hipMemcpyDeviceToHost, c->s));
             if (q3) FOTO_HIP_CHECK(hipMemcpyAsync(q3 + f * tot + off, sp->q[f], n * 8, hipMemcpyDeviceToHost, c->s));
             off += n;
         }

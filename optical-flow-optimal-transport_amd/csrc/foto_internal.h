@@ -176,19 +176,7 @@ struct KTimer {
         }
         pend.erase(pend.begin(), pend.begin() + n);
     }
-    void resolve() {   // call after a stream sync
-        for (auto& p : pend) {
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, p.a, p.b) == hipSuccess) {
-                n[p.cls] += 1;
-                ms[p.cls] += t;
-                bytes[p.cls] += p.bytes;
-            }
-            pool.push_back(p.a);
-            pool.push_back(p.b);
-        }
-        pend.clear();
-    }
+    void resolve() { resolve_first(pend.size()); }   // call after a stream sync
     void reset() {
         std::fill(n, n + 8, 0);
         std::fill(ms, ms + 8, 0.0);

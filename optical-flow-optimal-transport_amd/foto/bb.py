@@ -21,6 +21,32 @@ CG_SSTEP = 2
 CG_GAUSS = 3
 
 
+def fill_options(L, device, cg_rtol, cg_maxiter, cg_mode, rank, world, nccl_id, virtual_ranks, timing):
+    """(foto_bb_opts, the buffer its nccl_id points into or None) -- keep the buffer alive for as
+    long as the options are in use."""
+    o = _lib.BBOpts()
+    L.foto_bb_opts_default(ctypes.byref(o))
+    o.device = int(device)
+    o.cg_rtol = float(cg_rtol)
+    o.cg_maxiter = int(cg_maxiter)
+    o.cg_mode = int(cg_mode)
+    o.rank = int(rank)
+    o.world = int(world)
+    idbuf = None
+    if nccl_id is not None:
+        idbuf = ctypes.create_string_buffer(bytes(nccl_id), 128)
+        o.nccl_id = ctypes.cast(idbuf, ctypes.c_void_p)
+    o.virtual_ranks = int(virtual_ranks)
+    o.timing = 1 if timing else 0
+    return o, idbuf
+
+
+def kernel_stats(st):
+    """The ``kernels`` dictionary of a foto_bb_stats: per timed kernel class its launches, ms, bytes."""
+    return {name: {"n": int(st.n_k[i]), "ms": float(st.ms_k[i]), "bytes": float(st.bytes_k[i])}
+            for i, name in enumerate(_lib.K_NAMES) if st.n_k[i] > 0}
+
+
 class BBSolver:
     """Device-resident Benamou-Brenier state (mu, q, phi stay in HBM between calls).
 
@@ -46,7 +72,8 @@ class BBSolver:
         self.r = float(r)
         self.eps = float(reg_epsilon)
         nxy = Nx * Ny
-        o = self._options(device, cg_rtol, cg_maxiter, cg_mode, rank, world, nccl_id, virtual_ranks, timing)
+        o, self._id = fill_options(self._L, device, cg_rtol, cg_maxiter, cg_mode, rank, world, nccl_id, virtual_ranks,
+                                   timing)
         self._ctx = ctypes.c_void_p()
         if _device_pair is None:
             self._rho0 = f64(rho0, nxy, "rho0")
@@ -62,26 +89,13 @@ class BBSolver:
             self.sums = (float(sums[0]), float(sums[1]))
         self.world = int(world)
         self.rank = int(rank)
+        self._clear_log()
+
+    def _clear_log(self):
+        """the per-iteration record of a run: empty on a new or reset context"""
         self.crit = []
         self.cg_its = []
         self.cg_info = []
-
-    def _options(self, device, cg_rtol, cg_maxiter, cg_mode, rank, world, nccl_id, virtual_ranks, timing):
-        o = _lib.BBOpts()
-        self._L.foto_bb_opts_default(ctypes.byref(o))
-        o.device = int(device)
-        o.cg_rtol = float(cg_rtol)
-        o.cg_maxiter = int(cg_maxiter)
-        o.cg_mode = int(cg_mode)
-        o.rank = int(rank)
-        o.world = int(world)
-        self._id = None
-        if nccl_id is not None:
-            self._id = ctypes.create_string_buffer(bytes(nccl_id), 128)
-            o.nccl_id = ctypes.cast(self._id, ctypes.c_void_p)
-        o.virtual_ranks = int(virtual_ranks)
-        o.timing = 1 if timing else 0
-        return o
 
     # -------------------------------------------------------------- device buffers
     @classmethod
@@ -109,9 +123,7 @@ class BBSolver:
         self._check(self._L.foto_bb_reset_dev(self._ctx, ctypes.byref(a), ctypes.byref(b), 1 if normalize else 0,
                                               ctypes.c_void_p(D.stream_handle(stream, f0, f1)), dptr(sums)))
         self.sums = (float(sums[0]), float(sums[1]))
-        self.crit = []
-        self.cg_its = []
-        self.cg_info = []
+        self._clear_log()
 
     def flow_device(self, out=None, dtype="float32", layout="planar", stream=None):
         """flow() left on the device (foto_bb_flow_dev): a DeviceArray (or ``out``, any
@@ -202,9 +214,7 @@ class BBSolver:
         self._rho0 = f64(rho0, nxy, "rho0")
         self._rhoT = f64(rhoT, nxy, "rhoT")
         self._check(self._L.foto_bb_reset(self._ctx, dptr(self._rho0), dptr(self._rhoT)))
-        self.crit = []
-        self.cg_its = []
-        self.cg_info = []
+        self._clear_log()
 
     # -------------------------------------------------------------- lifecycle
     def close(self):
@@ -297,8 +307,7 @@ class BBSolver:
         self._check(self._L.foto_bb_stats_get(self._ctx, ctypes.byref(st)))
         d = {f: getattr(st, f) for f in ("outer_iters", "cg_iters_total", "last_crit", "ms_rhs", "ms_cg",
                                          "ms_prox", "ms_flow", "cg_redo")}
-        d["kernels"] = {name: {"n": int(st.n_k[i]), "ms": float(st.ms_k[i]), "bytes": float(st.bytes_k[i])}
-                        for i, name in enumerate(_lib.K_NAMES) if st.n_k[i] > 0}
+        d["kernels"] = kernel_stats(st)
         return d
 
     def reset_stats(self):
@@ -326,22 +335,30 @@ def _cache_enabled(opts):
             and int(opts.get("world", 1)) == 1)
 
 
-def cached_solver(rho0, rhoT, Nt, Nx, Ny, r, reg_epsilon, **opts):
-    """A BBSolver for this size and these options, reset to (rho0, rhoT): reused from the
-    cache when one exists, else created (the least recently used context beyond
-    CONTEXT_CACHE_SIZE is destroyed)."""
+def _cached(Nt, Nx, Ny, r, reg_epsilon, opts, reset, make):
+    """The cache walk: the context of this size and these options taken out and ``reset(s)``, or
+    ``make()``; put back as the most recently used, the least recently used beyond
+    CONTEXT_CACHE_SIZE destroyed."""
     # FOTO_* tuning variables are read when a context is built: part of its identity
     env = tuple(sorted((k, v) for k, v in os.environ.items() if k.startswith("FOTO_")))
     key = (int(Nt), int(Nx), int(Ny), float(r), float(reg_epsilon), tuple(sorted(opts.items())), env)
     s = _ctx_cache.pop(key, None)
     if s is not None:
-        s.reset(rho0, rhoT)
+        reset(s)
     else:
-        s = BBSolver(rho0, rhoT, Nt, Nx, Ny, r=r, reg_epsilon=reg_epsilon, **opts)
+        s = make()
     _ctx_cache[key] = s
     while len(_ctx_cache) > CONTEXT_CACHE_SIZE:
         _ctx_cache.popitem(last=False)[1].close()
     return s
+
+
+def cached_solver(rho0, rhoT, Nt, Nx, Ny, r, reg_epsilon, **opts):
+    """A BBSolver for this size and these options, reset to (rho0, rhoT): reused from the
+    cache when one exists, else created (the least recently used context beyond
+    CONTEXT_CACHE_SIZE is destroyed)."""
+    return _cached(Nt, Nx, Ny, r, reg_epsilon, opts, lambda s: s.reset(rho0, rhoT),
+                   lambda: BBSolver(rho0, rhoT, Nt, Nx, Ny, r=r, reg_epsilon=reg_epsilon, **opts))
 
 
 def cached_solver_device(f0, f1, Nt, r, reg_epsilon, *, normalize=False, stream=None, **opts):
@@ -350,17 +367,9 @@ def cached_solver_device(f0, f1, Nt, r, reg_epsilon, *, normalize=False, stream=
     from . import device as D
     a, b = D._pair(f0, f1)
     h, w = a.shape
-    env = tuple(sorted((k, v) for k, v in os.environ.items() if k.startswith("FOTO_")))
-    key = (int(Nt), int(w), int(h), float(r), float(reg_epsilon), tuple(sorted(opts.items())), env)
-    s = _ctx_cache.pop(key, None)
-    if s is not None:
-        s.reset_device(a, b, normalize=normalize, stream=stream)
-    else:
-        s = BBSolver.from_device(a, b, Nt, r=r, reg_epsilon=reg_epsilon, normalize=normalize, stream=stream, **opts)
-    _ctx_cache[key] = s
-    while len(_ctx_cache) > CONTEXT_CACHE_SIZE:
-        _ctx_cache.popitem(last=False)[1].close()
-    return s
+    return _cached(Nt, w, h, r, reg_epsilon, opts, lambda s: s.reset_device(a, b, normalize=normalize, stream=stream),
+                   lambda: BBSolver.from_device(a, b, Nt, r=r, reg_epsilon=reg_epsilon, normalize=normalize,
+                                                stream=stream, **opts))
 
 
 def drop_cached(s):
@@ -369,6 +378,21 @@ def drop_cached(s):
         if v is s:
             del _ctx_cache[k]
     s.close()
+
+
+def on_context(opts, cached, fresh, run):
+    """``run(s)`` on the context ``cached()`` returns -- a failed run leaves no half-used context
+    behind: it is forgotten and closed -- or, where these options are not cached, on ``fresh()``,
+    closed afterwards."""
+    if _cache_enabled(opts):
+        s = cached()
+        try:
+            return run(s)
+        except BaseException:
+            drop_cached(s)
+            raise
+    with fresh() as s:
+        return run(s)
 
 
 def clear_context_cache():
@@ -388,18 +412,9 @@ def solve(rho0, rhoT, Nt, Nx, Ny, r=1, convergence_tol=0.3, reg_epsilon=1e-3, ma
             log(f"WARNING: CG did not converge in {info} iterations.")
         log(str(np.float64(crit)) + " (" + str(it + 1) + "/" + str(max_it) + ")")
 
-    if _cache_enabled(opts):
-        s = cached_solver(rho0, rhoT, Nt, Nx, Ny, r, reg_epsilon, **opts)
-        try:
-            return _run(s, max_it, convergence_tol, cb, stats)
-        except BaseException:   # a failed solve leaves no half-used context behind
-            for k, v in list(_ctx_cache.items()):
-                if v is s:
-                    del _ctx_cache[k]
-            s.close()
-            raise
-    with BBSolver(rho0, rhoT, Nt, Nx, Ny, r=r, reg_epsilon=reg_epsilon, **opts) as s:
-        return _run(s, max_it, convergence_tol, cb, stats)
+    return on_context(opts, lambda: cached_solver(rho0, rhoT, Nt, Nx, Ny, r, reg_epsilon, **opts),
+                      lambda: BBSolver(rho0, rhoT, Nt, Nx, Ny, r=r, reg_epsilon=reg_epsilon, **opts),
+                      lambda s: _run(s, max_it, convergence_tol, cb, stats))
 
 
 def solve_ex(rho0, rhoT, Nt, Nx, Ny, r=1, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, cap=None,
@@ -415,14 +430,8 @@ def solve_ex(rho0, rhoT, Nt, Nx, Ny, r=1, convergence_tol=0.3, reg_epsilon=1e-3,
     Nt, Nx, Ny = int(Nt), int(Nx), int(Ny)
     nxy = Nx * Ny
     a0, aT = f64(rho0, nxy, "rho0"), f64(rhoT, nxy, "rhoT")
-    o = _lib.BBOpts()
-    L.foto_bb_opts_default(ctypes.byref(o))
-    o.device, o.cg_mode, o.cg_rtol, o.cg_maxiter = int(device), int(cg_mode), float(cg_rtol), int(cg_maxiter)
-    o.rank, o.world, o.virtual_ranks, o.timing = int(rank), int(world), int(virtual_ranks), 1 if timing else 0
-    idbuf = None
-    if nccl_id is not None:
-        idbuf = ctypes.create_string_buffer(bytes(nccl_id), 128)
-        o.nccl_id = ctypes.cast(idbuf, ctypes.c_void_p)
+    # (idbuf: what o.nccl_id points into, alive until the call below has returned)
+    o, idbuf = fill_options(L, device, cg_rtol, cg_maxiter, cg_mode, rank, world, nccl_id, virtual_ranks, timing)
     cap = int(max_it if cap is None else cap)
     crit = np.zeros(max(cap, 1))
     its = np.zeros(max(cap, 1), dtype=np.int32)
@@ -446,8 +455,7 @@ def solve_ex(rho0, rhoT, Nt, Nx, Ny, r=1, convergence_tol=0.3, reg_epsilon=1e-3,
            "phi_t0": st.phi_t0, "phi_nloc": st.phi_nloc, "ms_create": st.ms_create, "ms_loop": st.ms_loop,
            "ms_flow": st.ms_flow, "alg_bytes_per_iter": st.alg_bytes_per_iter,
            "cg_iters_total": int(st.bb.cg_iters_total), "cg_redo": int(st.bb.cg_redo),
-           "kernels": {name: {"n": int(st.bb.n_k[i]), "ms": float(st.bb.ms_k[i]), "bytes": float(st.bb.bytes_k[i])}
-                       for i, name in enumerate(_lib.K_NAMES) if st.bb.n_k[i] > 0}}
+           "kernels": kernel_stats(st.bb)}
     if want_phi:
         rep["phi"] = phi[:st.phi_nloc * nxy].copy()
     return u, v, m, rep

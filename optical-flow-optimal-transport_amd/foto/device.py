@@ -61,6 +61,28 @@ def _typestr(dtype):
     return ts
 
 
+def packed_strides(shape, item):
+    """The byte strides of a C-contiguous array of ``shape``."""
+    st, acc = [], item
+    for s in reversed(tuple(shape)):
+        st.append(acc)
+        acc *= max(s, 1)
+    return tuple(reversed(st))
+
+
+def c_contiguous(shape, strides, item):
+    """Whether byte ``strides`` (None: packed) lay ``shape`` out C-contiguously: the one such test
+    of the package (DeviceArray.contiguous and every device argument that must be packed)."""
+    if strides is None:
+        return True
+    acc = item
+    for s, st in zip(reversed(tuple(shape)), reversed(tuple(strides))):
+        if s > 1 and st != acc:
+            return False
+        acc *= s
+    return True
+
+
 class _Owner:
     """One foto_dev_malloc allocation, freed with its last DeviceArray view."""
 
@@ -96,11 +118,7 @@ class DeviceArray:
         self._owner = _owner if _owner is not None else _Owner(max(size * self.dtype.itemsize, 1))
         self._offset = int(_offset)
         if _strides is None:
-            st, acc = [], self.dtype.itemsize
-            for s in reversed(self.shape):
-                st.append(acc)
-                acc *= max(s, 1)
-            _strides = tuple(reversed(st))
+            _strides = packed_strides(self.shape, self.dtype.itemsize)
         self.strides = tuple(int(s) for s in _strides)
 
     # ---------------------------------------------------------------- interface
@@ -118,12 +136,7 @@ class DeviceArray:
 
     @property
     def contiguous(self):
-        acc = self.dtype.itemsize
-        for s, st in zip(reversed(self.shape), reversed(self.strides)):
-            if s > 1 and st != acc:
-                return False
-            acc *= s
-        return True
+        return c_contiguous(self.shape, self.strides, self.dtype.itemsize)
 
     @property
     def __cuda_array_interface__(self):
@@ -232,6 +245,26 @@ def _interface(obj):
     return int(ptr or 0), str(d["typestr"]), tuple(int(s) for s in d["shape"]), d.get("strides"), d.get("stream")
 
 
+def device_interface(obj):
+    """_interface of a device argument.  A foreign object's pointers come from whichever HIP
+    runtime its library uses, so runtime_check first; a DeviceArray's are libfoto's own."""
+    if not isinstance(obj, DeviceArray):
+        runtime_check()
+    return _interface(obj)
+
+
+def make_image(ptr, code, stride_y, stride_x, divisor, shape, keep):
+    """The _lib.Image of a frame: element strides, ``divisor`` None = 255 for uint8 and 1 otherwise;
+    carries ``.shape`` = (h, w) and keeps ``keep`` alive."""
+    im = _lib.Image()
+    im.data, im.dtype = ptr, code
+    im.stride_y, im.stride_x = stride_y, stride_x
+    im.divisor = float(divisor) if divisor is not None else (255.0 if code == _lib.FOTO_U8 else 1.0)
+    im.shape = (int(shape[0]), int(shape[1]))
+    im._keep = keep
+    return im
+
+
 def stream_handle(stream=None, *objs):
     """The hipStream_t (as an integer; 0 = the legacy null stream) for a call: an explicit
     ``stream`` (an integer handle, or an object with ``.cuda_stream`` such as torch.cuda.Stream),
@@ -260,9 +293,7 @@ def as_image(obj, divisor=None):
     The returned ``_lib.Image`` carries ``.shape`` = (h, w) and keeps ``obj`` alive."""
     if isinstance(obj, _lib.Image):
         return obj
-    if not isinstance(obj, DeviceArray):
-        runtime_check()   # a foreign object's pointers come from whichever runtime its library uses
-    ptr, typestr, shape, strides, _ = _interface(obj)
+    ptr, typestr, shape, strides, _ = device_interface(obj)
     if typestr not in _DTYPES:
         raise TypeError(f"typestr {typestr!r}: frames are uint8 ('|u1'), float32 ('<f4') or float64 ('<f8')")
     if len(shape) != 2:
@@ -275,14 +306,7 @@ def as_image(obj, divisor=None):
     sy, sx = (int(s) for s in strides)
     if sy % item or sx % item:
         raise ValueError(f"byte strides {(sy, sx)} are not multiples of the {item}-byte item size")
-    im = _lib.Image()
-    im.data = ptr
-    im.dtype = code
-    im.stride_y, im.stride_x = sy // item, sx // item
-    im.divisor = float(divisor) if divisor is not None else (255.0 if code == _lib.FOTO_U8 else 1.0)
-    im.shape = (h, w)
-    im._keep = obj
-    return im
+    return make_image(ptr, code, sy // item, sx // item, divisor, (h, w), obj)
 
 
 def _pair(f0, f1, divisor=None):
@@ -294,56 +318,40 @@ def _pair(f0, f1, divisor=None):
 
 def export_target(out, dtype, layout, h, w):
     """(DeviceArray or the caller's object, pointer, dtype code, layout code) of a flow export."""
-    if dtype not in _OUT_DTYPES:
-        dtype = np.dtype(dtype).name
-    if dtype not in _OUT_DTYPES:
-        raise ValueError(f"dtype {dtype!r}: 'float32' or 'float64'")
+    dtype = _dtype_name(dtype, _OUT_DTYPES, None)   # (a wrong dtype is reported before a wrong layout)
     if layout not in _LAYOUTS:
         raise ValueError(f"layout {layout!r}: 'planar' ([3][h][w] = u, v, m) or 'interleaved' ([h][w][2] = (u, v))")
     shape = (3, h, w) if layout == "planar" else (h, w, 2)
-    if out is None:
-        out = DeviceArray(shape, dtype)
-        return out, out.ptr, _OUT_DTYPES[dtype], _LAYOUTS[layout]
-    if not isinstance(out, DeviceArray):
-        runtime_check()
-    ptr, typestr, oshape, strides, _ = _interface(out)
-    want = _typestr(dtype)
-    if typestr != want or tuple(oshape) != shape:
-        raise ValueError(f"out: expected {dtype} of shape {shape}, got {typestr} of shape {tuple(oshape)}")
-    if strides is not None:
-        item, acc = np.dtype(dtype).itemsize, np.dtype(dtype).itemsize
-        for s, st in zip(reversed(shape), reversed(tuple(strides))):
-            if s > 1 and st != acc:
-                raise ValueError("out must be C-contiguous")
-            acc *= s
-    return out, ptr, _OUT_DTYPES[dtype], _LAYOUTS[layout]
+    out, ptr, code = _shaped_target(out, dtype, _OUT_DTYPES, shape, None)
+    return out, ptr, code, _LAYOUTS[layout]
 
 
 _FRAME_DTYPES = {"uint8": _lib.FOTO_U8, "float32": _lib.FOTO_F32, "float64": _lib.FOTO_F64}
+
+
+def _dtype_name(dtype, codes, what):
+    """The key of ``codes`` that ``dtype`` (a name, or anything np.dtype takes) stands for; the
+    ValueError names ``what`` the values are (None: a flow export's own wording)."""
+    if dtype not in codes:
+        dtype = np.dtype(dtype).name
+    if dtype not in codes:
+        raise ValueError(f"dtype {dtype!r}: " + (f"{what} are " if what else "") + " or ".join(repr(k) for k in codes))
+    return dtype
 
 
 def _shaped_target(out, dtype, codes, shape, what):
     """(DeviceArray or the caller's object, pointer, dtype code): a new DeviceArray of ``shape``
     or the caller's ``out``, which must be C-contiguous device memory of that dtype and shape.
     ValueError before the library is touched."""
-    if dtype not in codes:
-        dtype = np.dtype(dtype).name
-    if dtype not in codes:
-        raise ValueError(f"dtype {dtype!r}: {what} are " + " or ".join(repr(k) for k in codes))
+    dtype = _dtype_name(dtype, codes, what)
     if out is None:
         out = DeviceArray(shape, dtype)
         return out, out.ptr, codes[dtype]
-    if not isinstance(out, DeviceArray):
-        runtime_check()
-    ptr, typestr, oshape, strides, _ = _interface(out)
+    ptr, typestr, oshape, strides, _ = device_interface(out)
     if typestr != _typestr(dtype) or tuple(oshape) != tuple(shape):
         raise ValueError(f"out: expected {dtype} of shape {tuple(shape)}, got {typestr} of shape {tuple(oshape)}")
-    if strides is not None:
-        acc = np.dtype(dtype).itemsize
-        for s, st in zip(reversed(shape), reversed(tuple(strides))):
-            if s > 1 and st != acc:
-                raise ValueError("out must be C-contiguous")
-            acc *= s
+    if not c_contiguous(shape, strides, np.dtype(dtype).itemsize):
+        raise ValueError("out must be C-contiguous")
     return out, ptr, codes[dtype]
 
 
@@ -390,19 +398,13 @@ def track_points(points):
 def track_source(points):
     """(pointer, dtype code, M) of device start points: a C-contiguous (M, 2) float32 | float64
     device array.  ValueError before the library is touched."""
-    if not isinstance(points, DeviceArray):
-        runtime_check()
-    ptr, typestr, shape, strides, _ = _interface(points)
+    ptr, typestr, shape, strides, _ = device_interface(points)
     if typestr not in ("<f4", "<f8"):
         raise ValueError(f"points: typestr {typestr!r}; device start points are float32 or float64")
     if len(shape) != 2 or shape[1] != 2:
         raise ValueError(f"points of shape {shape}: a device (M, 2) array of (x, y) start points")
-    if strides is not None:
-        acc = np.dtype(typestr).itemsize
-        for s, st in zip(reversed(shape), reversed(tuple(strides))):
-            if s > 1 and st != acc:
-                raise ValueError("points must be C-contiguous")
-            acc *= s
+    if not c_contiguous(shape, strides, np.dtype(typestr).itemsize):
+        raise ValueError("points must be C-contiguous")
     return ptr, _DTYPES[typestr][0], int(shape[0])
 
 
@@ -413,26 +415,32 @@ def track_target(out, dtype, R, M):
 
 # -------------------------------------------------------------------- convenience
 
+def _bb_solved(f0, f1, Nt, r, convergence_tol, reg_epsilon, max_it, normalize, stream, opts, run, *more):
+    """The frame of bb_flow, bb_path and bb_track: the pair solved with the reference's stop rules
+    on the cached context (foto.bb.cached_solver's, reset to this pair) or, the cache off, on a
+    fresh one, then ``run(solver, stream handle)``; ``more``: further arguments that may name the
+    stream."""
+    from . import bb
+    a, b = _pair(f0, f1)
+    st = stream_handle(stream, f0, f1, *more)
+
+    def go(s):
+        s.iterate(max_it, convergence_tol=convergence_tol, stop_rules=True)
+        return run(s, st)
+
+    return bb.on_context(
+        opts, lambda: bb.cached_solver_device(a, b, Nt, r, reg_epsilon, normalize=normalize, stream=st, **opts),
+        lambda: bb.BBSolver.from_device(a, b, Nt, r=r, reg_epsilon=reg_epsilon, normalize=normalize, stream=st, **opts),
+        go)
+
+
 def bb_flow(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, normalize=False,
             dtype="float32", layout="planar", out=None, stream=None, **opts):
     """benamou_brenier.solve on device frames, the flow left on the device: a context from the
     cache (foto.bb.cached_solver's, reset to this pair), the reference's stop rules, one export.
     Returns the DeviceArray (or ``out``)."""
-    from . import bb
-    a, b = _pair(f0, f1)
-    h, w = a.shape
-    st = stream_handle(stream, f0, f1)
-    if bb._cache_enabled(opts):
-        s = bb.cached_solver_device(a, b, Nt, r, reg_epsilon, normalize=normalize, stream=st, **opts)
-        try:
-            s.iterate(max_it, convergence_tol=convergence_tol, stop_rules=True)
-            return s.flow_device(out=out, dtype=dtype, layout=layout, stream=st)
-        except BaseException:
-            bb.drop_cached(s)
-            raise
-    with bb.BBSolver.from_device(a, b, Nt, r=r, reg_epsilon=reg_epsilon, normalize=normalize, stream=st, **opts) as s:
-        s.iterate(max_it, convergence_tol=convergence_tol, stop_rules=True)
-        return s.flow_device(out=out, dtype=dtype, layout=layout, stream=st)
+    return _bb_solved(f0, f1, Nt, r, convergence_tol, reg_epsilon, max_it, normalize, stream, opts,
+                      lambda s, st: s.flow_device(out=out, dtype=dtype, layout=layout, stream=st))
 
 
 def bb_path(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, frames=None, normalize=False,
@@ -444,25 +452,13 @@ def bb_path(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100
     on the device.  With ``normalize`` the frames are scaled by the frame-0 sum, back to the
     intensity range of ``f0``.  Returns (frames [K][h][w], flow path [Nt-1][3][h][w] or
     [Nt-1][h][w][2]); the last flow record is bb_flow's result."""
-    from . import bb
-    a, b = _pair(f0, f1)
-    st = stream_handle(stream, f0, f1)
     pos = Nt if frames is None else frames
 
-    def run(s):
-        s.iterate(max_it, convergence_tol=convergence_tol, stop_rules=True)
+    def run(s, st):
         fr = s.frames_device(pos, scale=s.sums[0] if normalize else 1.0, out=frames_out, dtype=frame_dtype, stream=st)
         return fr, s.flow_path_device(out=out, dtype=dtype, layout=layout, stream=st)
 
-    if bb._cache_enabled(opts):
-        s = bb.cached_solver_device(a, b, Nt, r, reg_epsilon, normalize=normalize, stream=st, **opts)
-        try:
-            return run(s)
-        except BaseException:
-            bb.drop_cached(s)
-            raise
-    with bb.BBSolver.from_device(a, b, Nt, r=r, reg_epsilon=reg_epsilon, normalize=normalize, stream=st, **opts) as s:
-        return run(s)
+    return _bb_solved(f0, f1, Nt, r, convergence_tol, reg_epsilon, max_it, normalize, stream, opts, run)
 
 
 def bb_track(f0, f1, Nt, points, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, normalize=False,
@@ -471,23 +467,9 @@ def bb_track(f0, f1, Nt, points, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, m
     context, then the trajectories of the device start points ``points`` ((M, 2) float32 |
     float64, (x, y) in pixel-index coordinates) left on the device.  Returns [Nt-1][M][2]
     displacements (``all_steps``) or [1][M][2], the last record: where bb_flow moves each point."""
-    from . import bb
-    a, b = _pair(f0, f1)
-    st = stream_handle(stream, f0, f1, points)
-
-    def run(s):
-        s.iterate(max_it, convergence_tol=convergence_tol, stop_rules=True)
-        return s.track_device(points, out=out, dtype=dtype, all_steps=all_steps, stream=st)
-
-    if bb._cache_enabled(opts):
-        s = bb.cached_solver_device(a, b, Nt, r, reg_epsilon, normalize=normalize, stream=st, **opts)
-        try:
-            return run(s)
-        except BaseException:
-            bb.drop_cached(s)
-            raise
-    with bb.BBSolver.from_device(a, b, Nt, r=r, reg_epsilon=reg_epsilon, normalize=normalize, stream=st, **opts) as s:
-        return run(s)
+    return _bb_solved(f0, f1, Nt, r, convergence_tol, reg_epsilon, max_it, normalize, stream, opts,
+                      lambda s, st: s.track_device(points, out=out, dtype=dtype, all_steps=all_steps, stream=st),
+                      points)
 
 
 def gn_flow(f0, f1, alpha, lam, *, dtype="float32", layout="planar", out=None, stream=None):

@@ -47,18 +47,12 @@ def intensity_error(I, IGT, w, h):
 
 def _dev_f64(x, n, name):
     from . import device as D
-    if not isinstance(x, D.DeviceArray):
-        D.runtime_check()
-    ptr, typestr, shape, strides, _ = D._interface(x)
+    ptr, typestr, shape, strides, _ = D.device_interface(x)
     size = int(np.prod(shape, dtype=np.int64))
     if typestr != "<f8" or size != n:
         raise ValueError(f"{name}: expected {n} float64 values on the device, got {size} of {typestr}")
-    if strides is not None:
-        acc = 8
-        for s, st in zip(reversed(shape), reversed(tuple(strides))):
-            if s > 1 and st != acc:
-                raise ValueError(f"{name}: must be C-contiguous")
-            acc *= s
+    if not D.c_contiguous(shape, strides, 8):
+        raise ValueError(f"{name}: must be C-contiguous")
     return ctypes.c_void_p(ptr)
 
 

@@ -23,13 +23,8 @@ _U8 = {"uint8": _lib.FOTO_U8}
 
 
 def _contiguous(shape, strides, item, what):
-    if strides is None:
-        return
-    acc = item
-    for s, st in zip(reversed(shape), reversed(tuple(strides))):
-        if s > 1 and st != acc:
-            raise ValueError(f"{what} must be C-contiguous")
-        acc *= s
+    if not D.c_contiguous(shape, strides, item):
+        raise ValueError(f"{what} must be C-contiguous")
 
 
 def flow_arg(flow, layout="planar"):
@@ -37,9 +32,7 @@ def flow_arg(flow, layout="planar"):
     shape, dtype or a non-contiguous array, before the library is touched."""
     if layout not in D._LAYOUTS:
         raise ValueError(f"layout {layout!r}: 'planar' ([R][3][h][w] = u, v, m) or 'interleaved' ([R][h][w][2] = (u, v))")
-    if not isinstance(flow, D.DeviceArray):
-        D.runtime_check()
-    ptr, typestr, shape, strides, _ = D._interface(flow)
+    ptr, typestr, shape, strides, _ = D.device_interface(flow)
     if typestr not in ("<f4", "<f8"):
         raise ValueError(f"flow: typestr {typestr!r}; a flow is float32 or float64")
     if len(shape) not in (3, 4):
@@ -65,9 +58,7 @@ def source_arg(src, channels_last=True, divisor=None):
     """(_lib.Image of channel 0, channels, stride_c in elements, has_channel_axis) of a device
     frame: 2-D (h, w), or 3-D (h, w, C) (``channels_last``) / (C, h, w); uint8 / float32 /
     float64, any strides that are multiples of the item size."""
-    if not isinstance(src, D.DeviceArray):
-        D.runtime_check()
-    ptr, typestr, shape, strides, _ = D._interface(src)
+    ptr, typestr, shape, strides, _ = D.device_interface(src)
     if typestr not in D._DTYPES:
         raise ValueError(f"src: typestr {typestr!r}; frames are uint8 ('|u1'), float32 ('<f4') or float64 ('<f8')")
     if len(shape) not in (2, 3):
@@ -75,11 +66,7 @@ def source_arg(src, channels_last=True, divisor=None):
     code, npdt = D._DTYPES[typestr]
     item = np.dtype(npdt).itemsize
     if strides is None:
-        strides, acc = [], item
-        for s in reversed(shape):
-            strides.append(acc)
-            acc *= max(s, 1)
-        strides = tuple(reversed(strides))
+        strides = D.packed_strides(shape, item)
     strides = tuple(int(s) for s in strides)
     if any(s % item for s in strides):
         raise ValueError(f"src: byte strides {strides} are not multiples of the {item}-byte item size")
@@ -92,12 +79,7 @@ def source_arg(src, channels_last=True, divisor=None):
         (C, h, w), (sc, sy, sx) = shape, strides
     if C < 1:
         raise ValueError(f"src of shape {shape} has no channel")
-    im = _lib.Image()
-    im.data, im.dtype = ptr, code
-    im.stride_y, im.stride_x = sy // item, sx // item
-    im.divisor = float(divisor) if divisor is not None else (255.0 if code == _lib.FOTO_U8 else 1.0)
-    im.shape = (int(h), int(w))
-    im._keep = src
+    im = D.make_image(ptr, code, sy // item, sx // item, divisor, (h, w), src)
     return im, int(C), (sc // item if C > 1 else 1), has_c
 
 
@@ -141,9 +123,7 @@ def flow_color(flow, *, layout="planar", maxmotion=0.0, out=None, maxrad=None, s
     fl, R, h, w, batched = flow_arg(flow, layout)
     mr = None
     if maxrad is not None:
-        if not isinstance(maxrad, D.DeviceArray):
-            D.runtime_check()
-        mptr, typestr, mshape, mstrides, _ = D._interface(maxrad)
+        mptr, typestr, mshape, mstrides, _ = D.device_interface(maxrad)
         if typestr != "<f8" or int(np.prod(mshape, dtype=np.int64)) != R:
             raise ValueError(f"maxrad: expected {R} float64 values on the device, got {typestr} of shape {mshape}")
         _contiguous(mshape, mstrides, 8, "maxrad")

@@ -126,6 +126,27 @@ def test_sharded_gauss_deferred(gold, monkeypatch, vr, klim):
     np.testing.assert_allclose(a["crit"], d["crit"], rtol=1e-5, atol=0)
 
 
+@pytest.mark.parametrize("fuse", ["0", "1"])
+def test_sharded_gauss_redo_timed(gold, monkeypatch, fuse):
+    """Every sharded Gauss solve fails (FOTO_GQ_KLIM=1) and is redone at the crit sync: the redo's
+    prox -- the fused k_prox_rhs or, with FOTO_FUSE_PR=0, k_prox -- is the one step the first
+    enqueue, the single-shard redo and the sharded redo share, so with kernel timing on it is
+    counted as in the run that waits for every solve on the host (FOTO_CG_DEFER=0): the guarded
+    no-op launches are dropped, the re-run is timed.  Six iterations, stop rules off."""
+    d = gold("bb_c1.npz")
+    env = {"FOTO_GQ_KLIM": "1", "FOTO_FUSE_PR": fuse}
+    calls = [(6, 0.0, False)]
+    a = _run(d, monkeypatch, env, calls, virtual_ranks=2, timing=True)
+    b = _run(d, monkeypatch, {**env, "FOTO_CG_DEFER": "0"}, calls, virtual_ranks=2, timing=True)
+    monkeypatch.delenv("FOTO_CG_DEFER", raising=False)
+    n_prox = [x["stats"]["kernels"].get("prox", {"n": 0})["n"] for x in (a, b)]
+    print("cg_redo", a["stats"]["cg_redo"], b["stats"]["cg_redo"], "prox n", n_prox)
+    _same(a, b)
+    assert len(a["crit"]) == 6
+    assert a["stats"]["cg_redo"] == 6 and b["stats"]["cg_redo"] == 6
+    assert n_prox[0] == n_prox[1] > 0
+
+
 @pytest.mark.parametrize("klim", [None, "200"])
 def test_host_readback_stores(gold, monkeypatch, klim):
     """The crit pair and the Gauss solve's header reach the host as stores of the kernels
