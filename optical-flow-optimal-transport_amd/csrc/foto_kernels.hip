@@ -505,14 +505,20 @@ hipError_t launch_init_mu(const Geo& g, const double* rho0, const double* rhoT, 
 // closed forms, in an algebraically identical but cheaper form: (cos, sin)(atan2(b2, b1))
 // = (b1, b2) / |b|, x^(1/3) -> cbrt(x), (a+1)^3 and m^(3/2) by products.  Each changes a
 // result by at most an ulp or two (checked to 1e-12 against the reference's stepB in
-// tests/golden/stepb.npz, including both branches and the boundary); stepB runs once per
+// tests/golden/stepb.npz, including both branches and the boundary, and held to 4 x the
+// reference formulas' own error against the exact projection in tests/test_gpu_projk.py;
+// DESIGN.md 3.2 has the figures); stepB runs once per
 // outer iteration on every voxel, and atan2 / cos / sin / pow would dominate it.
 // rare branch (a < -1, small |b|): kept out of line so its acos / cos do not inflate the
 // register allocation of the kernels that inline project_K
 __device__ __noinline__ double proj_trig_z(double al, double rho) {
     const double m = -al - 1.0;
     const double sm = sqrt(m);
-    return 1.632993161855452 * sm * cos(0.3333333333333333 * acos(1.8371173070873836 * rho / (m * sm)));
+    // on the seam with the cubic branch the argument is 1 and can round an ulp or two above it
+    // (acos -> NaN; the projection itself is smooth there): capped by a select, which unlike
+    // fmin lets a NaN argument through
+    const double x = 1.8371173070873836 * rho / (m * sm);
+    return 1.632993161855452 * sm * cos(0.3333333333333333 * acos(x > 1.0 ? 1.0 : x));
 }
 
 // S^(1/3) and S^(-1/3) for finite S > 0 without the library cbrt and a division: S = m 2^e
@@ -546,9 +552,12 @@ __device__ __forceinline__ void project_K(double al, double b1, double b2, doubl
     const double ap1 = al + 1.0;
     double aH, rH;
     if (-32.0 * (ap1 * ap1 * ap1) - 108.0 * (rho * rho) < 0.0) {
-        const double S = 0.3535533905932738 * rho +
-                         0.16666666666666666 * sqrt(1.3333333333333333 * (al * al * al) + 4.0 * (al * al) +
-                                                    4.5 * (rho * rho) + 4.0 * al + 1.3333333333333333);
+        // the polynomial is (4 (a+1)^3 + 13.5 rho^2) / 3 expanded as the reference writes it: > 0
+        // in this branch, but next to the seam (a < -1) its terms cancel and the sum can round
+        // below 0 (sqrt -> NaN).  Floored by a select (a NaN passes, which fmax would swallow)
+        const double D = 1.3333333333333333 * (al * al * al) + 4.0 * (al * al) + 4.5 * (rho * rho) + 4.0 * al +
+                         1.3333333333333333;
+        const double S = 0.3535533905932738 * rho + 0.16666666666666666 * sqrt(D < 0.0 ? 0.0 : D);
         double c, ic;
         if (S > 0.0 && S <= 1.7976931348623157e308) {
             cbrt_pair(S, c, ic);
@@ -569,9 +578,10 @@ __device__ __forceinline__ void project_K(double al, double b1, double b2, doubl
         const double ir = 1.0 / rho;
         o1 = rH * (b1 * ir);
         o2 = rH * (b2 * ir);
-    } else {   // atan2(+-0, +0) = +-0, atan2(+-0, -0) = +-pi
+    } else {   // atan2(+-0, +0) = +-0, atan2(+-0, -0) = +-pi: rH cos = +-rH, rH sin = a zero of
+               // rH's sign times b2's (the reference's rH sin(+-pi) is rH * +-1.2e-16 instead)
         o1 = signbit(b1) ? -rH : rH;
-        o2 = 0.0;
+        o2 = rH * b2;
     }
 }
 
