@@ -420,6 +420,56 @@ int foto_bb_track(foto_bb_ctx* c, const double* pts, int64_t M, int all_steps, d
 int foto_bb_track_dev(foto_bb_ctx* c, const void* pts, int pts_dtype, int64_t M, int all_steps, void* out,
                       int dtype, void* stream);
 
+/* Transport report: how good the transport behind the exports above is, and what it costs -- per
+ * time plane n = 0..Nt-1 the sums, over the plane's Nx*Ny voxels, of FOTO_REPORT_COLS terms of the
+ * last completed outer iteration's mu = (rho, m1, m2) and g = (g_t, g_x, g_y) = grad_st phi
+ * (operators.py:114-127), h = dt = 1.  out: C-contiguous double[Nt][FOTO_REPORT_COLS].  Per voxel,
+ * in exactly this operation order (every term is bit-identical to its numpy restatement; only the
+ * sums are taken in another -- fixed -- order):
+ *   MASS    rho                                   np.sum(rhon[n,:]), benamou_brenier.py:266
+ *   KINETIC rho > 0 ? (m1*m1 + m2*m2) / (rho + rho) : 0       the action density |m|^2 / (2 rho)
+ *   VACUUM  rho > 0 ? 0 : (m1*m1 + m2*m2)         momentum left where the clamp of :232 emptied
+ *                                                 the density (a NaN rho lands here, and in MASS)
+ *   CONT    c*c, c = row k of div_st @ mu (operators.py:129-142, COO order t, x, y), then
+ *           c -= (rho0 - rho) on plane 0 and c += (rhoT - rho) on plane Nt-1: the F of
+ *           solve_benamou_brenier_step (benamou_brenier.py:64-82) with q = 0, the bits of
+ *           foto_bb_rhs(mu, 0, ...) -- the continuity equation and the two boundary frames
+ *   HJ_NUM  rho * fabs(g_t + 0.5 * (g_x*g_x + g_y*g_y))       benamou_brenier.py:246-247
+ *   HJ_DEN  rho * (g_x*g_x + g_y*g_y)                         benamou_brenier.py:248
+ *   DUAL    plane 0: -(phi * rho0); plane Nt-1: phi * rhoT; other planes: 0
+ *   DIST_T  (rho - rhoT) * (rho - rhoT)           utils.IE(Nx, Ny, rhoT, rhon[n]) of :265 is
+ *                                                 255 * sqrt(DIST_T / (Nx*Ny))
+ * sqrt(sum_n HJ_NUM / (sum_n HJ_DEN + 1e-10)) is the crit of that iteration (:249), up to
+ * summation order.  sum_n DUAL = sum phi_{Nt-1} rhoT - sum phi_0 rho0 is the dual estimate of the
+ * action that the trapezoid of KINETIC over n estimates primally; the two agree only at
+ * convergence and for equal masses of rho0 and rhoT -- neither is the other's check.
+ * One kernel launch per in-process shard, one read of the four fields; a plane's eight sums are
+ * reduced in an order that depends on (Nx, Ny) alone -- the same bits for any virtual_ranks, from
+ * call to call, and a function of that plane's data and its t-neighbours only.  State rules: those
+ * of foto_bb_flow_path (FOTO_ERR_STATE before any outer iteration, from the one-in-flight loop's
+ * callback, on an RCCL or a broken context).  Neither entry changes statistics or anything a later
+ * foto_bb_iterate reads; the scratch is a grow-only buffer of the context, made on first use.
+ * Host entry: one device-to-host copy of Nt * 64 bytes.  Device entry: the stream contract of the
+ * device-buffer section; `out` is checked to be 8-byte-aligned device memory of the context's
+ * device before anything is enqueued (FOTO_ERR_ARG, `out` untouched); the kernels write `out`
+ * directly, without a host synchronisation.  FOTO_ERR_ARG: a null pointer.                       */
+#define FOTO_REPORT_COLS 8
+#define FOTO_REPORT_MASS 0
+#define FOTO_REPORT_KINETIC 1
+#define FOTO_REPORT_VACUUM 2
+#define FOTO_REPORT_CONT 3
+#define FOTO_REPORT_HJ_NUM 4
+#define FOTO_REPORT_HJ_DEN 5
+#define FOTO_REPORT_DUAL 6
+#define FOTO_REPORT_DIST_T 7
+int foto_bb_report(foto_bb_ctx* c, double* out);                          /* host [Nt][8]   */
+int foto_bb_report_dev(foto_bb_ctx* c, double* out, void* stream);        /* device [Nt][8] */
+/* Test entry, no context: the same kernel on one shard from host arrays (mu3 = [rho; m1; m2], each
+ * Nt*Nx*Ny; phi; rho0, rhoT: Nx*Ny) -- benamou_brenier.py:64-82, 246-248, 262-267 as above.
+ * FOTO_ERR_ARG before any device is touched: a null pointer, Nt < 2, Nx < 1 or Ny < 1.           */
+int foto_report_from_state(const double* mu3, const double* phi, const double* rho0, const double* rhoT, int Nt,
+                           int Nx, int Ny, double* out);
+
 /* foto_gn_plan_solve (classical.py:68-130) on device frames, the solution exported to `out` as
  * foto_bb_flow_dev does (planar: u, v, m).  Same PCG launches, prediction, result and return
  * codes as foto_gn_plan_solve; it neither makes nor touches the plan's pinned host staging.  */

@@ -247,11 +247,15 @@ struct foto_bb_ctx {
     // between the launches of a path whose planes lie in several shards (virtual ranks)
     enum { TRK_PTS = 0, TRK_OUT = 1, TRK_POS = 2 };
     DevScratch trk[3];
+    // the transport report (foto_bb_report / _dev), grow-only, made on first use: the host entry's
+    // staged table [Nt][8] | the plane partials [Nt][8][pieces] | Nt tickets (zero between launches)
+    DevScratch rep;
     ~foto_bb_ctx() {
         if (sc) (void)hipStreamSynchronize(sc);
         if (s) (void)hipStreamSynchronize(s);   // (before the shards free their buffers)
         sh.clear();
         for (DevScratch& b : trk) if (b.p) (void)hipFree(b.p);
+        if (rep.p) (void)hipFree(rep.p);
         if (nc) (void)ncclCommDestroy(nc);
         if (hS) (void)hipHostFree(hS);
         for (double* h : hgath) if (h) (void)hipHostFree(h);
@@ -1302,6 +1306,48 @@ static int frames_launch(foto_bb_ctx* c, const Completed& k, const double* s, in
     return 0;
 }
 
+// ------------------------------------------------------------------ transport report
+// foto_bb_report / _dev: k_report once per in-process shard on the completed iteration's mu and phi
+// (k.of()), the t-neighbour planes of a shard's edges taken from the shards that own them.  The
+// table goes to `out` (device memory), or to the scratch's staging table when out is null
+// (*staged).  Touches neither the statistics nor anything the outer loop reads.
+static int report_run(foto_bb_ctx* c, const Completed& k, double* out, double** staged) {
+    const int64_t nxy = (int64_t)c->Nx * c->Ny;
+    const size_t ntab = (size_t)c->Nt * FOTO_REPORT_COLS, npart = ntab * (size_t)report_pieces(nxy);
+    const size_t bytes = (ntab + npart) * sizeof(double) + (size_t)c->Nt * sizeof(unsigned);
+    if (c->rep.cap < bytes) {
+        FOTO_TRY(c->rep.reserve(bytes, c->s));
+        FOTO_HIP_CHECK(hipMemsetAsync((double*)c->rep.p + ntab + npart, 0, (size_t)c->Nt * sizeof(unsigned), c->s));
+    }
+    double* const table = (double*)c->rep.p;
+    double* const part = table + ntab;
+    unsigned* const ticket = (unsigned*)(part + npart);
+    if (!out) out = table;
+    if (staged) *staged = table;
+    for (auto& sp : c->sh) {
+        const Shard& s = *sp;
+        const Rot& ks = k.of(s);
+        ReportIn in{};
+        in.rho = ks.mu[0]; in.m1 = ks.mu[1]; in.m2 = ks.mu[2]; in.phi = ks.phi;
+        in.rho0 = s.rho0; in.rhoT = s.rhoT;
+        if (s.g.t0 > 0) {
+            const Shard* lo = plane_owner(c, s.g.t0 - 1);
+            if (!lo) { set_error("report: no local shard owns plane %d", s.g.t0 - 1); return FOTO_ERR_STATE; }
+            const int64_t o = (int64_t)(s.g.t0 - 1 - lo->g.t0) * nxy;
+            in.rho_lo = k.of(*lo).mu[0] + o;
+            in.phi_lo = k.of(*lo).phi + o;
+        }
+        if (s.g.t0 + s.g.nloc < c->Nt) {
+            const Shard* hi = plane_owner(c, s.g.t0 + s.g.nloc);
+            if (!hi) { set_error("report: no local shard owns plane %d", s.g.t0 + s.g.nloc); return FOTO_ERR_STATE; }
+            in.rho_hi = k.of(*hi).mu[0];
+            in.phi_hi = k.of(*hi).phi;
+        }
+        FOTO_HIP_CHECK(launch_report(s.g, in, part, ticket, out, c->s));
+    }
+    return 0;
+}
+
 }  // namespace foto
 
 // ============================================================================ C ABI (BB)
@@ -1714,6 +1760,36 @@ int foto_bb_track_dev(foto_bb_ctx* c, const void* pts, int pts_dtype, int64_t M,
         FOTO_TRY(c->trk[foto_bb_ctx::TRK_POS].reserve(np * sizeof(double), c->s));
     FOTO_TRY(c->link.enter((hipStream_t)stream, c->s));   // (before the first read of `pts` / write of `out`)
     FOTO_TRY(track_run(c, k, pts, pts_dtype, M, all_steps, out, dtype));
+    return c->link.leave(c->s, (hipStream_t)stream);
+}
+
+int foto_bb_report(foto_bb_ctx* c, double* out) {
+    const char* who = "foto_bb_report";
+    FOTO_TRY(path_state_check(c, who));
+    if (!out) { set_error("%s: null pointer", who); return FOTO_ERR_ARG; }
+    Completed k;
+    FOTO_TRY(completed_state(c, who, &k));
+    double* table = nullptr;
+    FOTO_TRY(report_run(c, k, nullptr, &table));
+    FOTO_HIP_CHECK(hipMemcpyAsync(out, table, (size_t)c->Nt * FOTO_REPORT_COLS * sizeof(double),
+                                  hipMemcpyDeviceToHost, c->s));
+    FOTO_HIP_CHECK(hipStreamSynchronize(c->s));
+    return 0;
+}
+
+int foto_bb_report_dev(foto_bb_ctx* c, double* out, void* stream) {
+    const char* who = "foto_bb_report_dev";
+    FOTO_TRY(path_state_check(c, who));
+    if (!out) { set_error("%s: null pointer", who); return FOTO_ERR_ARG; }
+    if ((uintptr_t)out % sizeof(double) != 0) {
+        set_error("%s: out %p is not aligned to its 8-byte element", who, (void*)out);
+        return FOTO_ERR_ARG;
+    }
+    FOTO_TRY(dev_ptr_check(out, (size_t)c->Nt * FOTO_REPORT_COLS * sizeof(double), stream_device(c->s), who, "out"));
+    Completed k;
+    FOTO_TRY(completed_state(c, who, &k));
+    FOTO_TRY(c->link.enter((hipStream_t)stream, c->s));   // (before the first write of `out`)
+    FOTO_TRY(report_run(c, k, out, nullptr));
     return c->link.leave(c->s, (hipStream_t)stream);
 }
 

@@ -278,6 +278,36 @@ int foto_track_from_phi(const double* phi, int Nt, int Nx, int Ny, const double*
     return S.sync();
 }
 
+int foto_report_from_state(const double* mu3, const double* phi, const double* rho0, const double* rhoT, int Nt,
+                           int Nx, int Ny, double* out) {
+    const char* who = "foto_report_from_state";
+    if (!mu3 || !phi || !rho0 || !rhoT || !out) { set_error("%s: null pointer", who); return FOTO_ERR_ARG; }
+    if (Nt < 2 || Nx < 1 || Ny < 1) {
+        set_error("%s: grid (Nt=%d, Nx=%d, Ny=%d) needs Nt >= 2, Nx >= 1, Ny >= 1", who, Nt, Nx, Ny);
+        return FOTO_ERR_ARG;
+    }
+    if ((int64_t)Nx * Ny >= ((int64_t)1 << 31)) { set_error("%s: more than 2^31 voxels per plane", who); return FOTO_ERR_ARG; }
+    Scope S;
+    FOTO_TRY(S.init());
+    const Geo g = make_geo(Nt, Nx, Ny);
+    const size_t N = (size_t)Nt * g.nxy, ntab = (size_t)Nt * FOTO_REPORT_COLS;
+    const size_t npart = ntab * (size_t)report_pieces(g.nxy);
+    double *mu, *ph, *r0, *rT, *scr;
+    FOTO_TRY(S.up(mu3, 3 * N, &mu));
+    FOTO_TRY(S.up(phi, N, &ph));
+    FOTO_TRY(S.up(rho0, g.nxy, &r0));
+    FOTO_TRY(S.up(rhoT, g.nxy, &rT));
+    FOTO_TRY(S.dev(ntab + npart + (size_t)Nt, &scr));   // table | partials | tickets (one double's room each)
+    unsigned* ticket = (unsigned*)(scr + ntab + npart);
+    FOTO_HIP_CHECK(hipMemsetAsync(ticket, 0, (size_t)Nt * sizeof(unsigned), S.s));
+    ReportIn in{};
+    in.rho = mu; in.m1 = mu + N; in.m2 = mu + 2 * N; in.phi = ph;
+    in.rho0 = r0; in.rhoT = rT;
+    FOTO_HIP_CHECK(launch_report(g, in, scr + ntab, ticket, scr, S.s));
+    FOTO_TRY(S.down(out, scr, ntab));
+    return S.sync();
+}
+
 // ----------------------------------------------------------------------------- GN
 
 int foto_gn_apply(const double* f1, const double* f2, int w, int h, double alpha, double lam, const double* x3,

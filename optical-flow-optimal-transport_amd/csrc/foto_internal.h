@@ -213,6 +213,22 @@ hipError_t launch_init_mu(const Geo& g, const double* rho0, const double* rhoT, 
 hipError_t launch_rhs(const Geo& g, const double* mut, const double* mux, const double* muy, const double* qt,
                       const double* qx, const double* qy, const double* rho0, const double* rhoT, double r,
                       double* F, RedBuf rb, double* gath, int rank, hipStream_t s);
+// The transport report (foto_bb_report / _dev, foto_report_from_state): out[t][FOTO_REPORT_COLS]
+// for the shard's planes t in [t0, t0 + nloc), one launch.  A block sums one piece of one plane;
+// the pieces are a function of the plane size alone, so a plane's sums do not depend on the
+// sharding.  part: Nt * FOTO_REPORT_COLS * report_pieces(nxy) doubles, laid out
+// [plane][col][piece] (global plane); ticket: Nt counters, zero before the launch and left at zero.
+constexpr int REPORT_PIECE = 2048;   // voxels of a plane per block
+inline int report_pieces(int64_t nxy) { return (int)((nxy + REPORT_PIECE - 1) / REPORT_PIECE); }
+struct ReportIn {
+    const double *rho, *m1, *m2, *phi;   // the shard's mu and phi, at local plane 0
+    // the plane below the shard's first / above its last one, from the shard that owns it (null
+    // at the global ends): never mu's halo planes, which the fused path does not exchange
+    const double *rho_lo, *rho_hi, *phi_lo, *phi_hi;
+    const double *rho0, *rhoT;           // one plane each
+};
+hipError_t launch_report(const Geo& g, const ReportIn& in, double* part, unsigned* ticket, double* out,
+                         hipStream_t s);
 // stencil CG iteration kernels
 hipError_t launch_cg_dir(const Geo& g, int k, const double* rvec, const double* pold, double* pnew,
                          const CGArgs& a, CGScal* S, RedBuf rb, const double* gath_rr, double* gath_pap,

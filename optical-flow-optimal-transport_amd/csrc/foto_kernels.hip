@@ -475,6 +475,132 @@ hipError_t launch_rhs(const Geo& g, const double* mut, const double* mux, const 
     return hipGetLastError();
 }
 
+// ----------------------------------------------------------------------------- transport report
+
+// foto_bb_report: FOTO_REPORT_COLS sums per time plane over (rho, m1, m2) = mu and g = grad_st phi
+// (include/foto.h has the terms; benamou_brenier.py:64-82, 246-248, 262-267).  One read of the
+// four fields.  A block owns one piece -- REPORT_PIECE consecutive voxels -- of one local plane (the
+// grid is pieces x nloc), so the pieces of a plane depend on (Nx, Ny) alone and a plane's sums are
+// the same bits however the planes are sharded.  Per plane: block partials to part[plane][col][piece]
+// (write-through), a ticket of the plane's own, and the block whose add comes last sums the
+// plane's partials in piece order with the fixed tree (grid_reduce_last's hand-off, one ticket
+// per plane instead of one per launch).  No floating-point atomics.
+// The t-neighbours of a shard's edge planes come through in.rho_lo / rho_hi / phi_lo / phi_hi
+// (mu's halo planes are not exchanged on the fused path).  Ordinary loads: the state is read
+// again by the next outer iteration.
+constexpr int REP_VPT = REPORT_PIECE / NT;   // voxels per thread
+__global__ __launch_bounds__(NT) void k_report(Geo g, ReportIn in, double* __restrict__ part, unsigned* ticket,
+                                               double* __restrict__ out) {
+    constexpr int K = FOTO_REPORT_COLS;
+    __shared__ double sh[K * (NT / 64)];
+    __shared__ int is_last;
+    // block -> (piece, plane).  Which block sums which piece does not enter the result, so the
+    // map is free: the blocks go to the 8 XCDs round robin, each with its own L2; every XCD gets
+    // a contiguous range of (piece, plane) items, plane fastest, so the three blocks that read a
+    // piece of plane l (as t-1, t, t+1) and the blocks of the pieces next to it run close together
+    // behind one L2 (152 -> 139 us at 640 x 480 x 32 against piece = blockIdx.x, plane = blockIdx.y)
+    const int pieces = gridDim.x;
+    int l, piece;
+    {
+        constexpr int NXCD = 8;
+        const int nb = gridDim.x * gridDim.y, b = blockIdx.y * gridDim.x + blockIdx.x;
+        const int per = nb / NXCD, rem = nb % NXCD, xcd = b % NXCD;
+        const int item = xcd * per + min(xcd, rem) + b / NXCD;
+        piece = item / g.nloc;
+        l = item - piece * g.nloc;
+    }
+    const int t = g.t0 + l;
+    const int64_t nxy = g.nxy;
+    const bool first = t == 0, last = t == g.Nt - 1;
+    // the plane and its t-neighbours: the shard's own planes, or at its edges the plane the caller
+    // passed (at the global ends the plane itself stands in: the value is selected away below)
+    const double* const rc = in.rho + (int64_t)l * nxy;
+    const double* const pc = in.phi + (int64_t)l * nxy;
+    const double* const m1c = in.m1 + (int64_t)l * nxy;
+    const double* const m2c = in.m2 + (int64_t)l * nxy;
+    const double* const rm = l > 0 ? rc - nxy : first ? rc : in.rho_lo;
+    const double* const pm = l > 0 ? pc - nxy : first ? pc : in.phi_lo;
+    const double* const rp = l + 1 < g.nloc ? rc + nxy : last ? rc : in.rho_hi;
+    const double* const pp1 = l + 1 < g.nloc ? pc + nxy : last ? pc : in.phi_hi;
+    const double* const r0 = first ? in.rho0 : in.rhoT;   // (used on plane 0 only; elsewhere a load of the line rhoT's brings)
+    double v[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = 0.0;
+    // (x, y) of the thread's first voxel by one division, of the next ones (NT voxels on) by steps
+    const int64_t off0 = (int64_t)piece * REPORT_PIECE + threadIdx.x;
+    const int sy = NT / g.Nx, sx = NT - sy * g.Nx;
+    int y = (int)(off0 / g.Nx), x = (int)(off0 - (int64_t)y * g.Nx);
+#pragma unroll
+    for (int e = 0; e < REP_VPT; ++e, x += sx, y += sy) {
+        if (x >= g.Nx) { x -= g.Nx; ++y; }
+        const int64_t off = off0 + (int64_t)e * NT;
+        if (off >= nxy) continue;
+        // every load is unconditional, from an index clamped into the plane, so that they issue
+        // together; the edge zeros of the stencils are selected afterwards
+        const bool hx = x > 0, hX = x < g.Nx - 1, hy = y > 0, hY = y < g.Ny - 1;
+        const int64_t oxm = hx ? off - 1 : off, oxp = hX ? off + 1 : off;
+        const int64_t oym = hy ? off - g.Nx : off, oyp = hY ? off + g.Nx : off;
+        const double rho = rc[off], rho_m = rm[off], rho_p = rp[off];
+        const double m1 = m1c[off], m1_m = m1c[oxm], m1_p = m1c[oxp];
+        const double m2 = m2c[off], m2_m = m2c[oym], m2_p = m2c[oyp];
+        const double c = pc[off], c_tm = pm[off], c_tp = pp1[off];
+        const double c_xm = pc[oxm], c_xp = pc[oxp], c_ym = pc[oym], c_yp = pc[oyp];
+        const double rT = in.rhoT[off], rA = r0[off];
+        const double gt = d1w(t, g.Nt, !first ? c_tm : 0.0, c, !last ? c_tp : 0.0);
+        const double gx = d1w(x, g.Nx, hx ? c_xm : 0.0, c, hX ? c_xp : 0.0);
+        const double gy = d1w(y, g.Ny, hy ? c_ym : 0.0, c, hY ? c_yp : 0.0);
+        // the continuity residual: div_st_row's three blocks on mu, then k_rhs's boundary planes with q = 0
+        double cr = 0.0;
+        acc_d1w(cr, t, g.Nt, !first ? rho_m : 0.0, rho, !last ? rho_p : 0.0);
+        acc_d1w(cr, x, g.Nx, hx ? m1_m : 0.0, m1, hX ? m1_p : 0.0);
+        acc_d1w(cr, y, g.Ny, hy ? m2_m : 0.0, m2, hY ? m2_p : 0.0);
+        if (first) cr -= rA - rho;
+        if (last) cr += rT - rho;
+        const double mm = m1 * m1 + m2 * m2, gg = gx * gx + gy * gy, dT = rho - rT;
+        const bool pos = rho > 0.0;   // (false for NaN: a NaN density counts as emptied)
+        v[FOTO_REPORT_MASS] += rho;
+        v[FOTO_REPORT_KINETIC] += pos ? mm / (rho + rho) : 0.0;
+        v[FOTO_REPORT_VACUUM] += pos ? 0.0 : mm;
+        v[FOTO_REPORT_CONT] += cr * cr;
+        v[FOTO_REPORT_HJ_NUM] += rho * fabs(gt + 0.5 * gg);
+        v[FOTO_REPORT_HJ_DEN] += rho * gg;
+        v[FOTO_REPORT_DUAL] += first ? -(c * rA) : last ? c * rT : 0.0;
+        v[FOTO_REPORT_DIST_T] += dT * dT;
+    }
+    block_sum<K>(v, sh);
+    double* const pp = part + (int64_t)t * K * pieces;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            __hip_atomic_store(&pp[(int64_t)k * pieces + piece], v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned tk = __hip_atomic_fetch_add(&ticket[t], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        is_last = (tk == (unsigned)(pieces - 1));
+    }
+    __syncthreads();
+    if (!is_last) return;
+    double acc[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = 0.0;
+    for (int p = threadIdx.x; p < pieces; p += NT) {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            acc[k] += __hip_atomic_load(&pp[(int64_t)k * pieces + p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    block_sum<K>(acc, sh);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) out[(int64_t)t * K + k] = acc[k];
+        __hip_atomic_store(&ticket[t], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+hipError_t launch_report(const Geo& g, const ReportIn& in, double* part, unsigned* ticket, double* out,
+                         hipStream_t s) {
+    k_report<<<dim3(report_pieces(g.nxy), g.nloc), NT, 0, s>>>(g, in, part, ticket, out);
+    return hipGetLastError();
+}
+
 // mu_rho[n] = (1 - n/(Nt-1)) rho0 + (n/(Nt-1)) rhoT, m = 0, q = 0 (benamou_brenier.py:191-194)
 __global__ __launch_bounds__(NT) void k_init_mu(Geo g, const double* __restrict__ rho0,
                                                 const double* __restrict__ rhoT, double* mut, double* mux,

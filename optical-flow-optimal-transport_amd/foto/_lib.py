@@ -189,6 +189,10 @@ SIGNATURES = {
     "foto_track_from_phi": (_I, [_D, _I, _I, _I, _D, ctypes.c_int64, _I, _D]),
     "foto_bb_track": (_I, [_P, _D, ctypes.c_int64, _I, _D]),
     "foto_bb_track_dev": (_I, [_P, _P, _I, ctypes.c_int64, _I, _P, _I, _P]),
+    # the transport report: per-plane mass, action, continuity and HJ residual sums
+    "foto_bb_report": (_I, [_P, _D]),
+    "foto_bb_report_dev": (_I, [_P, _P, _P]),
+    "foto_report_from_state": (_I, [_D, _D, _D, _D, _I, _I, _I, _D]),
     "foto_gn_plan_solve_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _P, _I, _I, _P,
                                     ctypes.POINTER(_I)]),
     "foto_warp_dev": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),

@@ -203,6 +203,25 @@ class BBSolver:
                                               ctypes.c_void_p(D.stream_handle(stream, out, points))))
         return out
 
+    # -------------------------------------------------------------- transport report
+    def report(self):
+        """The TransportReport (foto.report) of the last completed outer iteration: per time
+        plane the mass, action, vacuum momentum, continuity and Hamilton-Jacobi residual sums
+        (foto_bb_report), one 64 Nt-byte download.  State rules of flow_path()."""
+        from .report import REPORT_COLS, TransportReport
+        out = np.empty((self.Nt, REPORT_COLS))
+        self._check(self._L.foto_bb_report(self._ctx, dptr(out)))
+        return TransportReport(out, self.Nt, self.Nx, self.Ny)
+
+    def report_device(self, out=None, stream=None):
+        """report()'s table left on the device (foto_bb_report_dev): a DeviceArray (or ``out``,
+        any C-contiguous device array) (Nt, 8) float64, without a host synchronisation."""
+        from . import device as D
+        out, ptr = D.report_target(out, self.Nt)
+        self._check(self._L.foto_bb_report_dev(self._ctx, ctypes.c_void_p(ptr),
+                                               ctypes.c_void_p(D.stream_handle(stream, out))))
+        return out
+
     def _check(self, rc):
         return check(rc, self._L)
 

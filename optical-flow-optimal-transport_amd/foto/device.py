@@ -413,6 +413,14 @@ def track_target(out, dtype, R, M):
     return _shaped_target(out, dtype, _OUT_DTYPES, (int(R), int(M), 2), "track records")
 
 
+def report_target(out, Nt):
+    """(out, pointer) of a transport-report export: a new DeviceArray or the caller's ``out``,
+    C-contiguous float64 of shape (Nt, 8).  ValueError before the library is touched."""
+    from .report import REPORT_COLS
+    out, ptr, _ = _shaped_target(out, "float64", {"float64": _lib.FOTO_F64}, (int(Nt), REPORT_COLS), "report tables")
+    return out, ptr
+
+
 # -------------------------------------------------------------------- convenience
 
 def _bb_solved(f0, f1, Nt, r, convergence_tol, reg_epsilon, max_it, normalize, stream, opts, run, *more):
@@ -470,6 +478,14 @@ def bb_track(f0, f1, Nt, points, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, m
     return _bb_solved(f0, f1, Nt, r, convergence_tol, reg_epsilon, max_it, normalize, stream, opts,
                       lambda s, st: s.track_device(points, out=out, dtype=dtype, all_steps=all_steps, stream=st),
                       points)
+
+
+def bb_report(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, normalize=False, stream=None,
+              **opts):
+    """bb_flow's solve on the cached context, then the transport report of its last outer
+    iteration instead of the flow: a foto.report.TransportReport (BBSolver.report())."""
+    return _bb_solved(f0, f1, Nt, r, convergence_tol, reg_epsilon, max_it, normalize, stream, opts,
+                      lambda s, st: s.report())
 
 
 def gn_flow(f0, f1, alpha, lam, *, dtype="float32", layout="planar", out=None, stream=None):

@@ -125,6 +125,19 @@ def track_from_phi(phi, Nt, Nx, Ny, points, all_steps=True):
     return out
 
 
+def report_from_state(mu, phi, rho0, rhoT, Nt, Nx, Ny):
+    """The (Nt, 8) table of foto_bb_report from a caller's state, without a context: ``mu`` =
+    [rho; m1; m2] and ``phi`` of Nt*Nx*Ny voxels, ``rho0`` / ``rhoT`` of Nx*Ny.  The same kernel,
+    so the table has the bits of BBSolver.report() on that state (foto.report has the columns)."""
+    from .report import REPORT_COLS
+    N = Nt * Nx * Ny
+    a, p = f64(mu, 3 * N, "mu"), f64(phi, N, "phi")
+    r0, rT = f64(rho0, Nx * Ny, "rho0"), f64(rhoT, Nx * Ny, "rhoT")
+    out = np.empty((max(Nt, 0), REPORT_COLS))
+    check(lib().foto_report_from_state(dptr(a), dptr(p), dptr(r0), dptr(rT), Nt, Nx, Ny, dptr(out)))
+    return out
+
+
 def _bc(bc):
     if bc not in ("N", "D"):
         raise NotImplementedError("These boundary conditions are not implemented")
