@@ -2,7 +2,8 @@
 // foto_dct.hip, foto_probe.hip), the fixed-order block sum (foto_dev.hip, foto_eval.hip), the
 // trajectory step (k_traj, k_track: foto_kernels.hip) and the backward warp (k_warp:
 // foto_eval.hip, k_render_warp: foto_render.hip).  Outputs that are documented as bit-identical
-// to each other are so because they run the one definition here.
+// to each other are so because they run the one definition here.  The sums across blocks and
+// the wave primitives under them are shared the same way in foto_reduce.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -135,20 +135,8 @@ __device__ __forceinline__ void gq_load_bins(GqBins* L, const GqBins* __restrict
 }
 
 __device__ __forceinline__ double gq_uniform_sum(double v) {   // wave total, the same in every lane
-    v += dbl_dpp<0x111>(v);
-    v += dbl_dpp<0x112>(v);
-    v += dbl_dpp<0x114>(v);
-    v += dbl_dpp<0x118>(v);
+    dpp_row_sums(v);
     return ((dbl_readlane(v, 15) + dbl_readlane(v, 31)) + dbl_readlane(v, 47)) + dbl_readlane(v, 63);
-}
-
-// DPP on the rows in ROWMASK only (the other rows read 0)
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ double dbl_dpp_rows(double v) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffLL), CTRL, ROWMASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROWMASK, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
 
 // ---------------------------------------------------------------------------- 1. histogram (bin order)
@@ -387,17 +375,14 @@ __global__ __launch_bounds__(256) void k_gq_hist_perm(SpecTab T, const double* _
                 }
             }
         }
-        // wave totals in lane 63: row_shr tree (lane 15 of each row holds its row), then
+        // wave totals in lane 63: the row tree (lane 15 of each row holds its row), then
         // row_bcast:15 into rows 1, 3 and row_bcast:31 into rows 2, 3: (R3 + R2) + (R1 + R0)
 #pragma unroll
         for (int m = 0; m < GQ_NM; ++m) {
             double v = acc[m];
-            v += dbl_dpp<0x111>(v);
-            v += dbl_dpp<0x112>(v);
-            v += dbl_dpp<0x114>(v);
-            v += dbl_dpp<0x118>(v);
-            v += dbl_dpp_rows<0x142, 0xa>(v);
-            v += dbl_dpp_rows<0x143, 0xc>(v);
+            dpp_row_sums(v);
+            v += dbl_dpp<0x142, 0xa>(v);
+            v += dbl_dpp<0x143, 0xc>(v);
             acc[m] = v;
         }
         if (lane == 63) {
@@ -796,7 +781,10 @@ __device__ __forceinline__ void gq_cg_body(const GqNodes* __restrict__ nd, doubl
     // block sums of (a, b), the same in every lane
     auto reduce2 = [&](double a, double b, int slot, double* ra, double* rb) {
         // the two wave sums side by side (two independent DPP chains), totals in lane 63:
-        // row_shr tree, then row_bcast 15 / 31 -- (R3 + R2) + (R1 + R0)
+        // row_shr tree, then row_bcast 15 / 31 -- (R3 + R2) + (R1 + R0).  The tree is
+        // dpp_row_sums' (foto_reduce.h), written out for the pair: through a two-value form of
+        // that function the pair's last adds land in other VGPRs, and the interleaved A/B
+        // (profiles/reduce_refactor_ab.txt) did not keep every repetition inside the old code's spread
         a += dbl_dpp<0x111>(a);
         b += dbl_dpp<0x111>(b);
         a += dbl_dpp<0x112>(a);
@@ -805,10 +793,10 @@ __device__ __forceinline__ void gq_cg_body(const GqNodes* __restrict__ nd, doubl
         b += dbl_dpp<0x114>(b);
         a += dbl_dpp<0x118>(a);
         b += dbl_dpp<0x118>(b);
-        a += dbl_dpp_rows<0x142, 0xa>(a);
-        b += dbl_dpp_rows<0x142, 0xa>(b);
-        a += dbl_dpp_rows<0x143, 0xc>(a);
-        b += dbl_dpp_rows<0x143, 0xc>(b);
+        a += dbl_dpp<0x142, 0xa>(a);
+        b += dbl_dpp<0x142, 0xa>(b);
+        a += dbl_dpp<0x143, 0xc>(a);
+        b += dbl_dpp<0x143, 0xc>(b);
         if (lane == 63) red[slot][wv] = dbl2{a, b};
         __syncthreads();
         dbl2 t = red[slot][0];

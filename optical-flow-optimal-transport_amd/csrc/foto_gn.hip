@@ -12,6 +12,7 @@
 #include <chrono>
 
 #include "foto_internal.h"
+#include "foto_reduce.h"
 
 #include <algorithm>
 #include <atomic>
@@ -24,67 +25,6 @@
 #include <vector>
 
 namespace foto {
-
-// reductions shared with foto_kernels.hip (re-declared here: header-only templates)
-__device__ __forceinline__ double gn_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-template <int K>
-__device__ __forceinline__ void gn_block_sum(double (&v)[K], double* sh) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        v[k] = gn_wave_sum(v[k]);
-        if (lane == 0) sh[k * (NT / 64) + w] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            double s = sh[k * (NT / 64)];
-#pragma unroll
-            for (int j = 1; j < NT / 64; ++j) s += sh[k * (NT / 64) + j];
-            v[k] = s;
-        }
-    }
-}
-
-template <int K>
-__device__ bool gn_reduce_last(double (&v)[K], RedBuf rb, double (&tot)[K]) {
-    __shared__ double sh[K * (NT / 64)];
-    __shared__ int is_last;
-    gn_block_sum<K>(v, sh);
-    const int nb = gridDim.x;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            __hip_atomic_store(&rb.partials[(int64_t)k * nb + blockIdx.x], v[k], __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned t = __hip_atomic_fetch_add(rb.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = (t == (unsigned)(nb - 1));
-    }
-    __syncthreads();
-    if (!is_last) return false;
-    double acc[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = 0.0;
-    for (int i = threadIdx.x; i < nb; i += NT) {
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            acc[k] += __hip_atomic_load(&rb.partials[(int64_t)k * nb + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    gn_block_sum<K>(acc, sh);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) tot[k] = acc[k];
-        __hip_atomic_store(rb.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return true;
-}
 
 // PCG kernels run a grid-stride loop over pixels on at most two blocks per CU: each block
 // adds one agent-scope ticket per launch, and 1200 tickets on one address (one block per
@@ -290,7 +230,7 @@ __global__ __launch_bounds__(NT) void k_gn_pcg_init(int w, int h, const double* 
         rz += ru * zu + rv * zv + rm * zm;
     }
     double v[2] = {rr, rz}, tot[2];
-    if (gn_reduce_last<2>(v, rb, tot) && threadIdx.x == 0) { gath[0] = tot[0]; gath[1] = tot[1]; }
+    if (grid_reduce_last<2>(v, rb, tot) && threadIdx.x == 0) { gath[0] = tot[0]; gath[1] = tot[1]; }
 }
 
 hipError_t launch_gn_pcg_init(int w, int h, const double* fx, const double* fy, const double* f2, double alpha,
@@ -333,7 +273,7 @@ __global__ __launch_bounds__(NT) void k_gn_pcg_dir(int w, int h, int k_arg, cons
         pq += pu * qu + pvv * qv + pm * qm;
     }
     double v[1] = {pq}, tot[1];
-    if (gn_reduce_last<1>(v, rb, tot) && threadIdx.x == 0) {
+    if (grid_reduce_last<1>(v, rb, tot) && threadIdx.x == 0) {
         S->rho = rz;
         if (k == 0) { S->bb = rr; S->atol = atol; }
         gath_pq[0] = tot[0];
@@ -381,7 +321,7 @@ __global__ __launch_bounds__(NT) void k_gn_pcg_upd(int w, int h, int k, const do
         rz += rn[0] * zu + rn[1] * zv + rn[2] * zm;
     }
     double v[2] = {rr, rz}, tot[2];
-    if (gn_reduce_last<2>(v, rb, tot) && threadIdx.x == 0) {
+    if (grid_reduce_last<2>(v, rb, tot) && threadIdx.x == 0) {
         gath_rz[0] = tot[0];
         gath_rz[1] = tot[1];
     }
@@ -529,7 +469,7 @@ __device__ __forceinline__ void mg_sum_partials(const double* const (&src)[K], i
     for (int k = 0; k < K; ++k) {
         double v = 0.0;
         for (int i = threadIdx.x; i < nb; i += NT) v += src[k][i];
-        v = gn_wave_sum(v);
+        v = wave_sum(v);
         if (lane == 0) sh[k][wv] = v;
     }
     __syncthreads();
@@ -545,7 +485,7 @@ __device__ __forceinline__ void mg_sum_partials(const double* const (&src)[K], i
 // this block's partial of v -> dst[block] (fixed order)
 __device__ __forceinline__ void mg_block_partial(double v, double* dst) {
     __shared__ double sh[NT / 64];
-    v = gn_wave_sum(v);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1198,7 +1138,7 @@ __global__ __launch_bounds__(1024) void k_mg_coarse(MGLev L, const CGScal* S, co
         rz += f0[q] * xs[cur][i] + f1[q] * xs[cur][n + i] + f2v[q] * xs[cur][2 * n + i];
     }
     if constexpr (RZ) {
-        rz = gn_wave_sum(rz);
+        rz = wave_sum(rz);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = rz;
         __syncthreads();
         if (threadIdx.x == 0) {

@@ -14,79 +14,13 @@
 //              along t with the t-neighbours in registers; p.Ap block partials.
 //   k_cg_upd : x += alpha p, r -= alpha A p (A p recomputed from p: cheaper than storing
 //              and re-reading q), r.r partials.
-// Both finish with a last-block reduction (write-through partials + agent-scope ticket,
-// MI355X_MICROARCH.md "Valid forms" row 1): no extra launch per dot product.
+// Both finish with a last-block reduction (grid_reduce_last, foto_reduce.h: write-through
+// partials + agent-scope ticket): no extra launch per dot product.
 #include "foto_devutil.h"
 #include "foto_internal.h"
+#include "foto_reduce.h"
 
 namespace foto {
-
-// ============================================================================ reductions
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// Fixed-tree block sum of K values; result valid in thread 0.  `sh` holds K*NT/64 doubles.
-template <int K, int NTH = NT>
-__device__ __forceinline__ void block_sum(double (&v)[K], double* sh) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        v[k] = wave_sum(v[k]);
-        if (lane == 0) sh[k * (NTH / 64) + w] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            double s = sh[k * (NTH / 64)];
-#pragma unroll
-            for (int j = 1; j < NTH / 64; ++j) s += sh[k * (NTH / 64) + j];
-            v[k] = s;
-        }
-    }
-}
-
-// Every block contributes v[K]; the block whose ticket add comes last sums all block
-// partials in block order (deterministic) and returns true with the totals in thread 0.
-// Hand-off: partials stored sc1 (write-through) + vmcnt(0) before an agent-scope ticket
-// add; the last block reads them with sc1 loads after its add returned and a barrier.
-template <int K, int NTH = NT>
-__device__ bool grid_reduce_last(double (&v)[K], RedBuf rb, double (&tot)[K]) {
-    __shared__ double sh[K * (NTH / 64)];
-    __shared__ int is_last;
-    block_sum<K, NTH>(v, sh);
-    const int nb = gridDim.x;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            __hip_atomic_store(&rb.partials[(int64_t)k * nb + blockIdx.x], v[k], __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned t = __hip_atomic_fetch_add(rb.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = (t == (unsigned)(nb - 1));
-    }
-    __syncthreads();
-    if (!is_last) return false;
-    double acc[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = 0.0;
-    for (int i = threadIdx.x; i < nb; i += NTH) {
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            acc[k] += __hip_atomic_load(&rb.partials[(int64_t)k * nb + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    block_sum<K, NTH>(acc, sh);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) tot[k] = acc[k];
-        __hip_atomic_store(rb.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return true;
-}
 
 // ============================================================================ stencils
 
@@ -571,11 +505,8 @@ __global__ __launch_bounds__(NT) void k_report(Geo g, ReportIn in, double* __res
     double* const pp = part + (int64_t)t * K * pieces;
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int k = 0; k < K; ++k)
-            __hip_atomic_store(&pp[(int64_t)k * pieces + piece], v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned tk = __hip_atomic_fetch_add(&ticket[t], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = (tk == (unsigned)(pieces - 1));
+        for (int k = 0; k < K; ++k) partial_store(&pp[(int64_t)k * pieces + piece], v[k]);
+        is_last = ticket_take_last(&ticket[t], pieces);
     }
     __syncthreads();
     if (!is_last) return;
@@ -584,14 +515,13 @@ __global__ __launch_bounds__(NT) void k_report(Geo g, ReportIn in, double* __res
     for (int k = 0; k < K; ++k) acc[k] = 0.0;
     for (int p = threadIdx.x; p < pieces; p += NT) {
 #pragma unroll
-        for (int k = 0; k < K; ++k)
-            acc[k] += __hip_atomic_load(&pp[(int64_t)k * pieces + p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int k = 0; k < K; ++k) acc[k] += partial_load(&pp[(int64_t)k * pieces + p]);
     }
     block_sum<K>(acc, sh);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < K; ++k) out[(int64_t)t * K + k] = acc[k];
-        __hip_atomic_store(&ticket[t], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ticket_reset(&ticket[t]);
     }
 }
 

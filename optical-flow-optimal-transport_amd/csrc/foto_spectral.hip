@@ -23,207 +23,10 @@
 
 #include "foto_dct.h"
 #include "foto_devutil.h"
+#include "foto_reduce.h"
 #include "foto_spectral.h"
 
 namespace foto {
-
-// ============================================================================ reductions (local copies)
-
-__device__ __forceinline__ double sp_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-template <int K>
-__device__ __forceinline__ void sp_block_sum(double (&v)[K], double* sh) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        v[k] = sp_wave_sum(v[k]);
-        if (lane == 0) sh[k * (NT / 64) + w] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            double s = sh[k * (NT / 64)];
-#pragma unroll
-            for (int j = 1; j < NT / 64; ++j) s += sh[k * (NT / 64) + j];
-            v[k] = s;
-        }
-    }
-}
-
-template <int K>
-__device__ bool sp_reduce_last(double (&v)[K], RedBuf rb, double (&tot)[K]) {
-    __shared__ double sh[K * (NT / 64)];
-    __shared__ int is_last;
-    sp_block_sum<K>(v, sh);
-    const int nb = gridDim.x;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            __hip_atomic_store(&rb.partials[(int64_t)k * nb + blockIdx.x], v[k], __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned t = __hip_atomic_fetch_add(rb.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = (t == (unsigned)(nb - 1));
-    }
-    __syncthreads();
-    if (!is_last) return false;
-    double acc[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = 0.0;
-    for (int i = threadIdx.x; i < nb; i += NT) {
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            acc[k] += __hip_atomic_load(&rb.partials[(int64_t)k * nb + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    sp_block_sum<K>(acc, sh);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) tot[k] = acc[k];
-        __hip_atomic_store(rb.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return true;
-}
-
-// ---------------------------------------------------------------------------- reduce-scatter
-// Wave-level sum of K per-lane values without LDS: at each xor level a lane keeps one half
-// of its remaining values and adds the partner's copy of that half (the partner sends it),
-// so the K values halve per level (48 -> 24 -> 12 -> 6 -> 3 over xor 32, 16, 8, 4) and the
-// last levels butterfly the remainder.  Lane l ends with the wave totals of quantities
-// rs_base(l) + j, j < rs_count<K>(); lanes differing only in the butterflied low bits hold
-// identical values.  Every total is a pairwise tree over the 64 lanes: deterministic, and
-// (measured in the s-step prototype) as accurate as compensated summation for the moments.
-template <int K>
-constexpr int rs_levels() {   // halving levels
-    int c = K, l = 0;
-    while (c % 2 == 0 && l < 6) { c /= 2; ++l; }
-    return l;
-}
-template <int K>
-constexpr int rs_count() { return K >> rs_levels<K>(); }
-
-template <int C, int MASK>
-__device__ __forceinline__ void rs_halve(double* v, int lane) {
-    if constexpr (C % 2 == 0 && MASK >= 1) {
-        const bool hi = (lane & MASK) != 0;
-#pragma unroll
-        for (int j = 0; j < C / 2; ++j) {
-            if (j % 8 == 0) asm volatile("" ::: "memory");   // bound batched shuffles (registers)
-            const double send = hi ? v[j] : v[C / 2 + j];
-            const double keep = hi ? v[C / 2 + j] : v[j];
-            v[j] = keep + __shfl_xor(send, MASK, 64);
-        }
-        rs_halve<C / 2, MASK / 2>(v, lane);
-    } else if constexpr (MASK >= 1) {
-#pragma unroll
-        for (int j = 0; j < C; ++j) v[j] += __shfl_xor(v[j], MASK, 64);
-        rs_halve<C, MASK / 2>(v, lane);
-    }
-}
-
-template <int K>
-__device__ __forceinline__ int rs_base(int lane) {
-    int base = 0, c = K;
-#pragma unroll
-    for (int l = 0, mask = 32; l < rs_levels<K>(); ++l, mask >>= 1) {
-        c /= 2;
-        if (lane & mask) base += c;
-    }
-    return base;
-}
-
-// Block (NTH threads) sum of K values per thread into red[k] (shared, K): reduce-scatter per
-// wave, then the waves' partials are added pairwise by K threads.  wred: shared, (NTH/64) * K.
-template <int K, int NTH>
-__device__ __forceinline__ void blk_sum_rs(double (&v)[K], double* wred, double* out /* shared K */) {
-    constexpr int NW = NTH / 64, LEV = rs_levels<K>(), CNT = rs_count<K>();
-    constexpr int LOWMASK = (LEV >= 6) ? 0 : ((32 >> (LEV > 0 ? LEV - 1 : 0)) - 1) & (LEV > 0 ? 63 : 63);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    rs_halve<K, 32>(v, lane);
-    const int base = rs_base<K>(lane);
-    const int low = (LEV == 0) ? 63 : ((32 >> (LEV - 1)) - 1);
-    (void)LOWMASK;
-    if ((lane & low) == 0) {
-#pragma unroll
-        for (int j = 0; j < CNT; ++j) wred[w * K + base + j] = v[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double a[NW];
-#pragma unroll
-        for (int i = 0; i < NW; ++i) a[i] = wred[i * K + threadIdx.x];
-#pragma unroll
-        for (int st = 1; st < NW; st *= 2)
-#pragma unroll
-            for (int i = 0; i + st < NW; i += 2 * st) a[i] += a[i + st];
-        out[threadIdx.x] = a[0];
-    }
-    __syncthreads();
-}
-
-// Cross-block sum of K values per thread: block sums by reduce-scatter, k-major partials,
-// agent-scope ticket; the last block gathers the partials with 16 threads per quantity
-// (16 loads in flight each: one round trip for up to 256 blocks), pairwise throughout.
-// With 256-thread blocks and 1024 blocks the gather was 14 us of each pass; with 1024-thread
-// blocks (one per CU) and this layout of the loads it is ~3 us.
-template <int K, int NTH>
-__device__ bool sp_reduce_last_rs(double (&v)[K], RedBuf rb, double* tot /* shared, K */) {
-    constexpr int NW = NTH / 64;
-    __shared__ double wred[NW * K];
-    __shared__ double bsum[K];
-    __shared__ int is_last;
-    const int tid = threadIdx.x, nb = gridDim.x;
-    blk_sum_rs<K, NTH>(v, wred, bsum);
-    if (tid < K)
-        __hip_atomic_store(&rb.partials[(int64_t)tid * nb + blockIdx.x], bsum[tid], __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    if (tid < 64) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // wave 0's stores drained before its ticket add
-        if (tid == 0) {
-            const unsigned t = __hip_atomic_fetch_add(rb.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            is_last = (t == (unsigned)(nb - 1));
-        }
-    }
-    __syncthreads();
-    if (!is_last) return false;
-    // Gather: thread t sums quantity t / 16 over the blocks b = t % 16 + 16 j (16 loads in
-    // flight per round, pairwise), then the 16 lanes of a quantity combine by xor butterfly.
-    // K * 16 threads per round of quantities (all 48 at once with 1024-thread blocks).
-    constexpr int QPR = NTH / 16;   // quantities per round
-#pragma unroll
-    for (int c = 0; c < K; c += QPR) {
-        const int k = c + (tid >> 4), sub = tid & 15;
-        double x = 0.0;
-        if (k < K) {
-            for (int base = 0; base < nb; base += 256) {
-                double y[16];
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const int b = min(base + sub + 16 * j, nb - 1);
-                    y[j] = __hip_atomic_load(&rb.partials[(int64_t)k * nb + b], __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-                }
-#pragma unroll
-                for (int j = 0; j < 16; ++j) y[j] = (base + sub + 16 * j < nb) ? y[j] : 0.0;
-#pragma unroll
-                for (int st = 1; st < 16; st *= 2)
-#pragma unroll
-                    for (int j = 0; j + st < 16; j += 2 * st) y[j] += y[j + st];
-                x += y[0];
-            }
-        }
-#pragma unroll
-        for (int m = 8; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-        if (k < K && sub == 0) tot[k] = x;
-    }
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(rb.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
-}
 
 // ============================================================================ CG in the eigenbasis
 
@@ -302,7 +105,7 @@ __global__ __launch_bounds__(NT) void k_spec_init(SpecTab T, const double* __res
         }
     });
     double v[2] = {a0, a1}, tot[2];
-    if (sp_reduce_last<2>(v, rb, tot) && threadIdx.x == 0) { gath[0] = tot[0]; gath[1] = tot[1]; }
+    if (grid_reduce_last<2>(v, rb, tot) && threadIdx.x == 0) { gath[0] = tot[0]; gath[1] = tot[1]; }
 }
 
 // One CG iteration k (Chronopoulos-Gear): given rho_k = r.r and m_k = r.lam.r (gathered),
@@ -351,7 +154,7 @@ __global__ __launch_bounds__(NT) void k_spec_cg(SpecTab T, int k, double* __rest
         }
     });
     double v[2] = {a0, a1}, tot[2];
-    if (sp_reduce_last<2>(v, rb, tot) && threadIdx.x == 0) {
+    if (grid_reduce_last<2>(v, rb, tot) && threadIdx.x == 0) {
         S->rho = rho;
         S->pap = alpha;
         if (k == 0) { S->atol = atol; S->bb = rho; }
@@ -437,27 +240,9 @@ constexpr int S_PROJ = (NMOM - 3) / 2;   // projected interval after n <= S_PROJ
 // |terms| sums by FMA with |.| operand modifiers, lane sums by a DPP row_shr tree (lanes 15 and
 // 31 hold the row totals), neighbours for lam U by DPP wave shifts -- no LDS round trip.
 
-__device__ __forceinline__ double dbl_readlane(double v, int lane) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), lane);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dbl_dpp(double v) {   // lanes without a source read 0
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffLL), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, true);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
-// sum over lanes 0 .. 31 (lanes >= NG hold 0), uniform result: row_shr 1, 2, 4, 8 tree
+// sum over lanes 0 .. 31 (lanes >= NG hold 0), uniform result: the row tree, then rows 0 and 1
 __device__ __forceinline__ double dpp_sum32(double v) {
-    v += dbl_dpp<0x111>(v);
-    v += dbl_dpp<0x112>(v);
-    v += dbl_dpp<0x114>(v);
-    v += dbl_dpp<0x118>(v);
+    dpp_row_sums(v);
     return dbl_readlane(v, 15) + dbl_readlane(v, 31);
 }
 
@@ -632,6 +417,26 @@ __device__ void sstep_plan_wave(SStep* Sg, SStep S, const double* tot, int init,
     }
 }
 
+// What the last block does with the summed moments tot[NACC] (shared).  Without PLAN they go to
+// this rank's slot of gath (k_spec_s2_plan plans after the all-gather) and every thread is done:
+// true.  With PLAN, false in wave 0 alone, which goes on to plan the next pass (sstep_plan_wave).
+template <bool PLAN, int NTH>
+__device__ __forceinline__ bool moments_handed_over(const double* tot, double* gath, int rank) {
+    if (!PLAN) {
+        rank_slot_store<NACC, NTH>(gath, rank, tot);
+        return true;
+    }
+    return threadIdx.x >= 64;
+}
+
+// ... after an INIT sweep that took the rr moments alone (q = 0: rq, qq vanish)
+template <bool PLAN, int NTH>
+__device__ __forceinline__ bool init_moments_handed_over(double* tot, double* gath, int rank) {
+    for (int m = NMOM + threadIdx.x; m < NACC; m += NTH) tot[m] = 0.0;
+    __syncthreads();
+    return moments_handed_over<PLAN, NTH>(tot, gath, rank);
+}
+
 // element pair of tile t owned by this thread (see spec_for_each); n2 = 0: none
 struct SpElem {
     int64_t i;
@@ -687,26 +492,9 @@ __global__ __launch_bounds__(S2_NTH) __attribute__((amdgpu_waves_per_eu(S2_WPE))
     double acc[NACC];
 #pragma unroll
     for (int m = 0; m < NACC; ++m) acc[m] = 0.0;
-    auto moments = [&](double lam, double r, double q) {
-        const double x = (lam - c0) * ic1, x2 = x + x;
-        const double rr = r * r, rq = r * q, qq = q * q;
-        acc[0] += rr;
-        acc[NMOM] += rq;
-        acc[2 * NMOM] += qq;
-        acc[1] = fma(x, rr, acc[1]);
-        acc[NMOM + 1] = fma(x, rq, acc[NMOM + 1]);
-        acc[2 * NMOM + 1] = fma(x, qq, acc[2 * NMOM + 1]);
-        double tm2 = 1.0, tm1 = x;
-#pragma unroll
-        for (int m = 2; m < NMOM; ++m) {
-            const double t = fma(x2, tm1, -tm2);
-            acc[m] = fma(t, rr, acc[m]);
-            acc[NMOM + m] = fma(t, rq, acc[NMOM + m]);
-            acc[2 * NMOM + m] = fma(t, qq, acc[2 * NMOM + m]);
-            tm2 = tm1;
-            tm1 = t;
-        }
-    };
+    // (a lambda around the shared function, here and in ring_pass_t: the two calls per tile are
+    // inlined where the written-out formula was, and the tile loop keeps its instructions)
+    auto moments = [&](double lam, double r, double q) { cheb_moments_acc<3, NMOM>(acc, (lam - c0) * ic1, r, q); };
     const int rows = T.Nt * T.nyl;
     const int ntx = (T.Nx + 127) / 128;
     const int ntiles = ntx * ((rows + TR - 1) / TR);
@@ -742,12 +530,8 @@ __global__ __launch_bounds__(S2_NTH) __attribute__((amdgpu_waves_per_eu(S2_WPE))
         if (e.n2 == 2) moments(e.l1, r1, q1);
     }
     __shared__ double tot[NACC];
-    if (!sp_reduce_last_rs<NACC, S2_NTH>(acc, rb, tot)) return;
-    if (!FUSE) {
-        for (int m = threadIdx.x; m < NACC; m += S2_NTH) gath[rank * NACC + m] = tot[m];
-        return;
-    }
-    if (threadIdx.x >= 64) return;
+    if (!grid_reduce_last_rs<NACC, S2_NTH>(acc, rb, tot)) return;
+    if (moments_handed_over<FUSE, S2_NTH>(tot, gath, rank)) return;
     sstep_plan_wave(Sg, S0, tot, INIT ? 1 : 0, rtol, maxiter);
 }
 
@@ -948,26 +732,7 @@ __device__ __forceinline__ void ring_pass_t(const SpecTab& T, const RingWave& w,
     const bool loadq = __builtin_amdgcn_readfirstlane((!INIT && k > 0) ? 1 : 0) != 0;
     const bool momu = __builtin_amdgcn_readfirstlane(mom ? 1 : 0) != 0;
     const double* src = (INIT || k == 0) ? bh : rh;   // r_0 = b^ (the INIT pass leaves it there)
-    auto moments = [&](double lam, double r, double q) {
-        const double x = (lam - c0) * ic1, x2 = x + x;
-        const double rr = r * r, rq = r * q, qq = q * q;
-        acc[0] += rr;
-        acc[NMOM] += rq;
-        acc[2 * NMOM] += qq;
-        acc[1] = fma(x, rr, acc[1]);
-        acc[NMOM + 1] = fma(x, rq, acc[NMOM + 1]);
-        acc[2 * NMOM + 1] = fma(x, qq, acc[2 * NMOM + 1]);
-        double tm2 = 1.0, tm1 = x;
-#pragma unroll
-        for (int m = 2; m < NMOM; ++m) {
-            const double t = fma(x2, tm1, -tm2);
-            acc[m] = fma(t, rr, acc[m]);
-            acc[NMOM + m] = fma(t, rq, acc[NMOM + m]);
-            acc[2 * NMOM + m] = fma(t, qq, acc[2 * NMOM + m]);
-            tm2 = tm1;
-            tm1 = t;
-        }
-    };
+    auto moments = [&](double lam, double r, double q) { cheb_moments_acc<3, NMOM>(acc, (lam - c0) * ic1, r, q); };
     const int nj = w.nj;
     const float invx = 1.0f / (float)T.Nx, invy = 1.0f / (float)T.nyl;
     const int g = loadq ? 2 : 1;               // DMA instructions per tile
@@ -1163,9 +928,12 @@ __global__ __launch_bounds__(S2_NTH) __attribute__((amdgpu_waves_per_eu(S2_WPE))
     const bool final_pass = LATE && S0.fin && !S0.done;
     if (!LATE || !S0.done) ring_pass<D, INIT>(T, w, lds_u32(tab), S0, rh, ph, bh, acc, issued, !final_pass);
     else if (issued) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the prefetch
-    if (!sp_reduce_last_rs<NACC, S2_NTH>(acc, rb, tot)) return;
+    if (!grid_reduce_last_rs<NACC, S2_NTH>(acc, rb, tot)) return;
     if constexpr (LATE) {
-        if (!S0.done && !final_pass)   // this rank's slot (the all-gather between passes fills the others)
+        // this rank's slot (the all-gather between passes fills the others).  rank_slot_store's loop
+        // written out: inlined from there, its bound test merges with the entry's threadIdx.x < NACC,
+        // which then stays live across the tile loop and moves this kernel's SGPR spills
+        if (!S0.done && !final_pass)
             for (int m = threadIdx.x; m < NACC; m += S2_NTH) gath[rank * NACC + m] = tot[m];
         if (threadIdx.x == 0) {
             SStep So = Sl;   // == S0 (thread 0 wrote it before the barrier)
@@ -1181,33 +949,21 @@ __global__ __launch_bounds__(S2_NTH) __attribute__((amdgpu_waves_per_eu(S2_WPE))
         }
         return;
     }
-    if (!FUSE) {
-        for (int m = threadIdx.x; m < NACC; m += S2_NTH) gath[rank * NACC + m] = tot[m];
-        return;
-    }
-    if (threadIdx.x >= 64) return;
+    if (moments_handed_over<FUSE, S2_NTH>(tot, gath, rank)) return;
     sstep_plan_wave(Sg, S0, tot, INIT ? 1 : 0, rtol, maxiter);
 }
 
 constexpr bool ring_fits(int D) { return (RING_NW * D * RING_SLOT + RING_TAB) * 8 <= 150 * 1024; }
 static_assert(ring_fits(RING_D), "ring + tables exceed the LDS");
 
-// host launcher (D = 0: RING_D)
+// host launcher
 static hipError_t launch_s2_ring(const SpecTab& T, double* rh, double* ph, const double* bh, SStep* Sg, RedBuf rb,
-                                 double rtol, int maxiter, double* gath, int rank, bool init, bool fuse, int D,
+                                 double rtol, int maxiter, double* gath, int rank, bool init, bool fuse,
                                  int nb = 256, hipStream_t s = 0, int world = 1) {
-    if (D == 0) D = RING_D;
-#define FOTO_RL(DD, I, F) \
-    k_spec_s2r<DD, I, F><<<nb, S2_NTH, 0, s>>>(T, rh, ph, bh, Sg, rb, rtol, maxiter, gath, rank, world)
-#define FOTO_RL_D(DD)                                                                        \
-    if (D == DD) {                                                                           \
-        if constexpr (ring_fits(DD)) {                                                       \
-            if (init) { if (fuse) FOTO_RL(DD, true, true); else FOTO_RL(DD, true, false); } \
-            else { if (fuse) FOTO_RL(DD, false, true); else FOTO_RL(DD, false, false); }    \
-        } else return hipErrorInvalidValue;                                                  \
-    }
-    FOTO_RL_D(2) else FOTO_RL_D(3) else FOTO_RL_D(4) else FOTO_RL_D(5) else FOTO_RL_D(8) else return hipErrorInvalidValue;
-#undef FOTO_RL_D
+#define FOTO_RL(I, F) \
+    k_spec_s2r<RING_D, I, F><<<nb, S2_NTH, 0, s>>>(T, rh, ph, bh, Sg, rb, rtol, maxiter, gath, rank, world)
+    if (init) { if (fuse) FOTO_RL(true, true); else FOTO_RL(true, false); }
+    else { if (fuse) FOTO_RL(false, true); else FOTO_RL(false, false); }
 #undef FOTO_RL
     return hipGetLastError();
 }
@@ -1305,19 +1061,8 @@ __global__ __launch_bounds__(TC_NTH) __attribute__((amdgpu_waves_per_eu(TC_WPE))
         }
         auto emit = [&](int k, double X) {
             bh[k * ncols + c] = X;
-            if constexpr (MODE == TC_PLAIN) return;
             const double lam = T.reps + T.r * ((mts[k] + myv) + mxv);   // spec_lam's order
-            const double x = (lam - c0) * ic1, x2 = x + x, rr = X * X;
-            acc[0] += rr;
-            acc[1] = fma(x, rr, acc[1]);
-            double tm2 = 1.0, tm1 = x;
-#pragma unroll
-            for (int m = 2; m < NMOM; ++m) {
-                const double t = fma(x2, tm1, -tm2);
-                acc[m] = fma(t, rr, acc[m]);
-                tm2 = tm1;
-                tm1 = t;
-            }
+            cheb_moments_acc<1, NMOM>(acc, (lam - c0) * ic1, X);
         };
 #pragma unroll
         for (int m = 0; m < H; ++m) {
@@ -1331,16 +1076,9 @@ __global__ __launch_bounds__(TC_NTH) __attribute__((amdgpu_waves_per_eu(TC_WPE))
             emit(2 * m + 1, o);
         }
     }
-    if constexpr (MODE == TC_PLAIN) return;
     __shared__ double tot[NACC];
-    if (!sp_reduce_last_rs<NMOM, TC_NTH>(acc, rb, tot)) return;
-    for (int m = NMOM + threadIdx.x; m < NACC; m += TC_NTH) tot[m] = 0.0;   // q = 0: rq, qq vanish
-    __syncthreads();
-    if (MODE == TC_GATH) {
-        for (int m = threadIdx.x; m < NACC; m += TC_NTH) gath[rank * NACC + m] = tot[m];
-        return;
-    }
-    if (threadIdx.x >= 64) return;
+    if (!grid_reduce_last_rs<NMOM, TC_NTH>(acc, rb, tot)) return;
+    if (init_moments_handed_over<MODE == TC_PLAN, TC_NTH>(tot, gath, rank)) return;
     sstep_plan_wave(Sg, S0, tot, 1, rtol, maxiter);
 }
 
@@ -1437,29 +1175,13 @@ __global__ __launch_bounds__(TC_NTH) __attribute__((amdgpu_waves_per_eu(NTT > 48
             bh[k * ncols + c] = X;
             if constexpr (MODE == TC_PLAIN) continue;
             const double lam = T.reps + T.r * ((mts[k] + myv) + mxv);   // spec_lam's order
-            const double x = (lam - c0) * ic1, x2 = x + x, rr = X * X;
-            acc[0] += rr;
-            acc[1] = fma(x, rr, acc[1]);
-            double tm2 = 1.0, tm1 = x;
-#pragma unroll
-            for (int mm = 2; mm < NMOM; ++mm) {
-                const double t = fma(x2, tm1, -tm2);
-                acc[mm] = fma(t, rr, acc[mm]);
-                tm2 = tm1;
-                tm1 = t;
-            }
+            cheb_moments_acc<1, NMOM>(acc, (lam - c0) * ic1, X);
         }
     }
     if constexpr (MODE == TC_PLAIN) return;
     __shared__ double tot[NACC];
-    if (!sp_reduce_last_rs<NMOM, TC_NTH>(acc, rb, tot)) return;
-    for (int m = NMOM + threadIdx.x; m < NACC; m += TC_NTH) tot[m] = 0.0;   // q = 0: rq, qq vanish
-    __syncthreads();
-    if (MODE == TC_GATH) {
-        for (int m = threadIdx.x; m < NACC; m += TC_NTH) gath[rank * NACC + m] = tot[m];
-        return;
-    }
-    if (threadIdx.x >= 64) return;
+    if (!grid_reduce_last_rs<NMOM, TC_NTH>(acc, rb, tot)) return;
+    if (init_moments_handed_over<MODE == TC_PLAN, TC_NTH>(tot, gath, rank)) return;
     sstep_plan_wave(Sg, S0, tot, 1, rtol, maxiter);
 }
 
@@ -2008,7 +1730,7 @@ static hipError_t launch_s2(SpecImpl* P, bool init, double rtol, int maxiter, do
     const bool fuse = (gath == nullptr);
     double* gw = gath ? gath : P->gath;
     if (P->ring)
-        return launch_s2_ring(T, P->rh, P->ph, P->bh, P->S2, P->rb, rtol, maxiter, gw, P->rank, init, fuse, RING_D,
+        return launch_s2_ring(T, P->rh, P->ph, P->bh, P->S2, P->rb, rtol, maxiter, gw, P->rank, init, fuse,
                               P->nb_ring, s);
 #define FOTO_S2_LAUNCH(V, I, F) \
     k_spec_s2<V, I, F><<<nb, S2_NTH, 0, s>>>(T, P->rh, P->ph, P->bh, P->S2, P->rb, rtol, maxiter, gw, P->rank)
@@ -2507,7 +2229,7 @@ int SpectralPlan::cg_pass(double rtol, int maxiter, KTimer* kt, hipStream_t s) {
     hipEvent_t e = kt ? kt->start(s) : nullptr;
     if (P->late_plan())   // plans at its start from the all-gathered moments (no cg_plan after it)
         FOTO_HIP_CHECK(launch_s2_ring(P->tab(), P->rh, P->ph, P->bh, P->S2, P->rb, rtol, maxiter, P->gath, P->rank,
-                                      false, true, RING_D, P->nb_ring, s, P->world));
+                                      false, true, P->nb_ring, s, P->world));
     else
         FOTO_HIP_CHECK(launch_s2(P, false, rtol, maxiter, P->gath, s));
     if (kt) kt->stop(e, s, FOTO_K_SPEC, 32.0 * P->nbox());
