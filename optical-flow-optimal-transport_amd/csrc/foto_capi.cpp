@@ -349,7 +349,6 @@ int foto_gn_rhs(const double* f1, const double* f2, int w, int h, double* b3) {
 }
 
 // classical.GLLOpticalFlow.process: PCG to rtol on the assembled-equivalent operator.
-// Device-resident loop; the host polls the done flag between chunks of iterations.
 static int gn_solve_impl(const double* f1, const double* f2, int w, int h, double alpha, double lam, double rtol,
                          int maxiter, double* u, double* v, double* m, int* iterations, foto_gn_stats* st);
 
@@ -438,63 +437,12 @@ static int gn_solve_impl(const double* f1, const double* f2, int w, int h, doubl
         return rc;
     }
     // 3x3 block-Jacobi PCG (the first GPU version; kept for A/B runs)
-    Scope S;
-    FOTO_TRY(S.init());
-    const size_t n = (size_t)w * h;
-    double *d1, *d2, *fx, *fy, *ft, *b, *x, *r, *z, *p0, *p1, *part, *gath, *scal;
-    const int nb = flat_blocks((int64_t)n);
-    {   // one allocation (a solve is ~15 ms; per-buffer hipMalloc/hipFree added up to ~1 ms)
-        const size_t nscal = sizeof(CGScal) / sizeof(double) + 1;
-        double* base;
-        FOTO_TRY(S.dev(23 * n + 2 * (size_t)nb + 8 + 8 + nscal, &base));
-        d1 = base; fx = base + 2 * n; fy = fx + n; ft = fy + n;
-        d2 = base + n;
-        b = ft + n; x = b + 3 * n; r = x + 3 * n; z = r + 3 * n; p0 = z + 3 * n; p1 = p0 + 3 * n;
-        part = p1 + 3 * n; gath = part + 2 * (size_t)nb + 8; scal = gath + 8;
-        FOTO_HIP_CHECK(hipMemcpyAsync(d1, f1, n * sizeof(double), hipMemcpyHostToDevice, S.s));
-        FOTO_HIP_CHECK(hipMemcpyAsync(d2, f2, n * sizeof(double), hipMemcpyHostToDevice, S.s));
-    }
-    CGScal* dS = (CGScal*)scal;
-    FOTO_HIP_CHECK(hipMemsetAsync(part + 2 * nb, 0, 8 * sizeof(double), S.s));
-    FOTO_HIP_CHECK(hipMemsetAsync(dS, 0, sizeof(CGScal), S.s));
-    FOTO_HIP_CHECK(hipMemsetAsync(x, 0, 3 * n * sizeof(double), S.s));
-    RedBuf rb{part, (unsigned*)(part + 2 * nb), 2 * nb};
-    double* g_rz = gath;       // {r.r, r.z}
-    double* g_pq = gath + 2;   // {p.q}
-    FOTO_HIP_CHECK(launch_gn_coeffs(w, h, d1, d2, fx, fy, ft, S.s));
-    FOTO_HIP_CHECK(launch_gn_rhs(w, h, fx, fy, d2, ft, b, S.s));
-    FOTO_HIP_CHECK(launch_gn_pcg_init(w, h, fx, fy, d2, alpha, lam, b, r, z, rb, g_rz, S.s));
-    CGScal* hS = nullptr;
-    FOTO_HIP_CHECK(hipHostMalloc((void**)&hS, sizeof(CGScal)));
-    std::unique_ptr<CGScal, void (*)(CGScal*)> hguard(hS, [](CGScal* p) { (void)hipHostFree(p); });
-    int k = 0;
-    bool done = false;
-    {
-        while (k < maxiter) {
-            const int chunk = std::min(k == 0 ? 64 : 32, maxiter - k);
-            for (int j = 0; j < chunk; ++j, ++k) {
-                double* po = (k & 1) ? p1 : p0;
-                double* pn = (k & 1) ? p0 : p1;
-                FOTO_HIP_CHECK(launch_gn_pcg_dir(w, h, k, fx, fy, d2, alpha, lam, z, po, pn, dS, rb, g_rz, g_pq, rtol,
-                                                 S.s));
-                FOTO_HIP_CHECK(launch_gn_pcg_upd(w, h, k, fx, fy, d2, alpha, lam, pn, x, r, z, dS, rb, g_pq, g_rz,
-                                                 S.s));
-            }
-            FOTO_HIP_CHECK(hipMemcpyAsync(hS, dS, sizeof(CGScal), hipMemcpyDeviceToHost, S.s));
-            FOTO_TRY(S.sync());
-            if (hS->done) { done = true; break; }
-        }
-    }
-    FOTO_TRY(S.down(u, x, n));
-    FOTO_TRY(S.down(v, x + n, n));
-    FOTO_TRY(S.down(m, x + 2 * n, n));
-    FOTO_TRY(S.sync());
-    if (iterations) *iterations = done ? hS->iters : maxiter;
-    if (st) {   // (no plan, no multigrid: 3 fields of 10 + 3 coefficient + 6 block-inverse values)
+    const int rc = gn_bj_solve(f1, f2, w, h, alpha, lam, rtol, maxiter, u, v, m, iterations);
+    if (st && rc >= 0) {   // (no plan, no multigrid: 3 fields of 10 + 3 coefficient + 6 block-inverse values)
         st->levels = 0;
-        st->alg_bytes_per_iter = 8.0 * (double)n * (3 * 10 + 3 + 6);
+        st->alg_bytes_per_iter = 8.0 * (double)w * h * (3 * 10 + 3 + 6);
     }
-    return done ? 0 : maxiter;
+    return rc;
 }
 
 }  // extern "C"

@@ -9,20 +9,15 @@
 // smoothing with the per-pixel 3x3 block D + v v^T, v = (fx, fy, -f2); FOTO_GN_MG=0 keeps
 // plain block-Jacobi PCG), driven on the device with the same last-block reductions as
 // the BB CG and replayed as a hipGraph.
+#include <algorithm>
 #include <chrono>
+#include <cstring>
+#include <memory>
+#include <vector>
 
+#include "foto_hostpool.h"
 #include "foto_internal.h"
 #include "foto_reduce.h"
-
-#include <algorithm>
-#include <atomic>
-#include <condition_variable>
-#include <cstring>
-#include <functional>
-#include <memory>
-#include <mutex>
-#include <thread>
-#include <vector>
 
 namespace foto {
 
@@ -98,54 +93,28 @@ __device__ __forceinline__ GNPix gn_pix(int w, int h, int64_t i) {
     return P;
 }
 
-// one field's Laplacian block row in CSR order: (y-1), (x-1), diag, (x+1), (y+1)
-// The five values are fetched unconditionally (clamped indices) and the missing neighbours
-// skipped by selects: with the fetches behind branches every neighbour was its own memory
-// round trip (~25 us per PCG kernel at 640x480).  Same additions in the same order.
-template <class F>
-__device__ __forceinline__ double gn_lap_row(const GNPix& P, int w, int64_t i, double coef, double dg, F val,
-                                             double s) {
-    const double m = -coef;
-    const double vym = val(P.hy ? i - w : i), vxm = val(P.hx ? i - 1 : i), vc = val(i);
-    const double vxp = val(P.hX ? i + 1 : i), vyp = val(P.hY ? i + w : i);
-    s = P.hy ? s + m * vym : s;
-    s = P.hx ? s + m * vxm : s;
-    s += dg * vc;
-    s = P.hX ? s + m * vxp : s;
-    s = P.hY ? s + m * vyp : s;
-    return s;
+// The five stencil indices of pixel i in CSR order: (y-1), (x-1), centre, (x+1), (y+1).  A missing
+// neighbour is fetched at the centre's index (clamped) and skipped by a select in gn_lap_row:
+// with the fetches behind branches every neighbour was its own memory round trip (~25 us per
+// PCG kernel at 640x480).
+__device__ __forceinline__ void gn_idx5(const GNPix& P, int w, int64_t i, int64_t (&j)[5]) {
+    j[0] = P.hy ? i - w : i; j[1] = P.hx ? i - 1 : i; j[2] = i; j[3] = P.hX ? i + 1 : i; j[4] = P.hY ? i + w : i;
 }
 
-// (A z)_i for all three fields; F(field, index) -> value of the vector being multiplied.
+// v[f][k] = val(f, j_k): the stencil values of all three fields at pixel i
 template <class F>
-__device__ __forceinline__ void gn_row(const GNPix& P, int w, int64_t n, int64_t i, double fx, double fy, double f2,
-                                       double a, double l, F val, double& yu, double& yv, double& ym) {
-    auto U = [&](int64_t j) { return val(0, j); };
-    auto V = [&](int64_t j) { return val(1, j); };
-    auto Mm = [&](int64_t j) { return val(2, j); };
-    const double ui = val(0, i), vi = val(1, i), mi = val(2, i);
-    double s = gn_lap_row(P, w, i, a, a * P.c + fx * fx, U, 0.0);
-    s += (fx * fy) * vi;
-    s += (-fx * f2) * mi;
-    yu = s;
-    s = 0.0;
-    s += (fy * fx) * ui;   // CSR order: the u column precedes the v block
-    s = gn_lap_row(P, w, i, a, a * P.c + fy * fy, V, s);
-    s += (-fy * f2) * mi;
-    yv = s;
-    s = 0.0;
-    s += (-f2 * fx) * ui;
-    s += (-f2 * fy) * vi;
-    s = gn_lap_row(P, w, i, l, l * P.c + f2 * f2, Mm, s);
-    ym = s;
-    (void)n;
+__device__ __forceinline__ void gn_gather5(const GNPix& P, int w, int64_t i, F val, double (&v)[3][5]) {
+    int64_t j[5];
+    gn_idx5(P, w, i, j);
+#pragma unroll
+    for (int f = 0; f < 3; ++f)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) v[f][k] = val(f, j[k]);
 }
 
-// gn_row with the five stencil values of each field already fetched: V(f, k), k in CSR order
-// (y-1, x-1, centre, x+1, y+1; missing neighbours fetched at the centre's index, as gn_lap_row
-// does) -- the same additions in the same order
+// one field's Laplacian block row in CSR order over its five fetched values val(k)
 template <class F>
-__device__ __forceinline__ double gn_lap_row_v(const GNPix& P, double coef, double dg, F val, double s) {
+__device__ __forceinline__ double gn_lap_row(const GNPix& P, double coef, double dg, F val, double s) {
     const double m = -coef;
     s = P.hy ? s + m * val(0) : s;
     s = P.hx ? s + m * val(1) : s;
@@ -155,23 +124,25 @@ __device__ __forceinline__ double gn_lap_row_v(const GNPix& P, double coef, doub
     return s;
 }
 
+// (A z)_i for all three fields; val(f, k) = the k-th stencil value (gn_idx5's order) of field f
+// of the vector being multiplied
 template <class F>
-__device__ __forceinline__ void gn_row_v(const GNPix& P, double fx, double fy, double f2, double a, double l, F val,
-                                         double& yu, double& yv, double& ym) {
+__device__ __forceinline__ void gn_row(const GNPix& P, double fx, double fy, double f2, double a, double l, F val,
+                                       double& yu, double& yv, double& ym) {
     const double ui = val(0, 2), vi = val(1, 2), mi = val(2, 2);
-    double s = gn_lap_row_v(P, a, a * P.c + fx * fx, [&](int k) { return val(0, k); }, 0.0);
+    double s = gn_lap_row(P, a, a * P.c + fx * fx, [&](int k) { return val(0, k); }, 0.0);
     s += (fx * fy) * vi;
     s += (-fx * f2) * mi;
     yu = s;
     s = 0.0;
-    s += (fy * fx) * ui;
-    s = gn_lap_row_v(P, a, a * P.c + fy * fy, [&](int k) { return val(1, k); }, s);
+    s += (fy * fx) * ui;   // CSR order: the u column precedes the v block
+    s = gn_lap_row(P, a, a * P.c + fy * fy, [&](int k) { return val(1, k); }, s);
     s += (-fy * f2) * mi;
     yv = s;
     s = 0.0;
     s += (-f2 * fx) * ui;
     s += (-f2 * fy) * vi;
-    s = gn_lap_row_v(P, l, l * P.c + f2 * f2, [&](int k) { return val(2, k); }, s);
+    s = gn_lap_row(P, l, l * P.c + f2 * f2, [&](int k) { return val(2, k); }, s);
     ym = s;
 }
 
@@ -183,8 +154,9 @@ __global__ __launch_bounds__(NT) void k_gn_apply(int w, int h, const double* __r
     const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
     if (i >= n) return;
     const GNPix P = gn_pix(w, h, i);
-    double yu, yv, ym;
-    gn_row(P, w, n, i, fx[i], fy[i], f2[i], a, l, [&](int f, int64_t j) { return x[f * n + j]; }, yu, yv, ym);
+    double xv[3][5], yu, yv, ym;
+    gn_gather5(P, w, i, [&](int f, int64_t j) { return x[f * n + j]; }, xv);
+    gn_row(P, fx[i], fy[i], f2[i], a, l, [&](int f, int k) { return xv[f][k]; }, yu, yv, ym);
     y[i] = yu;
     y[n + i] = yv;
     y[2 * n + i] = ym;
@@ -233,12 +205,6 @@ __global__ __launch_bounds__(NT) void k_gn_pcg_init(int w, int h, const double* 
     if (grid_reduce_last<2>(v, rb, tot) && threadIdx.x == 0) { gath[0] = tot[0]; gath[1] = tot[1]; }
 }
 
-hipError_t launch_gn_pcg_init(int w, int h, const double* fx, const double* fy, const double* f2, double alpha,
-                              double lam, const double* b, double* r, double* z, RedBuf rb, double* gath,
-                              hipStream_t s) {
-    k_gn_pcg_init<<<gn_grid((int64_t)w * h), NT, 0, s>>>(w, h, fx, fy, f2, alpha, lam, b, r, z, rb, gath);
-    return hipGetLastError();
-}
 
 // Iteration k, first half: stop test on ||r||, beta = rz / rz_prev, p = z + beta p (computed
 // for the pixel and its 4 neighbours), q = A p, partial p.q; writes p.
@@ -266,9 +232,10 @@ __global__ __launch_bounds__(NT) void k_gn_pcg_dir(int w, int h, int k_arg, cons
             const int64_t o = f * n + j;
             return (k == 0) ? z[o] : beta * po[o] + z[o];
         };
-        double qu, qv, qm;
-        gn_row(P, w, n, i, fx[i], fy[i], f2[i], a, l, pv, qu, qv, qm);
-        const double pu = pv(0, i), pvv = pv(1, i), pm = pv(2, i);
+        double p5[3][5], qu, qv, qm;
+        gn_gather5(P, w, i, pv, p5);
+        gn_row(P, fx[i], fy[i], f2[i], a, l, [&](int f, int q) { return p5[f][q]; }, qu, qv, qm);
+        const double pu = p5[0][2], pvv = p5[1][2], pm = p5[2][2];
         pn[i] = pu; pn[n + i] = pvv; pn[2 * n + i] = pm;
         pq += pu * qu + pvv * qv + pm * qm;
     }
@@ -280,13 +247,6 @@ __global__ __launch_bounds__(NT) void k_gn_pcg_dir(int w, int h, int k_arg, cons
     }
 }
 
-hipError_t launch_gn_pcg_dir(int w, int h, int k, const double* fx, const double* fy, const double* f2, double alpha,
-                             double lam, const double* z, const double* pold, double* pnew, CGScal* S, RedBuf rb,
-                             const double* gath_rz, double* gath_pq, double rtol, hipStream_t s) {
-    k_gn_pcg_dir<<<gn_grid((int64_t)w * h), NT, 0, s>>>(w, h, k, fx, fy, f2, alpha, lam, z, pold, pnew, S, rb,
-                                                            gath_rz, gath_pq, rtol);
-    return hipGetLastError();
-}
 
 // second half: alpha = rz / p.q; x += alpha p; r -= alpha A p; z = M r; partials (r.r, r.z)
 __global__ __launch_bounds__(NT) void k_gn_pcg_upd(int w, int h, int k, const double* __restrict__ fx,
@@ -302,8 +262,9 @@ __global__ __launch_bounds__(NT) void k_gn_pcg_upd(int w, int h, int k, const do
     for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
         const GNPix P = gn_pix(w, h, i);
         const double cfx = fx[i], cfy = fy[i], cf2 = f2[i];
-        double qu, qv, qm;
-        gn_row(P, w, n, i, cfx, cfy, cf2, a, l, [&](int f, int64_t j) { return p[f * n + j]; }, qu, qv, qm);
+        double p5[3][5], qu, qv, qm;
+        gn_gather5(P, w, i, [&](int f, int64_t j) { return p[f * n + j]; }, p5);
+        gn_row(P, cfx, cfy, cf2, a, l, [&](int f, int q) { return p5[f][q]; }, qu, qv, qm);
         const double q3[3] = {qu, qv, qm};
         double rn[3];
 #pragma unroll
@@ -327,15 +288,71 @@ __global__ __launch_bounds__(NT) void k_gn_pcg_upd(int w, int h, int k, const do
     }
 }
 
-hipError_t launch_gn_pcg_upd(int w, int h, int k, const double* fx, const double* fy, const double* f2, double alpha,
-                             double lam, const double* p, double* x, double* r, double* z, CGScal* S, RedBuf rb,
-                             const double* gath_pq, double* gath_rz, hipStream_t s) {
-    k_gn_pcg_upd<<<gn_grid((int64_t)w * h), NT, 0, s>>>(w, h, k, fx, fy, f2, alpha, lam, p, x, r, z, S, rb,
-                                                            gath_pq, gath_rz);
-    return hipGetLastError();
+
+
+
+// The block-Jacobi PCG's driver (FOTO_GN_MG=0; kept for A/B runs): a device-resident loop, the
+// host polls the done flag between chunks of iterations.
+int gn_bj_solve(const double* f1, const double* f2, int w, int h, double alpha, double lam, double rtol, int maxiter,
+                double* u, double* v, double* m, int* iterations) {
+    struct Call {   // the call's stream, its one device allocation and the pinned scalars
+        hipStream_t s = nullptr;
+        double* base = nullptr;
+        CGScal* hS = nullptr;
+        ~Call() {
+            if (s) (void)hipStreamSynchronize(s);
+            if (base) (void)hipFree(base);
+            if (hS) (void)hipHostFree(hS);
+            stream_release(s);
+        }
+    } C;
+    FOTO_TRY(stream_acquire(&C.s));
+    hipStream_t s = C.s;
+    const size_t n = (size_t)w * h;
+    const int nb = flat_blocks((int64_t)n), grid = gn_grid((int64_t)n);
+    // one allocation (a solve is ~15 ms; per-buffer hipMalloc/hipFree added up to ~1 ms)
+    const size_t nscal = sizeof(CGScal) / sizeof(double) + 1;
+    FOTO_HIP_CHECK(hipMalloc((void**)&C.base, (23 * n + 2 * (size_t)nb + 8 + 8 + nscal) * sizeof(double)));
+    double *d1 = C.base, *d2 = d1 + n, *fx = d2 + n, *fy = fx + n, *ft = fy + n, *b = ft + n, *x = b + 3 * n,
+           *r = x + 3 * n, *z = r + 3 * n, *p0 = z + 3 * n, *p1 = p0 + 3 * n, *part = p1 + 3 * n,
+           *gath = part + 2 * (size_t)nb + 8;
+    CGScal* dS = (CGScal*)(gath + 8);
+    FOTO_HIP_CHECK(hipMemcpyAsync(d1, f1, n * sizeof(double), hipMemcpyHostToDevice, s));
+    FOTO_HIP_CHECK(hipMemcpyAsync(d2, f2, n * sizeof(double), hipMemcpyHostToDevice, s));
+    FOTO_HIP_CHECK(hipMemsetAsync(part + 2 * nb, 0, 8 * sizeof(double), s));
+    FOTO_HIP_CHECK(hipMemsetAsync(dS, 0, sizeof(CGScal), s));
+    FOTO_HIP_CHECK(hipMemsetAsync(x, 0, 3 * n * sizeof(double), s));
+    const RedBuf rb{part, (unsigned*)(part + 2 * nb), 2 * nb};
+    double* g_rz = gath;       // {r.r, r.z}
+    double* g_pq = gath + 2;   // {p.q}
+    FOTO_HIP_CHECK(launch_gn_coeffs(w, h, d1, d2, fx, fy, ft, s));
+    FOTO_HIP_CHECK(launch_gn_rhs(w, h, fx, fy, d2, ft, b, s));
+    k_gn_pcg_init<<<grid, NT, 0, s>>>(w, h, fx, fy, d2, alpha, lam, b, r, z, rb, g_rz);
+    FOTO_HIP_CHECK(hipGetLastError());
+    FOTO_HIP_CHECK(hipHostMalloc((void**)&C.hS, sizeof(CGScal)));
+    int k = 0;
+    bool done = false;
+    while (k < maxiter) {
+        const int chunk = std::min(k == 0 ? 64 : 32, maxiter - k);
+        for (int j = 0; j < chunk; ++j, ++k) {
+            double* po = (k & 1) ? p1 : p0;
+            double* pn = (k & 1) ? p0 : p1;
+            k_gn_pcg_dir<<<grid, NT, 0, s>>>(w, h, k, fx, fy, d2, alpha, lam, z, po, pn, dS, rb, g_rz, g_pq, rtol);
+            FOTO_HIP_CHECK(hipGetLastError());
+            k_gn_pcg_upd<<<grid, NT, 0, s>>>(w, h, k, fx, fy, d2, alpha, lam, pn, x, r, z, dS, rb, g_pq, g_rz);
+            FOTO_HIP_CHECK(hipGetLastError());
+        }
+        FOTO_HIP_CHECK(hipMemcpyAsync(C.hS, dS, sizeof(CGScal), hipMemcpyDeviceToHost, s));
+        FOTO_HIP_CHECK(hipStreamSynchronize(s));
+        if (C.hS->done) { done = true; break; }
+    }
+    double* const outs[3] = {u, v, m};
+    for (int c = 0; c < 3; ++c)
+        FOTO_HIP_CHECK(hipMemcpyAsync(outs[c], x + c * n, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    FOTO_HIP_CHECK(hipStreamSynchronize(s));
+    if (iterations) *iterations = done ? C.hS->iters : maxiter;
+    return done ? 0 : maxiter;
 }
-
-
 
 // ============================================================================ multigrid-preconditioned CG
 //
@@ -352,13 +369,24 @@ hipError_t launch_gn_pcg_upd(int w, int h, int k, const double* fx, const double
 // here only changes the preconditioner: the PCG applies the exact operator (gn_row, CSR
 // order) and stops on the exact residual norm.
 //
-// Launch structure (13 kernels per PCG iteration at 640x480, replayed as a hipGraph):
+// Launch structure (10 kernels per PCG iteration at 640x480 with the default switches, 13 with
+// FOTO_GN_FOLD=0 FOTO_MG_LTAIL=0; replayed as a hipGraph):
 //   k_gnp_dir   stop test, beta, p = z + beta p, q = A p, partial p.q
-//   k_gnp_upd   alpha, x += alpha p, r -= alpha A p, partial r.r
+//   k_gnp_upd   alpha, x += alpha p, r -= alpha A p, partial r.r (FOTO_GN_FOLD=0 or one level;
+//               default: folded into level 0's k_mg_down2<true>)
 //   k_mg_down2  per level: pre-smoothing from zero, residual and restriction in one LDS tile
 //   k_mg_coarse the coarsest level in one block
+//   k_mg_ltail  the level above the coarsest (down leg, up leg) and the coarsest in one block, in
+//               LDS, where they fit (default; FOTO_MG_LTAIL=0: their k_mg_down2, k_mg_coarse, k_mg_up2)
 //   k_mg_up2    per level: prolongation of the coarse correction and post-smoothing in one
 //               LDS tile (level 0: z and the partial r.z)
+// Shared by every kernel above that needs them: gn_row (the operator row), mg_apply_b, mg_dinv_v,
+// mg_load6, mg_b_from / mg_dinv_vals, mg_pcells, mg_cell, mg_alpha, gn_upd_field.  Still written
+// out once per kernel, because a shared function changed the code generated for the level kernels
+// (profiles/gn_refactor_resources.txt): the restriction's taps and sums (k_mg_down2,
+// k_mg_ltail, k_mg_coarsen_d), the prolongation's weighted sum (k_mg_up2, k_mg_ltail) and the
+// coarsest level's sweeps (k_mg_coarse, k_mg_ltail).  A change to one of these goes to each copy;
+// test_gn_round5_forms_bit_identical holds them together, at 71x77 with odd extents on both levels.
 // Global sums are consumer-side: every reducing kernel stores one partial per block (no
 // atomics, no ticket), and every kernel that needs the sum adds the partials in the same
 // fixed order in each of its blocks, so all blocks take identical decisions.
@@ -389,24 +417,23 @@ __device__ __forceinline__ double mg_w1(int i, int I, int nc) {
     return (I0 == I ? 0.75 : 0.0) + (I1 == I ? 0.25 : 0.0);
 }
 
-__device__ __forceinline__ void mg_dinv(const MGLev& L, int64_t i, double r0, double r1, double r2, double& z0,
-                                        double& z1, double& z2) {
-    const int64_t n = (int64_t)L.w * L.h;
-    const double* D = L.Dinv;
-    const double d00 = D[i], d01 = D[n + i], d02 = D[2 * n + i], d11 = D[3 * n + i], d12 = D[4 * n + i],
-                 d22 = D[5 * n + i];
-    z0 = d00 * r0 + d01 * r1 + d02 * r2;
-    z1 = d01 * r0 + d11 * r1 + d12 * r2;
-    z2 = d02 * r0 + d12 * r1 + d22 * r2;
-}
-
 // the cell's 6 coefficient planes (B or Dinv: xx xy xm yy ym mm) into registers
 __device__ __forceinline__ void mg_load6(const double* __restrict__ P, int64_t n, int64_t i, double (&c)[6]) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) c[k] = P[k * n + i];
 }
 
-// mg_dinv with the cell's inverse block already in registers (the same arithmetic)
+// level 0's B of a cell from the GN coefficients (fx, fy, f2) there: v v^T, v = (fx, fy, -f2)
+__device__ __forceinline__ void mg_b_from(double a, double b, double m, double (&B)[6]) {
+    B[0] = a * a;
+    B[1] = a * b;
+    B[2] = -a * m;
+    B[3] = b * b;
+    B[4] = -b * m;
+    B[5] = m * m;
+}
+
+// z = D^-1 r with the cell's symmetric inverse block in registers
 __device__ __forceinline__ void mg_dinv_v(const double (&d)[6], double r0, double r1, double r2, double& z0,
                                           double& z1, double& z2) {
     z0 = d[0] * r0 + d[1] * r1 + d[2] * r2;
@@ -414,7 +441,8 @@ __device__ __forceinline__ void mg_dinv_v(const double (&d)[6], double r0, doubl
     z2 = d[2] * r0 + d[4] * r1 + d[5] * r2;
 }
 
-// (A x) of cell (x, y) with the cell's B in registers (mg_apply_t's arithmetic)
+// (A x) of cell (x, y) of level L with the cell's B in registers: X(f, dy, dx) is the value of
+// field f at the neighbour offset (dy, dx) in {-1, 0, 1}; neighbours outside the grid are skipped
 template <class F>
 __device__ __forceinline__ void mg_apply_b(const MGLev& L, int x, int y, const double (&B)[6], F X, double& a0,
                                            double& a1, double& a2, double& v0, double& v1, double& v2) {
@@ -433,28 +461,32 @@ __device__ __forceinline__ void mg_apply_b(const MGLev& L, int x, int y, const d
     v0 = v[0]; v1 = v[1]; v2 = v[2];
 }
 
-// (A x) of cell (x, y) = global index i, with the vector in an LDS tile: X(f, dy, dx) is the
-// value at the neighbour offset (dy, dx) in {-1, 0, 1}; neighbours outside the grid are skipped
-template <class F>
-__device__ __forceinline__ void mg_apply_t(const MGLev& L, int x, int y, int64_t i, F X, double& a0, double& a1,
-                                           double& a2, double& v0, double& v1, double& v2) {
-    const int64_t n = (int64_t)L.w * L.h;
-    const bool hxm = x > 0, hxp = x < L.w - 1, hym = y > 0, hyp = y < L.h - 1;
-    const double c = (double)((int)hxm + (int)hxp + (int)hym + (int)hyp);
-    double v[3], nb[3];
-#pragma unroll
-    for (int f = 0; f < 3; ++f) {
-        v[f] = X(f, 0, 0);
-        nb[f] = (hxm ? X(f, 0, -1) : 0.0) + (hxp ? X(f, 0, 1) : 0.0) + (hym ? X(f, -1, 0) : 0.0) +
-                (hyp ? X(f, 1, 0) : 0.0);
-    }
-    const double* B = L.B;
-    const double bxx = B[i], bxy = B[n + i], bxm = B[2 * n + i], byy = B[3 * n + i], bym = B[4 * n + i],
-                 bmm = B[5 * n + i];
-    a0 = L.s0 * (c * v[0] - nb[0]) + bxx * v[0] + bxy * v[1] + bxm * v[2];
-    a1 = L.s1 * (c * v[1] - nb[1]) + bxy * v[0] + byy * v[1] + bym * v[2];
-    a2 = L.s2 * (c * v[2] - nb[2]) + bxm * v[0] + bym * v[1] + bmm * v[2];
-    v0 = v[0]; v1 = v[1]; v2 = v[2];
+// Prolongation P (cell-centred bilinear): the coarse cells fine cell (gx, gy) interpolates from,
+// its own (gx / 2, gy / 2) and the nearer neighbour per axis clamped at the boundary, as indices
+// into a wc x hc plane in the order of the weights 9/16, 3/16 (x partner), 3/16 (y partner), 1/16
+// (the callers write the weighted sum out: as a function it changed their generated code)
+template <class I>
+__device__ __forceinline__ void mg_pcells(int gx, int gy, int wc, int hc, I (&c)[4]) {
+    const int X0 = gx >> 1, Y0 = gy >> 1;
+    int X1 = (gx & 1) ? X0 + 1 : X0 - 1, Y1 = (gy & 1) ? Y0 + 1 : Y0 - 1;
+    X1 = X1 < 0 ? 0 : (X1 > wc - 1 ? wc - 1 : X1);
+    Y1 = Y1 < 0 ? 0 : (Y1 > hc - 1 ? hc - 1 : Y1);
+    c[0] = (I)Y0 * wc + X0; c[1] = (I)Y0 * wc + X1; c[2] = (I)Y1 * wc + X0; c[3] = (I)Y1 * wc + X1;
+}
+
+// Cell c of a block's (GT_Y + 2 H) x (GT_X + 2 H) region, the tile at (x0, y0) with H halo cells:
+// its place in the region and in the grid.  (The in-grid test stays at the call sites: as a member
+// it merged their branches.  Two sites keep the divisions written out too: k_mg_down2's residual
+// stage and k_mg_up2's prolongation stage, whose generated code a call of mg_cell changed.)
+struct MGCell {
+    int ly, lx, gy, gx;
+};
+template <int H>
+__device__ __forceinline__ MGCell mg_cell(int c, int x0, int y0) {
+    constexpr int RW = GT_X + 2 * H;
+    MGCell t;
+    t.ly = c / RW; t.lx = c - t.ly * RW; t.gy = y0 - H + t.ly; t.gx = x0 - H + t.lx;
+    return t;
 }
 
 // ----------------------------------------------------------------------------- consumer-side sums
@@ -496,6 +528,28 @@ __device__ __forceinline__ void mg_block_partial(double v, double* dst) {
     }
 }
 
+// alpha = rz_k / p.q of a PCG iteration from the producers' partials (nb_rz of r.z, nb_pq of p.q)
+__device__ __forceinline__ double mg_alpha(const double* rz_cur, int nb_rz, const double* pq_part, int nb_pq) {
+    const double* s1[1] = {rz_cur};
+    double o1[1];
+    mg_sum_partials<1>(s1, nb_rz, o1);
+    const double* s2[1] = {pq_part};
+    double o2[1];
+    __syncthreads();   // mg_sum_partials' LDS is reused
+    mg_sum_partials<1>(s2, nb_pq, o2);
+    return o1[0] / o2[0];
+}
+
+// the PCG update of one field of one pixel (o = field * n + pixel; the callers go in field order):
+// x += alpha p, r' -> rnew (r' = r - alpha A p is formed by the caller: the down leg needs it on
+// its halo too); returns the r'.r' term
+__device__ __forceinline__ double gn_upd_field(int64_t o, double alpha, const double* p, double* x, double* rnew,
+                                               double rn) {
+    x[o] = x[o] + alpha * p[o];
+    rnew[o] = rn;
+    return rn * rn;
+}
+
 // ----------------------------------------------------------------------------- PCG kernels
 
 // r = b, partial r.r
@@ -535,7 +589,8 @@ __global__ __launch_bounds__(NT) void k_gnp_dir(int w, int h, const double* __re
     const GNPix P = gn_pix(w, h, in ? i : 0);
     double zv[3][5], pv5[3][5], cfx = 0.0, cfy = 0.0, cf2 = 0.0;
     {
-        const int64_t j5[5] = {P.hy ? i - w : i, P.hx ? i - 1 : i, i, P.hX ? i + 1 : i, P.hY ? i + w : i};
+        int64_t j5[5];
+        gn_idx5(P, w, i, j5);
 #pragma unroll
         for (int f = 0; f < 3; ++f)
 #pragma unroll
@@ -573,7 +628,7 @@ __global__ __launch_bounds__(NT) void k_gnp_dir(int w, int h, const double* __re
     if (in) {
         auto pv = [&](int f, int q) -> double { return (k == 0) ? zv[f][q] : beta * pv5[f][q] + zv[f][q]; };
         double qu, qv, qm;
-        gn_row_v(P, cfx, cfy, cf2, a, l, pv, qu, qv, qm);
+        gn_row(P, cfx, cfy, cf2, a, l, pv, qu, qv, qm);
         const double pu = pv(0, 2), pvv = pv(1, 2), pm = pv(2, 2);
         pn[i] = pu; pn[n + i] = pvv; pn[2 * n + i] = pm;
         if (qout) { qout[i] = qu; qout[n + i] = qv; qout[2 * n + i] = qm; }   // (the folded update's A p)
@@ -590,32 +645,20 @@ __global__ __launch_bounds__(NT) void k_gnp_upd(int w, int h, const double* __re
                                                 const double* rz_cur, int nb_rz, const double* pq_part, int nb_pq,
                                                 double* __restrict__ rr_part) {
     if (S->done) return;
-    double alpha;
-    {
-        const double* s1[1] = {rz_cur};
-        double o1[1];
-        mg_sum_partials<1>(s1, nb_rz, o1);
-        const double* s2[1] = {pq_part};
-        double o2[1];
-        __syncthreads();
-        mg_sum_partials<1>(s2, nb_pq, o2);
-        alpha = o1[0] / o2[0];
-    }
+    const double alpha = mg_alpha(rz_cur, nb_rz, pq_part, nb_pq);
     const int64_t n = (int64_t)w * h;
     const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
     double rr = 0.0;
     if (i < n) {
         const GNPix P = gn_pix(w, h, i);
-        double qu, qv, qm;
-        gn_row(P, w, n, i, fx[i], fy[i], f2[i], a, l, [&](int f, int64_t j) { return p[f * n + j]; }, qu, qv, qm);
+        double p5[3][5], qu, qv, qm;
+        gn_gather5(P, w, i, [&](int f, int64_t j) { return p[f * n + j]; }, p5);
+        gn_row(P, fx[i], fy[i], f2[i], a, l, [&](int f, int q) { return p5[f][q]; }, qu, qv, qm);
         const double q3[3] = {qu, qv, qm};
 #pragma unroll
         for (int f = 0; f < 3; ++f) {
             const int64_t o = f * n + i;
-            x[o] = x[o] + alpha * p[o];
-            const double rn = r[o] - alpha * q3[f];
-            r[o] = rn;
-            rr += rn * rn;
+            rr += gn_upd_field(o, alpha, p, x, r, r[o] - alpha * q3[f]);
         }
     }
     mg_block_partial(rr, rr_part);
@@ -635,13 +678,10 @@ __global__ __launch_bounds__(NT) void k_mg_b0(int64_t n, const double* __restric
                                               const double* __restrict__ f2, double* __restrict__ B) {
     const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
     if (i >= n) return;
-    const double a = fx[i], b = fy[i], m = f2[i];
-    B[i] = a * a;
-    B[n + i] = a * b;
-    B[2 * n + i] = -a * m;
-    B[3 * n + i] = b * b;
-    B[4 * n + i] = -b * m;
-    B[5 * n + i] = m * m;
+    double Bv[6];
+    mg_b_from(fx[i], fy[i], f2[i], Bv);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) B[k * n + i] = Bv[k];
 }
 
 // coarse B = (sum of children B weighted by the P weights) / (sum of those weights)
@@ -694,16 +734,6 @@ __device__ __forceinline__ void mg_dinv_cell(const MGLev& L, int x, int y, int64
     for (int k = 0; k < 6; ++k) Dinv[k * n + i] = D[k];
 }
 
-// level 0's B of a cell from the GN coefficients (fx, fy, f2) there: v v^T, v = (fx, fy, -f2)
-__device__ __forceinline__ void mg_b_from(double a, double b, double m, double (&B)[6]) {
-    B[0] = a * a;
-    B[1] = a * b;
-    B[2] = -a * m;
-    B[3] = b * b;
-    B[4] = -b * m;
-    B[5] = m * m;
-}
-
 // the GN coefficient planes level 0's B and D^-1 are made of (round 6: the PCG's level-0 legs
 // form both per cell from these 24 B instead of loading the stored 96 B; FOTO_GN_RECOMP=0: load)
 struct MGCoef {
@@ -717,7 +747,8 @@ __global__ __launch_bounds__(NT) void k_mg_dinv(MGLev L, double* __restrict__ Di
     const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
     if (i >= n) return;
     const int y = (int)(i / L.w), x = (int)(i - (int64_t)y * L.w);
-    const double Bv[6] = {L.B[i], L.B[n + i], L.B[2 * n + i], L.B[3 * n + i], L.B[4 * n + i], L.B[5 * n + i]};
+    double Bv[6];
+    mg_load6(L.B, n, i, Bv);
     mg_dinv_cell(L, x, y, i, Bv, Dinv);
 }
 
@@ -746,6 +777,7 @@ __global__ __launch_bounds__(NT) void k_mg_coarsen_d(int w, int h, const double*
     const int I = blockIdx.x * NT + threadIdx.x;
     if (I >= nc) return;
     const int J = I / C.w, K = I - J * C.w;
+    // (R's tap weights: the same as k_mg_down2's, written out)
     double wy[4], wx[4];
     int ro[4], co[4];
 #pragma unroll
@@ -834,9 +866,9 @@ __global__ __launch_bounds__(NT) void k_mg_down2(MGLev L, int wc, int hc, const 
 #pragma unroll
         for (int k = 0; k < C2; ++k) {
             const int c = threadIdx.x + k * NT;
-            const int ly = c / RW, lx = c - ly * RW, gy = y0 - 1 + ly, gx = x0 - 1 + lx;
-            if (c < RH * RW && gx >= 0 && gx < w && gy >= 0 && gy < h) {
-                const int64_t i = (int64_t)gy * w + gx;
+            const MGCell t = mg_cell<1>(c, x0, y0);
+            if (c < RH * RW && t.gx >= 0 && t.gx < w && t.gy >= 0 && t.gy < h) {
+                const int64_t i = (int64_t)t.gy * w + t.gx;
                 if constexpr (RC) {
                     b2[k][0] = U.cf.fx[i]; b2[k][1] = U.cf.fy[i]; b2[k][2] = U.cf.f2[i];
                 } else {
@@ -855,9 +887,9 @@ __global__ __launch_bounds__(NT) void k_mg_down2(MGLev L, int wc, int hc, const 
 #pragma unroll
     for (int k = 0; k < C1; ++k) {
         const int c = threadIdx.x + k * NT;
-        const int ly = c / XW, lx = c - ly * XW, gy = y0 - 2 + ly, gx = x0 - 2 + lx;
-        if (c < XH * XW && gx >= 0 && gx < w && gy >= 0 && gy < h) {
-            const int64_t i = (int64_t)gy * w + gx;
+        const MGCell t = mg_cell<2>(c, x0, y0);
+        if (c < XH * XW && t.gx >= 0 && t.gx < w && t.gy >= 0 && t.gy < h) {
+            const int64_t i = (int64_t)t.gy * w + t.gx;
             if constexpr (UPD) {
                 f1[k][0] = U.rold[i]; f1[k][1] = U.rold[n + i]; f1[k][2] = U.rold[2 * n + i];
             } else {
@@ -879,20 +911,13 @@ __global__ __launch_bounds__(NT) void k_mg_down2(MGLev L, int wc, int hc, const 
 #pragma unroll
         for (int k = 0; k < C1; ++k) {
             const int c = threadIdx.x + k * NT;
-            const int ly = c / XW, lx = c - ly * XW, gy = y0 - 2 + ly, gx = x0 - 2 + lx;
-            const bool in = c < XH * XW && gx >= 0 && gx < w && gy >= 0 && gy < h;
-            const int64_t i = in ? (int64_t)gy * w + gx : 0;
+            const MGCell t = mg_cell<2>(c, x0, y0);
+            const bool in = c < XH * XW && t.gx >= 0 && t.gx < w && t.gy >= 0 && t.gy < h;
+            const int64_t i = in ? (int64_t)t.gy * w + t.gx : 0;
 #pragma unroll
             for (int fl = 0; fl < 3; ++fl) qv[k][fl] = in ? U.q[fl * n + i] : 0.0;
         }
-        const double* s1[1] = {U.rz_cur};
-        double o1[1];
-        mg_sum_partials<1>(s1, U.nb_rz, o1);
-        const double* s2[1] = {U.pq_part};
-        double o2[1];
-        __syncthreads();
-        mg_sum_partials<1>(s2, U.nb_pq, o2);
-        alpha = o1[0] / o2[0];
+        alpha = mg_alpha(U.rz_cur, U.nb_rz, U.pq_part, U.nb_pq);
 #pragma unroll
         for (int k = 0; k < C1; ++k)
 #pragma unroll
@@ -903,7 +928,8 @@ __global__ __launch_bounds__(NT) void k_mg_down2(MGLev L, int wc, int hc, const 
     for (int k = 0; k < C1; ++k) {
         const int c = threadIdx.x + k * NT;
         if (c >= XH * XW) continue;
-        const int ly = c / XW, lx = c - ly * XW, gy = y0 - 2 + ly, gx = x0 - 2 + lx;
+        const MGCell t = mg_cell<2>(c, x0, y0);
+        const int ly = t.ly, lx = t.lx, gy = t.gy, gx = t.gx;
         double z0 = 0.0, z1 = 0.0, z2 = 0.0;
         if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
             if constexpr (RC) {
@@ -928,6 +954,7 @@ __global__ __launch_bounds__(NT) void k_mg_down2(MGLev L, int wc, int hc, const 
         const int c = threadIdx.x + k * NT;
         rv[k][0] = rv[k][1] = rv[k][2] = 0.0;
         if (c >= RH * RW) continue;
+        // (mg_cell<1> written out: a call here changed this stage's generated code)
         const int ly = c / RW, lx = c - ly * RW, gy = y0 - 1 + ly, gx = x0 - 1 + lx;
         double r0 = 0.0, r1 = 0.0, r2 = 0.0;
         if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
@@ -945,12 +972,7 @@ __global__ __launch_bounds__(NT) void k_mg_down2(MGLev L, int wc, int hc, const 
                 if constexpr (UPD) {   // k_gnp_upd's stores and its r.r terms, field order
                     const double fr[3] = {fa, fb, fcv};
 #pragma unroll
-                    for (int fl = 0; fl < 3; ++fl) {
-                        const int64_t o = fl * n + i;
-                        U.x[o] = U.x[o] + alpha * U.p[o];
-                        U.rnew[o] = fr[fl];
-                        rr += fr[fl] * fr[fl];
-                    }
+                    for (int fl = 0; fl < 3; ++fl) rr += gn_upd_field(fl * n + i, alpha, U.p, U.x, U.rnew, fr[fl]);
                 }
             }
         }
@@ -961,8 +983,8 @@ __global__ __launch_bounds__(NT) void k_mg_down2(MGLev L, int wc, int hc, const 
     for (int k = 0; k < C2; ++k) {
         const int c = threadIdx.x + k * NT;
         if (c >= RH * RW) continue;
-        const int ly = c / RW, lx = c - ly * RW;
-        rs[0][ly][lx] = rv[k][0]; rs[1][ly][lx] = rv[k][1]; rs[2][ly][lx] = rv[k][2];
+        const MGCell t = mg_cell<1>(c, x0, y0);
+        rs[0][t.ly][t.lx] = rv[k][0]; rs[1][t.ly][t.lx] = rv[k][1]; rs[2][t.ly][t.lx] = rv[k][2];
     }
     __syncthreads();
     const int64_t nc = (int64_t)wc * hc;
@@ -970,6 +992,7 @@ __global__ __launch_bounds__(NT) void k_mg_down2(MGLev L, int wc, int hc, const 
         const int cy = c / (GT_X / 2), cx = c - cy * (GT_X / 2);
         const int J = y0 / 2 + cy, K = x0 / 2 + cx;
         if (J >= hc || K >= wc) continue;
+        // R = P^T / 4, written out here, in k_mg_ltail and (the weights) in k_mg_coarsen_d
         double wy[4], wx[4];
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
@@ -1020,20 +1043,17 @@ __global__ __launch_bounds__(NT) void k_mg_up2(MGLev L, int wc, int hc, const CG
     const int tiles_x = (w + GT_X - 1) / GT_X;
     const int x0 = (blockIdx.x % tiles_x) * GT_X, y0 = (blockIdx.x / tiles_x) * GT_Y;
     for (int c = threadIdx.x; c < RH * RW; c += NT) {
+        // (mg_cell<1> written out: a call here changed this stage's generated code)
         const int ly = c / RW, lx = c - ly * RW, gy = y0 - 1 + ly, gx = x0 - 1 + lx;
         double v[3] = {0.0, 0.0, 0.0};
         if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
             const int64_t i = (int64_t)gy * w + gx;
-            const int X0 = gx >> 1, Y0 = gy >> 1;
-            int X1 = (gx & 1) ? X0 + 1 : X0 - 1, Y1 = (gy & 1) ? Y0 + 1 : Y0 - 1;
-            X1 = X1 < 0 ? 0 : (X1 > wc - 1 ? wc - 1 : X1);
-            Y1 = Y1 < 0 ? 0 : (Y1 > hc - 1 ? hc - 1 : Y1);
-            const int64_t c00 = (int64_t)Y0 * wc + X0, c01 = (int64_t)Y0 * wc + X1, c10 = (int64_t)Y1 * wc + X0,
-                          c11 = (int64_t)Y1 * wc + X1;
+            int64_t cc[4];
+            mg_pcells(gx, gy, wc, hc, cc);
 #pragma unroll
             for (int fl = 0; fl < 3; ++fl) {
                 const double* e = ec + fl * nc;
-                v[fl] = xg[fl * n + i] + (0.5625 * e[c00] + 0.1875 * e[c01] + 0.1875 * e[c10] + 0.0625 * e[c11]);
+                v[fl] = xg[fl * n + i] + (0.5625 * e[cc[0]] + 0.1875 * e[cc[1]] + 0.1875 * e[cc[2]] + 0.0625 * e[cc[3]]);
             }
         }
         xs[0][ly][lx] = v[0]; xs[1][ly][lx] = v[1]; xs[2][ly][lx] = v[2];
@@ -1041,7 +1061,8 @@ __global__ __launch_bounds__(NT) void k_mg_up2(MGLev L, int wc, int hc, const CG
     __syncthreads();
     double rz = 0.0;
     for (int c = threadIdx.x; c < GT_Y * GT_X; c += NT) {
-        const int ly = c / GT_X, lx = c - ly * GT_X, gy = y0 + ly, gx = x0 + lx;
+        const MGCell t = mg_cell<0>(c, x0, y0);
+        const int ly = t.ly, lx = t.lx, gy = t.gy, gx = t.gx;
         if (gx >= w || gy >= h) continue;
         const int64_t i = (int64_t)gy * w + gx;
         double a0, a1, a2, v0, v1, v2, z0, z1, z2;
@@ -1053,8 +1074,11 @@ __global__ __launch_bounds__(NT) void k_mg_up2(MGLev L, int wc, int hc, const CG
             mg_dinv_vals(L, gx, gy, Bv, D);
             mg_dinv_v(D, f[i] - a0, f[n + i] - a1, f[2 * n + i] - a2, z0, z1, z2);
         } else {
-            mg_apply_t(L, gx, gy, i, X, a0, a1, a2, v0, v1, v2);
-            mg_dinv(L, i, f[i] - a0, f[n + i] - a1, f[2 * n + i] - a2, z0, z1, z2);
+            double Bv[6], D[6];
+            mg_load6(L.B, n, i, Bv);
+            mg_apply_b(L, gx, gy, Bv, X, a0, a1, a2, v0, v1, v2);
+            mg_load6(L.Dinv, n, i, D);
+            mg_dinv_v(D, f[i] - a0, f[n + i] - a1, f[2 * n + i] - a2, z0, z1, z2);
         }
         const double f0 = f[i], f1 = f[n + i], f2v = f[2 * n + i];
         const double o0 = v0 + MG_OMEGA * z0, o1 = v1 + MG_OMEGA * z1, o2 = v2 + MG_OMEGA * z2;
@@ -1067,10 +1091,10 @@ __global__ __launch_bounds__(NT) void k_mg_up2(MGLev L, int wc, int hc, const CG
 }
 
 // coarsest level: MG_CSWEEPS damped block-Jacobi sweeps from zero in one block (x in LDS, each
-// thread's cell coefficients in registers: a sweep touches no global memory), up to MG_CPT cells
-// per thread (MG_COARSE > 1024: a coarsest level above 1024 cells, one V-cycle level less);
-// RZ (single-level hierarchy): also the partial f . x -> rz_part[0]
-constexpr int MG_CPT = (MG_COARSE + 1023) / 1024;
+// thread's cell coefficients in registers: a sweep touches no global memory), one cell per thread;
+// RZ (single-level hierarchy): also the partial f . x -> rz_part[0].  k_mg_ltail runs the same
+// sweeps on its own LDS buffers (a function shared by the two changed k_mg_ltail's generated code).
+static_assert(MG_COARSE <= 1024, "the coarsest level is one block with one cell per thread");
 template <bool RZ>
 __global__ __launch_bounds__(1024) void k_mg_coarse(MGLev L, const CGScal* S, const double* __restrict__ f,
                                                      double* __restrict__ xout, double* rz_part) {
@@ -1078,64 +1102,52 @@ __global__ __launch_bounds__(1024) void k_mg_coarse(MGLev L, const CGScal* S, co
     __shared__ double xs[2][3 * MG_COARSE];
     __shared__ double red[16];
     const int n = L.w * L.h;
-    double f0[MG_CPT], f1[MG_CPT], f2v[MG_CPT], b[MG_CPT][6], d[MG_CPT][6], c[MG_CPT];
-    int ci[MG_CPT];
-    bool in[MG_CPT], hxm[MG_CPT], hxp[MG_CPT], hym[MG_CPT], hyp[MG_CPT];
+    const int i = threadIdx.x;
+    const bool in = i < n;
+    const int y = in ? i / L.w : 0, xx = in ? i - y * L.w : 0;
+    const bool hxm = xx > 0, hxp = xx < L.w - 1, hym = y > 0, hyp = y < L.h - 1;
+    const double c = (double)mg_ncount(xx, y, L.w, L.h);
+    double f0 = 0.0, f1 = 0.0, f2v = 0.0, b[6], d[6];
+    for (int k = 0; k < 6; ++k) { b[k] = 0.0; d[k] = 0.0; }
+    if (in) {
+        f0 = f[i]; f1 = f[n + i]; f2v = f[2 * n + i];
 #pragma unroll
-    for (int q = 0; q < MG_CPT; ++q) {
-        const int i = threadIdx.x + q * (int)blockDim.x;
-        ci[q] = i;
-        in[q] = i < n;
-        const int y = in[q] ? i / L.w : 0, xx = in[q] ? i - y * L.w : 0;
-        hxm[q] = xx > 0; hxp[q] = xx < L.w - 1; hym[q] = y > 0; hyp[q] = y < L.h - 1;
-        c[q] = (double)mg_ncount(xx, y, L.w, L.h);
-        f0[q] = f1[q] = f2v[q] = 0.0;
-        for (int k = 0; k < 6; ++k) { b[q][k] = 0.0; d[q][k] = 0.0; }
-        if (in[q]) {
-            f0[q] = f[i]; f1[q] = f[n + i]; f2v[q] = f[2 * n + i];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) { b[q][k] = L.B[k * n + i]; d[q][k] = L.Dinv[k * n + i]; }
-            const double z0 = d[q][0] * f0[q] + d[q][1] * f1[q] + d[q][2] * f2v[q],
-                         z1 = d[q][1] * f0[q] + d[q][3] * f1[q] + d[q][4] * f2v[q],
-                         z2 = d[q][2] * f0[q] + d[q][4] * f1[q] + d[q][5] * f2v[q];
-            xs[0][i] = MG_OMEGA * z0; xs[0][n + i] = MG_OMEGA * z1; xs[0][2 * n + i] = MG_OMEGA * z2;
-        }
+        for (int k = 0; k < 6; ++k) { b[k] = L.B[k * n + i]; d[k] = L.Dinv[k * n + i]; }
+        double z0, z1, z2;
+        mg_dinv_v(d, f0, f1, f2v, z0, z1, z2);
+        xs[0][i] = MG_OMEGA * z0; xs[0][n + i] = MG_OMEGA * z1; xs[0][2 * n + i] = MG_OMEGA * z2;
     }
     __syncthreads();
     const double sc[3] = {L.s0, L.s1, L.s2};
     int cur = 0;
     for (int sweep = 1; sweep < MG_CSWEEPS; ++sweep) {
-#pragma unroll
-        for (int q = 0; q < MG_CPT; ++q) {
-            if (!in[q]) continue;
-            const int i = ci[q];
+        if (in) {
             const double* xc = xs[cur];
             double v[3], a[3];
 #pragma unroll
             for (int fl = 0; fl < 3; ++fl) {
                 const double* qq = xc + fl * n;
                 v[fl] = qq[i];
-                const double nb = (hxm[q] ? qq[i - 1] : 0.0) + (hxp[q] ? qq[i + 1] : 0.0) +
-                                  (hym[q] ? qq[i - L.w] : 0.0) + (hyp[q] ? qq[i + L.w] : 0.0);
-                a[fl] = sc[fl] * (c[q] * v[fl] - nb);
+                const double nb = (hxm ? qq[i - 1] : 0.0) + (hxp ? qq[i + 1] : 0.0) + (hym ? qq[i - L.w] : 0.0) +
+                                  (hyp ? qq[i + L.w] : 0.0);
+                a[fl] = sc[fl] * (c * v[fl] - nb);
             }
-            const double r0 = f0[q] - (a[0] + b[q][0] * v[0] + b[q][1] * v[1] + b[q][2] * v[2]);
-            const double r1 = f1[q] - (a[1] + b[q][1] * v[0] + b[q][3] * v[1] + b[q][4] * v[2]);
-            const double r2 = f2v[q] - (a[2] + b[q][2] * v[0] + b[q][4] * v[1] + b[q][5] * v[2]);
-            xs[cur ^ 1][i] = v[0] + MG_OMEGA * (d[q][0] * r0 + d[q][1] * r1 + d[q][2] * r2);
-            xs[cur ^ 1][n + i] = v[1] + MG_OMEGA * (d[q][1] * r0 + d[q][3] * r1 + d[q][4] * r2);
-            xs[cur ^ 1][2 * n + i] = v[2] + MG_OMEGA * (d[q][2] * r0 + d[q][4] * r1 + d[q][5] * r2);
+            const double r0 = f0 - (a[0] + b[0] * v[0] + b[1] * v[1] + b[2] * v[2]);
+            const double r1 = f1 - (a[1] + b[1] * v[0] + b[3] * v[1] + b[4] * v[2]);
+            const double r2 = f2v - (a[2] + b[2] * v[0] + b[4] * v[1] + b[5] * v[2]);
+            double z0, z1, z2;
+            mg_dinv_v(d, r0, r1, r2, z0, z1, z2);
+            xs[cur ^ 1][i] = v[0] + MG_OMEGA * z0;
+            xs[cur ^ 1][n + i] = v[1] + MG_OMEGA * z1;
+            xs[cur ^ 1][2 * n + i] = v[2] + MG_OMEGA * z2;
         }
         cur ^= 1;
         __syncthreads();
     }
     double rz = 0.0;
-#pragma unroll
-    for (int q = 0; q < MG_CPT; ++q) {
-        if (!in[q]) continue;
-        const int i = ci[q];
+    if (in) {
         xout[i] = xs[cur][i]; xout[n + i] = xs[cur][n + i]; xout[2 * n + i] = xs[cur][2 * n + i];
-        rz += f0[q] * xs[cur][i] + f1[q] * xs[cur][n + i] + f2v[q] * xs[cur][2 * n + i];
+        rz += f0 * xs[cur][i] + f1 * xs[cur][n + i] + f2v * xs[cur][2 * n + i];
     }
     if constexpr (RZ) {
         rz = wave_sum(rz);
@@ -1226,6 +1238,7 @@ __global__ __launch_bounds__(MG_LT_NTH) void k_mg_ltail(MGLev L, MGLev C, const 
     // stage 3: fc = R r (4 x 4 taps; taps outside the grid weigh 0 and read 0, as the tile's halo)
     for (int I0 = tid; I0 < nc; I0 += MG_LT_NTH) {
         const int J = I0 / wc, K = I0 - J * wc;
+        // (R's weights and sums written out, as in k_mg_down2: the header comment of this section)
         double wy[4], wx[4];
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
@@ -1254,7 +1267,8 @@ __global__ __launch_bounds__(MG_LT_NTH) void k_mg_ltail(MGLev L, MGLev C, const 
         fcL[2 * nc + I0] = 0.25 * a2;
     }
     __syncthreads();
-    // the coarsest level: k_mg_coarse<false>'s sweeps (one cell per thread: the host checks nc <= MG_LT_NTH)
+    // the coarsest level: k_mg_coarse<false>'s sweeps, written out here (one cell per thread: the
+    // host checks nc <= MG_LT_NTH)
     {
         double* xb0 = rL;
         double* xb1 = rL + 3 * nc;
@@ -1268,8 +1282,8 @@ __global__ __launch_bounds__(MG_LT_NTH) void k_mg_ltail(MGLev L, MGLev C, const 
         const double cn = (double)mg_ncount(xc, yc, wc, hc);
         if (in) {
             f0 = fcL[i]; f1 = fcL[nc + i]; f2v = fcL[2 * nc + i];
-            const double z0 = d[0] * f0 + d[1] * f1 + d[2] * f2v, z1 = d[1] * f0 + d[3] * f1 + d[4] * f2v,
-                         z2 = d[2] * f0 + d[4] * f1 + d[5] * f2v;
+            double z0, z1, z2;
+            mg_dinv_v(d, f0, f1, f2v, z0, z1, z2);
             xb0[i] = MG_OMEGA * z0; xb0[nc + i] = MG_OMEGA * z1; xb0[2 * nc + i] = MG_OMEGA * z2;
         }
         __syncthreads();
@@ -1291,6 +1305,7 @@ __global__ __launch_bounds__(MG_LT_NTH) void k_mg_ltail(MGLev L, MGLev C, const 
                 const double r0 = f0 - (a[0] + b[0] * v[0] + b[1] * v[1] + b[2] * v[2]);
                 const double r1 = f1 - (a[1] + b[1] * v[0] + b[3] * v[1] + b[4] * v[2]);
                 const double r2 = f2v - (a[2] + b[2] * v[0] + b[4] * v[1] + b[5] * v[2]);
+                // (D^-1 r written out: through mg_dinv_v this loop's generated code changed)
                 xnext[i] = v[0] + MG_OMEGA * (d[0] * r0 + d[1] * r1 + d[2] * r2);
                 xnext[nc + i] = v[1] + MG_OMEGA * (d[1] * r0 + d[3] * r1 + d[4] * r2);
                 xnext[2 * nc + i] = v[2] + MG_OMEGA * (d[2] * r0 + d[4] * r1 + d[5] * r2);
@@ -1305,15 +1320,12 @@ __global__ __launch_bounds__(MG_LT_NTH) void k_mg_ltail(MGLev L, MGLev C, const 
             const int ii = tid + q * MG_LT_NTH;
             if (ii >= n) continue;
             const int gy = ii / w, gx = ii - gy * w;
-            const int X0 = gx >> 1, Y0 = gy >> 1;
-            int X1 = (gx & 1) ? X0 + 1 : X0 - 1, Y1 = (gy & 1) ? Y0 + 1 : Y0 - 1;
-            X1 = X1 < 0 ? 0 : (X1 > wc - 1 ? wc - 1 : X1);
-            Y1 = Y1 < 0 ? 0 : (Y1 > hc - 1 ? hc - 1 : Y1);
-            const int c00 = Y0 * wc + X0, c01 = Y0 * wc + X1, c10 = Y1 * wc + X0, c11 = Y1 * wc + X1;
+            int cc[4];
+            mg_pcells(gx, gy, wc, hc, cc);
 #pragma unroll
             for (int fl = 0; fl < 3; ++fl) {
                 const double* e = ec + fl * nc;
-                xL[fl * n + ii] = xL[fl * n + ii] + (0.5625 * e[c00] + 0.1875 * e[c01] + 0.1875 * e[c10] + 0.0625 * e[c11]);
+                xL[fl * n + ii] = xL[fl * n + ii] + (0.5625 * e[cc[0]] + 0.1875 * e[cc[1]] + 0.1875 * e[cc[2]] + 0.0625 * e[cc[3]]);
             }
         }
     }
@@ -1340,95 +1352,6 @@ __global__ __launch_bounds__(MG_LT_NTH) void k_mg_ltail(MGLev L, MGLev C, const 
 // ============================================================================ GN plan (host)
 
 using namespace foto;
-
-namespace {
-
-// The host side of a solve is two copies between the caller's pageable arrays and the plan's
-// pinned staging: 5 MB in, 7.4 MB out at 640x480, 0.13 + 0.22 ms on one core against a 4.6 ms
-// solve (FOTO_GN_TRACE).  A few workers made with the staging split them; the caller takes a
-// share too.  FOTO_GN_HOST_THREADS (default 4) counts the workers; 0 copies on the caller alone.
-class HostPool {
-public:
-    explicit HostPool(int workers) {
-        for (int t = 0; t < workers; ++t) th_.emplace_back([this] { loop(); });
-    }
-    ~HostPool() {
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto& t : th_) t.join();
-    }
-    int workers() const { return (int)th_.size(); }
-    // f(i) for every i < n, on the workers and the caller; returns when all have run
-    void run(int n, const std::function<void(int)>& f) {
-        if (th_.empty() || n <= 1) {
-            for (int i = 0; i < n; ++i) f(i);
-            return;
-        }
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            job_ = &f;
-            n_ = n;
-            next_.store(0);
-            pending_ = (int)th_.size();
-            ++gen_;
-        }
-        cv_.notify_all();
-        drain();
-        std::unique_lock<std::mutex> g(mu_);
-        done_.wait(g, [this] { return pending_ == 0; });
-        job_ = nullptr;
-    }
-
-private:
-    void drain() {
-        for (int i; (i = next_.fetch_add(1)) < n_;) (*job_)(i);
-    }
-    void loop() {
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> g(mu_);
-                cv_.wait(g, [&] { return stop_ || gen_ != seen; });
-                if (stop_) return;
-                seen = gen_;
-            }
-            drain();
-            {
-                std::lock_guard<std::mutex> g(mu_);
-                --pending_;
-            }
-            done_.notify_one();
-        }
-    }
-    std::vector<std::thread> th_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_;
-    const std::function<void(int)>* job_ = nullptr;
-    int n_ = 0, pending_ = 0;
-    std::atomic<int> next_{0};
-    uint64_t gen_ = 0;
-    bool stop_ = false;
-};
-
-// memcpy in pieces of at least 256 KB over the pool
-void pool_memcpy(HostPool* pool, void* dst, const void* src, size_t bytes) {
-    const size_t piece = 256 << 10;
-    const int parts = pool ? (int)std::min<size_t>((size_t)pool->workers() + 1, (bytes + piece - 1) / piece) : 1;
-    if (parts <= 1) {
-        memcpy(dst, src, bytes);
-        return;
-    }
-    const size_t step = ((bytes + parts - 1) / parts + 4095) & ~(size_t)4095;
-    pool->run(parts, [&](int i) {
-        const size_t a = (size_t)i * step;
-        if (a < bytes) memcpy((char*)dst + a, (const char*)src + a, std::min(step, bytes - a));
-    });
-}
-
-}  // namespace
 
 struct foto_gn_plan {
     int w = 0, h = 0, maxiter = 0, device = 0;
@@ -1486,34 +1409,14 @@ namespace foto {
 // one thread per cell of the coarsest level, whole waves (fewer waves: cheaper barriers
 // between the sweeps)
 static int mg_coarse_threads(const foto_gn_plan::Lev& L) {
-    const int n = L.w * L.h;
-    const int per = (n + MG_CPT - 1) / MG_CPT;   // (MG_COARSE <= 1024: one cell per thread)
-    return std::min(1024, ((per + 63) / 64) * 64);
+    return std::min(1024, ((L.w * L.h + 63) / 64) * 64);
 }
 
-// z = V(r) and the partials of r.z -> rz_out
-// level 0's legs: B and D^-1 formed from the GN coefficients (tn.gn_recomp) or loaded
-static void mg_down0(foto_gn_plan* P, int wc, int hc, double* x, double* fc, const MGUpd& upd) {
-    const auto& L = P->lev[0];
-    if (P->tn.gn_recomp)
-        k_mg_down2<true, true><<<mg_tiles(L.w, L.h), NT, 0, P->s>>>(P->desc(0), wc, hc, P->dS, nullptr, x, fc, upd);
-    else
-        k_mg_down2<true, false><<<mg_tiles(L.w, L.h), NT, 0, P->s>>>(P->desc(0), wc, hc, P->dS, nullptr, x, fc, upd);
-}
-
-static void mg_up0(foto_gn_plan* P, int wc, int hc, const double* e, const double* r, const double* x, double* z,
-                   double* rz_out) {
-    const auto& L = P->lev[0];
-    if (P->tn.gn_recomp)
-        k_mg_up2<true, true><<<mg_tiles(L.w, L.h), NT, 0, P->s>>>(P->desc(0), wc, hc, P->dS, e, r, x, z, rz_out,
-                                                                 MGCoef{P->fx, P->fy, P->d2});
-    else
-        k_mg_up2<true, false><<<mg_tiles(L.w, L.h), NT, 0, P->s>>>(P->desc(0), wc, hc, P->dS, e, r, x, z, rz_out);
-}
-
+// z = V(r) and the partials of r.z -> rz_out.
 // Down legs of levels 0 .. b - 1, the bottom step, up legs b - 1 .. 0.  The bottom step is
 // k_mg_coarse on the coarsest level c (b = c), or with P->lt k_mg_ltail on levels c - 1 and c
-// in one block (b = c - 1); either leaves the correction e on level b.
+// in one block (b = c - 1); either leaves the correction e on level b.  Level 0's legs of a PCG
+// iteration form B and D^-1 from the GN coefficients (tn.gn_recomp) or load them.
 static int gn_vcycle(foto_gn_plan* P, const double* r, double* z, double* rz_out, const MGUpd* upd = nullptr) {
     hipStream_t s = P->s;
     const size_t nl = P->lev.size();
@@ -1528,7 +1431,8 @@ static int gn_vcycle(foto_gn_plan* P, const double* r, double* z, double* rz_out
         const auto& L = P->lev[l];
         const auto& C = P->lev[l + 1];
         if (l == 0 && upd)
-            mg_down0(P, C.w, C.h, L.x, C.f, *upd);
+            (P->tn.gn_recomp ? k_mg_down2<true, true> : k_mg_down2<true, false>)<<<mg_tiles(L.w, L.h), NT, 0, s>>>(
+                P->desc(0), C.w, C.h, P->dS, nullptr, L.x, C.f, *upd);
         else
             k_mg_down2<false><<<mg_tiles(L.w, L.h), NT, 0, s>>>(P->desc(l), C.w, C.h, P->dS, l == 0 ? r : L.f, L.x,
                                                                C.f, MGUpd{});
@@ -1551,7 +1455,8 @@ static int gn_vcycle(foto_gn_plan* P, const double* r, double* z, double* rz_out
         const auto& L = P->lev[l];
         const auto& C = P->lev[l + 1];
         if (l == 0) {
-            mg_up0(P, C.w, C.h, e, r, L.x, z, rz_out);
+            (P->tn.gn_recomp ? k_mg_up2<true, true> : k_mg_up2<true, false>)<<<mg_tiles(L.w, L.h), NT, 0, s>>>(
+                P->desc(0), C.w, C.h, P->dS, e, r, L.x, z, rz_out, MGCoef{P->fx, P->fy, P->d2});
         } else {
             k_mg_up2<false><<<mg_tiles(L.w, L.h), NT, 0, s>>>(P->desc(l), C.w, C.h, P->dS, e, L.f, L.x, L.y, nullptr);
             e = L.y;
@@ -1707,33 +1612,40 @@ struct GnDev {
     hipStream_t user;
 };
 
-static int gn_plan_solve(foto_gn_plan* P, const double* f1, const double* f2, double* u, double* v, double* m,
-                         int* iterations, const GnDev* dv = nullptr) {
+// the two frames into d1, d2: device frames, the pinned staging, or (first solve of the plan:
+// gn_staging) the caller's pageable arrays
+static int gn_upload(foto_gn_plan* P, const double* f1, const double* f2, const GnDev* dv) {
     const int w = P->w, h = P->h;
-    const int64_t n = (int64_t)w * h;
+    const size_t bytes = (size_t)w * h * sizeof(double);
     hipStream_t s = P->s;
-    GnTrace tr;
-    if (dv) FOTO_TRY(P->link.enter(dv->user, s));   // (before the first read of a frame)
-    FOTO_HIP_CHECK(hipEventRecord(P->ev[0], s));
+    double* const dst[2] = {P->d1, P->d2};
     if (dv) {
         FOTO_HIP_CHECK(launch_ingest(*dv->f1, w, h, P->d1, s));
         FOTO_HIP_CHECK(launch_ingest(*dv->f2, w, h, P->d2, s));
-    } else if (P->hbuf) {
-        double* hb = P->hbuf;
-        pool_memcpy(P->pool.get(), hb, f1, n * sizeof(double));
-        FOTO_HIP_CHECK(hipMemcpyAsync(P->d1, hb, n * sizeof(double), hipMemcpyHostToDevice, s));
-        pool_memcpy(P->pool.get(), hb + n, f2, n * sizeof(double));
-        FOTO_HIP_CHECK(hipMemcpyAsync(P->d2, hb + n, n * sizeof(double), hipMemcpyHostToDevice, s));
-    } else {   // first solve of the plan (gn_staging)
-        FOTO_HIP_CHECK(hipMemcpyAsync(P->d1, f1, n * sizeof(double), hipMemcpyHostToDevice, s));
-        FOTO_HIP_CHECK(hipMemcpyAsync(P->d2, f2, n * sizeof(double), hipMemcpyHostToDevice, s));
+        return 0;
     }
-    tr.mark("solve: upload staged");
+    const double* const src[2] = {f1, f2};
+    for (int c = 0; c < 2; ++c) {
+        const double* from = src[c];
+        if (P->hbuf) {
+            double* hb = P->hbuf + (size_t)c * w * h;
+            pool_memcpy(P->pool.get(), hb, from, bytes);
+            from = hb;
+        }
+        FOTO_HIP_CHECK(hipMemcpyAsync(dst[c], from, bytes, hipMemcpyHostToDevice, s));
+    }
+    return 0;
+}
+
+// the right-hand side and the image-dependent multigrid coefficients (B and D^-1 of every level)
+static int gn_setup(foto_gn_plan* P) {
+    const int w = P->w, h = P->h;
+    const int64_t n = (int64_t)w * h;
+    hipStream_t s = P->s;
     FOTO_HIP_CHECK(hipMemsetAsync(P->dS, 0, sizeof(CGScal), s));
     FOTO_HIP_CHECK(hipMemsetAsync(P->x, 0, 3 * n * sizeof(double), s));
     FOTO_HIP_CHECK(launch_gn_coeffs(w, h, P->d1, P->d2, P->fx, P->fy, P->ft, s));
     FOTO_HIP_CHECK(launch_gn_rhs(w, h, P->fx, P->fy, P->d2, P->ft, P->b, s));
-    // image-dependent multigrid coefficients
     if (P->tn.gn_setup_fuse) {
         k_mg_b0_d<<<flat_blocks(n), NT, 0, s>>>(P->desc(0), P->fx, P->fy, P->d2, P->lev[0].B, P->lev[0].Dinv);
         FOTO_HIP_CHECK(hipGetLastError());
@@ -1760,12 +1672,15 @@ static int gn_plan_solve(foto_gn_plan* P, const double* f1, const double* f2, do
     // r = b, r.r; z_0 = V(r), r.z -> rz_part[0]
     k_gnp_init<<<P->nb_pix, NT, 0, s>>>(n, P->b, P->r, P->rr_part);
     FOTO_HIP_CHECK(hipGetLastError());
-    FOTO_TRY(gn_vcycle(P, P->r, P->z, P->rz_part[0]));
-    FOTO_HIP_CHECK(hipEventRecord(P->ev[1], s));
-    tr.mark("solve: setup enqueued");
-    // replay the graph (G = GN_GRAPH_ITS iterations); the first wait comes after the previous solve's
-    // count: the top-of-iteration test that ends a solve of `its` iterations runs in iteration
-    // its, so its + 1 iterations are launched (rounded up to whole graphs)
+    return gn_vcycle(P, P->r, P->z, P->rz_part[0]);
+}
+
+// The PCG iterations: replay the graph (G = GN_GRAPH_ITS iterations) and poll the done flag.  The
+// first wait comes after the previous solve's count: the top-of-iteration test that ends a solve of
+// `its` iterations runs in iteration its, so its + 1 iterations are launched (rounded up to whole
+// graphs).  *launched = iterations enqueued; *done = the stop test fired (P->hS->iters holds the count).
+static int gn_run_pcg(foto_gn_plan* P, bool staging, int* launched, bool* done_out) {
+    hipStream_t s = P->s;
     int k = 0;
     bool done = false;
     const int maxiter = P->maxiter;
@@ -1785,44 +1700,76 @@ static int gn_plan_solve(foto_gn_plan* P, const double* f1, const double* f2, do
         for (; j + G <= chunk; j += G, k += G) FOTO_HIP_CHECK(hipGraphLaunch(P->gexec, s));
         for (; j < chunk; ++j, ++k) FOTO_TRY(gn_iteration(P, k & 1));   // (the remainder, outside the graph)
         FOTO_HIP_CHECK(hipMemcpyAsync(P->hS, P->dS, sizeof(CGScal), hipMemcpyDeviceToHost, s));
-        if (k == chunk && !dv) FOTO_TRY(gn_staging(P));   // while the first iterations run
+        if (k == chunk && staging) FOTO_TRY(gn_staging(P));   // while the first iterations run
         FOTO_HIP_CHECK(hipStreamSynchronize(s));
         if (P->hS->done) { done = true; break; }
     }
-    FOTO_HIP_CHECK(hipEventRecord(P->ev[2], s));
-    tr.mark("solve: PCG done");
-    // the solution straight into the mapped pinned staging by a kernel: the first large
-    // device-to-host hipMemcpy of a process took 8.5-14.8 ms at 640x480 (0.15-0.4 ms later)
+    *launched = k;
+    *done_out = done;
+    return 0;
+}
+
+// The solution to the caller.  Device target: one export kernel.  Host arrays: straight into the
+// mapped pinned staging by a kernel (the first large device-to-host hipMemcpy of a process took
+// 8.5-14.8 ms at 640x480, 0.15-0.4 ms later), u, v, m one after the other, each copied out by the
+// pool while the next crosses PCIe.
+static int gn_download(foto_gn_plan* P, double* u, double* v, double* m, const GnDev* dv, GnTrace& tr) {
+    const int64_t n = (int64_t)P->w * P->h;
+    hipStream_t s = P->s;
     if (dv) {
         FOTO_HIP_CHECK(launch_export(n, P->x, P->x + n, P->x + 2 * n, dv->out, dv->dtype, dv->layout, s));
-        FOTO_TRY(P->link.leave(s, dv->user));
-    } else {
-        FOTO_TRY(gn_staging(P));   // (maxiter 0: no iteration ran)
-        // u, v, m one after the other, each copied out while the next crosses PCIe
-        double* const outs[3] = {u, v, m};
-        for (int c = 0; c < 3; ++c) {
-            k_gn_download<<<flat_blocks(n), NT, 0, s>>>(n, P->x + c * n, P->hbuf_dev + (2 + c) * n);
-            FOTO_HIP_CHECK(hipGetLastError());
-            FOTO_HIP_CHECK(hipEventRecord(P->dl_ev[c], s));
-        }
-        for (int c = 0; c < 3; ++c) {
-            FOTO_HIP_CHECK(hipEventSynchronize(P->dl_ev[c]));
-            if (c == 0) tr.mark("solve: download u");
-            pool_memcpy(P->pool.get(), outs[c], P->hbuf + (2 + c) * n, n * sizeof(double));
-        }
+        return P->link.leave(s, dv->user);
     }
-    tr.mark("solve: copy out");
-    const int its = done ? P->hS->iters : maxiter;
+    FOTO_TRY(gn_staging(P));   // (maxiter 0: no iteration ran)
+    double* const outs[3] = {u, v, m};
+    for (int c = 0; c < 3; ++c) {
+        k_gn_download<<<flat_blocks(n), NT, 0, s>>>(n, P->x + c * n, P->hbuf_dev + (2 + c) * n);
+        FOTO_HIP_CHECK(hipGetLastError());
+        FOTO_HIP_CHECK(hipEventRecord(P->dl_ev[c], s));
+    }
+    for (int c = 0; c < 3; ++c) {
+        FOTO_HIP_CHECK(hipEventSynchronize(P->dl_ev[c]));
+        if (c == 0) tr.mark("solve: download u");
+        pool_memcpy(P->pool.get(), outs[c], P->hbuf + (2 + c) * n, n * sizeof(double));
+    }
+    return 0;
+}
+
+// ms of setup + upload and of the PCG from the plan's events, and the counts, into P->last
+static int gn_timing(foto_gn_plan* P, int its, int launched, bool wait) {
     float t0 = 0.f, t1 = 0.f;
     // (device path: nothing waited after ev[2] was recorded -- the host path's download events do --
     // and an elapsed time of an event still pending is hipErrorNotReady)
-    if (dv) FOTO_HIP_CHECK(hipEventSynchronize(P->ev[2]));
+    if (wait) FOTO_HIP_CHECK(hipEventSynchronize(P->ev[2]));
     FOTO_HIP_CHECK(hipEventElapsedTime(&t0, P->ev[0], P->ev[1]));
     FOTO_HIP_CHECK(hipEventElapsedTime(&t1, P->ev[1], P->ev[2]));
-    P->last[0] = t0; P->last[1] = t1; P->last[2] = its; P->last[3] = k;
+    P->last[0] = t0; P->last[1] = t1; P->last[2] = its; P->last[3] = launched;
+    return 0;
+}
+
+static int gn_plan_solve(foto_gn_plan* P, const double* f1, const double* f2, double* u, double* v, double* m,
+                         int* iterations, const GnDev* dv = nullptr) {
+    hipStream_t s = P->s;
+    GnTrace tr;
+    if (dv) FOTO_TRY(P->link.enter(dv->user, s));   // (before the first read of a frame)
+    FOTO_HIP_CHECK(hipEventRecord(P->ev[0], s));
+    FOTO_TRY(gn_upload(P, f1, f2, dv));
+    tr.mark("solve: upload staged");
+    FOTO_TRY(gn_setup(P));
+    FOTO_HIP_CHECK(hipEventRecord(P->ev[1], s));
+    tr.mark("solve: setup enqueued");
+    int launched = 0;
+    bool done = false;
+    FOTO_TRY(gn_run_pcg(P, !dv, &launched, &done));
+    FOTO_HIP_CHECK(hipEventRecord(P->ev[2], s));
+    tr.mark("solve: PCG done");
+    FOTO_TRY(gn_download(P, u, v, m, dv, tr));
+    tr.mark("solve: copy out");
+    const int its = done ? P->hS->iters : P->maxiter;
+    FOTO_TRY(gn_timing(P, its, launched, dv != nullptr));
     P->last_its = done ? its : 0;
     if (iterations) *iterations = its;
-    return done ? 0 : maxiter;
+    return done ? 0 : P->maxiter;
 }
 
 }  // namespace foto

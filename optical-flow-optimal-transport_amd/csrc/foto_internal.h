@@ -295,16 +295,10 @@ hipError_t launch_gn_rhs(int w, int h, const double* fx, const double* fy, const
                          double* b, hipStream_t s);
 hipError_t launch_gn_apply(int w, int h, const double* fx, const double* fy, const double* f2, double alpha,
                            double lam, const double* x, double* y, hipStream_t s);
-hipError_t launch_gn_pcg_init(int w, int h, const double* fx, const double* fy, const double* f2, double alpha,
-                              double lam, const double* b, double* r, double* z, RedBuf rb, double* gath,
-                              hipStream_t s);
-hipError_t launch_gn_pcg_dir(int w, int h, int k, const double* fx, const double* fy, const double* f2,
-                             double alpha, double lam, const double* z, const double* pold, double* pnew,
-                             CGScal* S, RedBuf rb, const double* gath_rz, double* gath_pq, double rtol,
-                             hipStream_t s);
-hipError_t launch_gn_pcg_upd(int w, int h, int k, const double* fx, const double* fy, const double* f2,
-                             double alpha, double lam, const double* p, double* x, double* r, double* z,
-                             CGScal* S, RedBuf rb, const double* gath_pq, double* gath_rz, hipStream_t s);
+// FOTO_GN_MG=0: the first-generation solver, CG with the 3x3 block-Jacobi preconditioner, from the
+// caller's host frames to the host flow; returns 0 (converged) or maxiter, *iterations as run
+int gn_bj_solve(const double* f1, const double* f2, int w, int h, double alpha, double lam, double rtol, int maxiter,
+                double* u, double* v, double* m, int* iterations);
 
 // ----------------------------------------------------------------------------- device buffers
 // (foto_dev.hip; the *_dev entries of include/foto.h)

@@ -641,7 +641,7 @@ def test_gn_solve(gold):
             np.testing.assert_allclose(a, b, rtol=0, atol=1e-7)
 
 
-@pytest.mark.parametrize("w,h", [(2, 2), (2, 9), (11, 2), (3, 5), (33, 17), (1100, 3), (5, 640)])
+@pytest.mark.parametrize("w,h", [(2, 2), (2, 9), (11, 2), (3, 5), (33, 17), (1100, 3), (5, 640), (71, 77)])
 def test_gn_edge_grids_vs_oracle(w, h):
     """GN on edge grids -- the minimum 2x2, one axis of 2 or 3, odd and prime sizes, strips whose
     hierarchy coarsens one axis down to a single cell (1100x3, 5x640) -- against the oracle's
@@ -676,7 +676,7 @@ def test_gn_solve_multilevel(pair, monkeypatch):
             np.testing.assert_allclose(a, b, rtol=0, atol=1e-6 * max(1.0, np.abs(b).max()))
 
 
-@pytest.mark.parametrize("w,h", [(640, 480), (584, 388), (320, 240), (160, 120), (2, 3000), (3001, 3)])
+@pytest.mark.parametrize("w,h", [(640, 480), (584, 388), (320, 240), (160, 120), (2, 3000), (3001, 3), (71, 77)])
 def test_gn_round5_forms_bit_identical(w, h, monkeypatch):
     """Round 5's GN launch structures -- the PCG update folded into the level-0 down leg and the
     last level above the coarsest solved with it in one LDS-resident block (k_mg_ltail; both

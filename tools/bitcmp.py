@@ -51,4 +51,20 @@ for mg in ("1", "0"):
     gu, gv, gm, info, its = gn.solve(f1, f2, Nx, Ny, 0.1, 0.2)
     out.update({f"gn_mg{mg}_u": gu, f"gn_mg{mg}_v": gv, f"gn_mg{mg}_m": gm, f"gn_mg{mg}_its": np.array([info, its])})
 os.environ.pop("FOTO_GN_MG")
+# GN, every launch structure: the three forms of test_gn_round5_forms_bit_identical and the
+# block-Jacobi PCG, at the bench size and at 71x77 (three levels with odd extents, k_mg_ltail
+# directly under the level-0 legs); a plan per call, as that test
+FORMS = {"sep": dict(FOTO_GN_SETUP_FUSE="0", FOTO_GN_RECOMP="0", FOTO_GN_FOLD="0", FOTO_MG_LTAIL="0"),
+         "fold": dict(FOTO_GN_SETUP_FUSE="1", FOTO_GN_RECOMP="1", FOTO_GN_FOLD="1", FOTO_MG_LTAIL="0"),
+         "ltail": dict(FOTO_GN_SETUP_FUSE="1", FOTO_GN_RECOMP="1", FOTO_GN_FOLD="1", FOTO_MG_LTAIL="1"),
+         "bj": dict(FOTO_GN_MG="0")}
+for w, h in ((640, 480), (71, 77)):
+    f1, f2 = sinusoid_pair(w, h)
+    for key, env in FORMS.items():
+        env = dict(env, FOTO_GN_PLAN_CACHE="0")
+        os.environ.update(env)
+        gu, gv, gm, info, its = gn.solve(f1, f2, w, h, 0.1, 0.2)
+        for k in env:
+            os.environ.pop(k)
+        out.update({f"gn_{w}x{h}_{key}_uvm": np.stack([gu, gv, gm]), f"gn_{w}x{h}_{key}_its": np.array([info, its])})
 np.savez(sys.argv[2], **out)
