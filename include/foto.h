@@ -476,6 +476,90 @@ int foto_report_from_state(const double* mu3, const double* phi, const double* r
 int foto_gn_plan_solve_dev(foto_gn_plan* p, const foto_image* f1, const foto_image* f2, void* out, int dtype,
                            int layout, void* stream, int* iterations);
 
+/* ------------------------------------------------------------------ coarse-to-fine GN
+ * The GN brightness equation fx u + fy v + ft - f2 m = 0 is a linearisation: it holds for
+ * displacements of about a pixel and returns too short a flow for larger ones.  The pyramid
+ * solves on an image pyramid and, per level, warps the second frame by the flow found so far and
+ * re-solves for the increment, regularising the TOTAL flow (DESIGN.md has the algorithm):
+ *   level sizes   (w_0, h_0) = (w, h); level l + 1 exists while l + 1 < levels and
+ *                 min(w_l, h_l) >= 2 min_size, with w_{l+1} = ceil(w_l / 2), h likewise;
+ *   restrict      c[j][i] = 0.25 (((f[J0][I0] + f[J0][I1]) + f[J1][I0]) + f[J1][I1]), I0 = 2 i,
+ *                 I1 = min(2 i + 1, w - 1), J likewise;
+ *   sample        S(f; x, y): bilinear, x clamped to [0, w - 1], i0 = min(floor(x), w - 2); a NaN
+ *                 coordinate gives NaN, read from in-frame taps (foto_warp's rule);
+ *   prolong       P(c)[j][i] = S(c; (i + 1/2) wc / w - 1/2, (j + 1/2) hc / h - 1/2), then
+ *                 u <- (w / wc) P(u), v <- (h / hc) P(v), m <- P(m);
+ *   warp          g[j][i] = (1 - m[j][i]) S(f2_l; i + u[j][i], j + v[j][i]);
+ *   increment     A(f1_l, g) d = b(f1_l, g) - [alpha N u; alpha N v; lambda N m] with A, b of
+ *                 foto_gn_apply / foto_gn_rhs and N = -Lambda2 the operator's Laplacian part; then
+ *                 (u, v, m) += d;
+ *   loop          coarsest level to level 0, `warps` increment solves per level; the very first
+ *                 solve has no prior (g = f2_l, b untouched), so levels = 1, warps = 1 is
+ *                 foto_gn_plan_solve, bit for bit.
+ * The flow is the reference's: f1(x) ~ (1 - m) f2(x + u); that foto_warp / foto_render_warp_dev
+ * draw it as ((1 + m) f1)(x - u) ~ f2 is a first-order identification.                        */
+#define FOTO_GN_PYR_MAX_LEVELS 16
+/* Host only (no HIP call): the level sizes, finest first, into wl / hl (cap entries each) and
+ * their count into *n.  FOTO_ERR_ARG: a null pointer, w or h < 2, levels < 1, min_size < 2,
+ * cap smaller than the count.                                                              */
+int foto_gn_pyr_sizes(int w, int h, int levels, int min_size, int* wl, int* hl, int cap, int* n);
+
+typedef struct {
+    int levels;      /* levels asked for (the sizes rule may build fewer)            default 4 */
+    int warps;       /* increment solves per level                                   default 3 */
+    int min_size;    /* a level is halved only while both extents are >= 2 min_size  default 16 */
+    double rtol;     /* every solve's PCG relative residual                      default 1e-10 */
+    int maxiter;     /* every solve's PCG cap                                   default 200000 */
+} foto_gn_pyr_opts;
+int foto_gn_pyr_opts_default(foto_gn_pyr_opts* o);
+
+/* Report of one pyramid solve.  The caller sizes its / info (cap entries each, either may be
+ * NULL); solves are listed in the order run, coarsest level first.                          */
+typedef struct {
+    int cap;                  /* in: entries of its / info                                    */
+    int* its;                 /* per solve: PCG iterations                                    */
+    int* info;                /* per solve: 0 converged, maxiter otherwise                    */
+    int levels;               /* levels built                                                 */
+    int solves;               /* solves run = levels * warps                                  */
+    int wl[FOTO_GN_PYR_MAX_LEVELS], hl[FOTO_GN_PYR_MAX_LEVELS];   /* level sizes, finest first */
+    double ms_level[FOTO_GN_PYR_MAX_LEVELS];   /* device time per level (index = level; the
+                                 coarsest level's includes the ingest and the restrictions)   */
+    double ms_new;            /* device time of the pyramid's own steps between the solves: the
+                                 restrictions, prolongations, warps and flow copies (event pairs
+                                 around them); the prior term and the add-back run inside a solve */
+    double ms_total;          /* host wall time of the call                                   */
+} foto_gn_pyr_stats;
+
+/* One plan per level on one stream, the level images and the flow buffers, made once.
+ * FOTO_ERR_ARG (nothing made, nothing enqueued): a null pointer, w or h < 2, alpha or lambda
+ * <= 0, levels < 1, warps < 1, min_size < 2, maxiter < 0.  opts NULL: the defaults.          */
+typedef struct foto_gn_pyr foto_gn_pyr;
+int foto_gn_pyr_create(int w, int h, double alpha, double lambda_, const foto_gn_pyr_opts* opts, foto_gn_pyr** out);
+void foto_gn_pyr_destroy(foto_gn_pyr* p);
+int foto_gn_pyr_device(const foto_gn_pyr* p);
+/* Host float64 frames in, u, v, m out (w * h each).  Returns 0, or the number of solves that hit
+ * maxiter, < 0 on error.  stats may be NULL.                                                */
+int foto_gn_pyr_solve(foto_gn_pyr* p, const double* f1, const double* f2, double* u, double* v, double* m,
+                      foto_gn_pyr_stats* stats);
+/* The same on device frames, exported like foto_gn_plan_solve_dev (same checks, same stream
+ * contract): `out` is a buffer foto_flow describes.  With stats the call waits for the last
+ * level's event to read the times.                                                          */
+int foto_gn_pyr_solve_dev(foto_gn_pyr* p, const foto_image* f1, const foto_image* f2, void* out, int dtype,
+                          int layout, void* stream, foto_gn_pyr_stats* stats);
+
+/* The pyramid's pieces on host arrays (tests).  foto_pyr_down: both frames of a w x h level to
+ * ceil(w/2) x ceil(h/2) in one launch (w, h >= 1).  foto_pyr_up: u, v, m from wc x hc to w x h
+ * with the scales above (all extents >= 2).  foto_gn_warp_prior: g from f2 and a prior (w, h >=
+ * 2).  foto_gn_solve_prior: one increment solve of A(f1, g) with the prior (u0, v0, m0) -- all
+ * three NULL: no prior, foto_gn_plan_solve -- returning the total flow; 0 or maxiter.        */
+int foto_pyr_down(const double* f1, const double* f2, int w, int h, double* c1, double* c2);
+int foto_pyr_up(const double* u, const double* v, const double* m, int wc, int hc, int w, int h, double* uo,
+                double* vo, double* mo);
+int foto_gn_warp_prior(const double* f2, const double* u, const double* v, const double* m, int w, int h, double* g);
+int foto_gn_solve_prior(const double* f1, const double* g, int w, int h, double alpha, double lambda_, double rtol,
+                        int maxiter, const double* u0, const double* v0, const double* m0, double* u, double* v,
+                        double* m, int* iterations);
+
 /* foto_warp / foto_flow_errors / foto_intensity_error (utils.py:186-248, 294-354) on contiguous
  * float64 DEVICE arrays of w * h elements: the same kernels and reduction order without the
  * uploads.  `out` of the warp is a device array (not aliasing an input); the metrics return

@@ -32,6 +32,13 @@ class GLLOpticalFlow(object):
     def setLambda(self, lambdap):
         self.lambdap = lambdap
 
+    def setPyramid(self, levels, warps):
+        """Extension (not in the reference): process() runs coarse-to-fine over ``levels`` pyramid
+        levels with ``warps`` warped increment solves per level (foto.gn.Pyramid), for
+        displacements beyond the pixel or so the linearised model holds for.  (1, 1), and never
+        calling this, is the reference's single solve."""
+        self.pyramid = (int(levels), int(warps))
+
     def assemble(self, f1, f2):
         """Stores the frames (the system is applied matrix-free on the GPU).  Like the
         reference, requires setLambda first (AttributeError otherwise)."""
@@ -81,6 +88,14 @@ class GLLOpticalFlow(object):
         the replayed PCG graph) comes from a process-wide cache keyed by (w, h, alpha, lambda,
         rtol, maxiter) (foto.gn.cached_plan), so every instance with the same size and
         parameters -- a batch of frames -- shares one."""
+        if getattr(self, "pyramid", (1, 1)) != (1, 1):
+            pyr = _gn.cached_pyramid(self.w, self.h, self.alpha, self.lambdap, levels=self.pyramid[0],
+                                     warps=self.pyramid[1], rtol=self.rtol, maxiter=self.maxiter)
+            u, v, m, info, st = pyr.solve(self.f1, self.f2)
+            self.iterations = sum(st["iterations"])
+            if info > 0:
+                print(f"WARNING: GN PCG did not converge in {info} of {st['solves']} pyramid solves.", file=sys.stderr)
+            return [u, v, m]
         plan = _gn.cached_plan(self.w, self.h, self.alpha, self.lambdap, self.rtol, self.maxiter)
         u, v, m, info, its = plan.solve(self.f1, self.f2)
         self.iterations = its

@@ -15,6 +15,7 @@
 #include <memory>
 #include <vector>
 
+#include "foto_gn.h"
 #include "foto_hostpool.h"
 #include "foto_internal.h"
 #include "foto_reduce.h"
@@ -77,52 +78,7 @@ hipError_t launch_gn_rhs(int w, int h, const double* fx, const double* fy, const
 
 // ----------------------------------------------------------------------------- operator
 
-struct GNPix {
-    int x, y;
-    bool hy, hx, hX, hY;
-    double c;   // neighbour count = diagonal of G^T G
-};
-
-__device__ __forceinline__ GNPix gn_pix(int w, int h, int64_t i) {
-    GNPix P;
-    // 32-bit division (w h < 2^31): the 64-bit one is a long software sequence per pixel
-    P.y = (int)((unsigned)i / (unsigned)w);
-    P.x = (int)i - P.y * w;
-    P.hy = P.y > 0; P.hY = P.y < h - 1; P.hx = P.x > 0; P.hX = P.x < w - 1;
-    P.c = (double)((int)P.hy + (int)P.hY + (int)P.hx + (int)P.hX);
-    return P;
-}
-
-// The five stencil indices of pixel i in CSR order: (y-1), (x-1), centre, (x+1), (y+1).  A missing
-// neighbour is fetched at the centre's index (clamped) and skipped by a select in gn_lap_row:
-// with the fetches behind branches every neighbour was its own memory round trip (~25 us per
-// PCG kernel at 640x480).
-__device__ __forceinline__ void gn_idx5(const GNPix& P, int w, int64_t i, int64_t (&j)[5]) {
-    j[0] = P.hy ? i - w : i; j[1] = P.hx ? i - 1 : i; j[2] = i; j[3] = P.hX ? i + 1 : i; j[4] = P.hY ? i + w : i;
-}
-
-// v[f][k] = val(f, j_k): the stencil values of all three fields at pixel i
-template <class F>
-__device__ __forceinline__ void gn_gather5(const GNPix& P, int w, int64_t i, F val, double (&v)[3][5]) {
-    int64_t j[5];
-    gn_idx5(P, w, i, j);
-#pragma unroll
-    for (int f = 0; f < 3; ++f)
-#pragma unroll
-        for (int k = 0; k < 5; ++k) v[f][k] = val(f, j[k]);
-}
-
-// one field's Laplacian block row in CSR order over its five fetched values val(k)
-template <class F>
-__device__ __forceinline__ double gn_lap_row(const GNPix& P, double coef, double dg, F val, double s) {
-    const double m = -coef;
-    s = P.hy ? s + m * val(0) : s;
-    s = P.hx ? s + m * val(1) : s;
-    s += dg * val(2);
-    s = P.hX ? s + m * val(3) : s;
-    s = P.hY ? s + m * val(4) : s;
-    return s;
-}
+// GNPix, gn_pix, gn_idx5, gn_gather5, gn_lap_row: foto_gn.h (shared with foto_gn_pyr.hip)
 
 // (A z)_i for all three fields; val(f, k) = the k-th stencil value (gn_idx5's order) of field f
 // of the vector being multiplied
@@ -1357,6 +1313,7 @@ struct foto_gn_plan {
     int w = 0, h = 0, maxiter = 0, device = 0;
     double alpha = 0, lam = 0, rtol = 0;
     hipStream_t s = nullptr;
+    bool own_s = true;               // false: the pyramid's stream (gn_plan_make), not released here
     double* base = nullptr;
     double *d1 = nullptr, *d2 = nullptr, *fx = nullptr, *fy = nullptr, *ft = nullptr, *b = nullptr, *x = nullptr,
            *r = nullptr, *z = nullptr, *p0 = nullptr, *p1 = nullptr;
@@ -1400,7 +1357,7 @@ struct foto_gn_plan {
         if (base) (void)hipFree(base);
         if (hS) (void)hipHostFree(hS);
         if (hbuf) (void)hipHostFree(hbuf);
-        stream_release(s);
+        if (own_s) stream_release(s);
     }
 };
 
@@ -1512,7 +1469,7 @@ static int gn_plan_init(foto_gn_plan* P) {
     const size_t n = (size_t)w * h;
     GnTrace tr;
     FOTO_HIP_CHECK(hipGetDevice(&P->device));
-    FOTO_TRY(stream_acquire(&P->s));   // (pooled: a new stream cost ~10 ms)
+    if (P->own_s) FOTO_TRY(stream_acquire(&P->s));   // (pooled: a new stream cost ~10 ms)
     tr.mark("stream");
     for (auto& e : P->ev) FOTO_HIP_CHECK(hipEventCreate(&e));
     for (auto& e : P->dl_ev) FOTO_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1637,8 +1594,9 @@ static int gn_upload(foto_gn_plan* P, const double* f1, const double* f2, const 
     return 0;
 }
 
-// the right-hand side and the image-dependent multigrid coefficients (B and D^-1 of every level)
-static int gn_setup(foto_gn_plan* P) {
+// the right-hand side and the image-dependent multigrid coefficients (B and D^-1 of every level);
+// x0 (the pyramid's increment solve): the prior's smoothness term leaves the right-hand side
+static int gn_setup(foto_gn_plan* P, const double* x0 = nullptr) {
     const int w = P->w, h = P->h;
     const int64_t n = (int64_t)w * h;
     hipStream_t s = P->s;
@@ -1646,6 +1604,7 @@ static int gn_setup(foto_gn_plan* P) {
     FOTO_HIP_CHECK(hipMemsetAsync(P->x, 0, 3 * n * sizeof(double), s));
     FOTO_HIP_CHECK(launch_gn_coeffs(w, h, P->d1, P->d2, P->fx, P->fy, P->ft, s));
     FOTO_HIP_CHECK(launch_gn_rhs(w, h, P->fx, P->fy, P->d2, P->ft, P->b, s));
+    if (x0) FOTO_HIP_CHECK(launch_gn_rhs_prior(w, h, P->alpha, P->lam, x0, P->b, s));
     if (P->tn.gn_setup_fuse) {
         k_mg_b0_d<<<flat_blocks(n), NT, 0, s>>>(P->desc(0), P->fx, P->fy, P->d2, P->lev[0].B, P->lev[0].Dinv);
         FOTO_HIP_CHECK(hipGetLastError());
@@ -1772,6 +1731,34 @@ static int gn_plan_solve(foto_gn_plan* P, const double* f1, const double* f2, do
     return done ? 0 : P->maxiter;
 }
 
+GnBufs gn_plan_bufs(foto_gn_plan* P) { return GnBufs{P->w, P->h, P->device, P->s, P->d1, P->d2, P->x}; }
+
+int gn_plan_solve_prior(foto_gn_plan* P, const double* x0, int* iterations, bool* done_out) {
+    // (no events: the pyramid times its levels itself, and nothing here waits after the PCG)
+    FOTO_TRY(gn_setup(P, x0));
+    int launched = 0;
+    bool done = false;
+    FOTO_TRY(gn_run_pcg(P, false, &launched, &done));
+    if (x0) FOTO_HIP_CHECK(launch_gn_add(3 * (int64_t)P->w * P->h, P->x, x0, P->s));
+    const int its = done ? P->hS->iters : P->maxiter;
+    P->last[0] = P->last[1] = 0.0; P->last[2] = its; P->last[3] = launched;
+    P->last_its = done ? its : 0;
+    *iterations = its;
+    *done_out = done;
+    return 0;
+}
+
+int gn_plan_make(int w, int h, double alpha, double lam, double rtol, int maxiter, hipStream_t shared,
+                 foto_gn_plan** out) {
+    auto P = std::make_unique<foto_gn_plan>();
+    P->w = w; P->h = h; P->alpha = alpha; P->lam = lam; P->rtol = rtol; P->maxiter = maxiter;
+    if (shared) { P->s = shared; P->own_s = false; }
+    P->tn = tuning_from_env();   // read here, once: fixed for the plan's life
+    FOTO_TRY(gn_plan_init(P.get()));
+    *out = P.release();
+    return 0;
+}
+
 }  // namespace foto
 
 extern "C" {
@@ -1784,12 +1771,7 @@ int foto_gn_plan_create(int w, int h, double alpha, double lambda_, double rtol,
         return FOTO_ERR_ARG;
     }
     if (maxiter < 0) { set_error("maxiter < 0"); return FOTO_ERR_ARG; }
-    auto P = std::make_unique<foto_gn_plan>();
-    P->w = w; P->h = h; P->alpha = alpha; P->lam = lambda_; P->rtol = rtol; P->maxiter = maxiter;
-    P->tn = tuning_from_env();   // read here, once: fixed for the plan's life
-    FOTO_TRY(gn_plan_init(P.get()));
-    *out = P.release();
-    return 0;
+    return gn_plan_make(w, h, alpha, lambda_, rtol, maxiter, nullptr, out);
 }
 
 int foto_gn_plan_solve(foto_gn_plan* p, const double* f1, const double* f2, double* u, double* v, double* m,

@@ -92,6 +92,36 @@ class GNStats(ctypes.Structure):
     ]
 
 
+GN_PYR_MAX_LEVELS = 16
+
+
+class GNPyrOpts(ctypes.Structure):
+    """foto_gn_pyr_opts (include/foto.h)."""
+    _fields_ = [
+        ("levels", ctypes.c_int),
+        ("warps", ctypes.c_int),
+        ("min_size", ctypes.c_int),
+        ("rtol", ctypes.c_double),
+        ("maxiter", ctypes.c_int),
+    ]
+
+
+class GNPyrStats(ctypes.Structure):
+    """foto_gn_pyr_stats (include/foto.h): the caller sizes its / info by cap."""
+    _fields_ = [
+        ("cap", ctypes.c_int),
+        ("its", ctypes.POINTER(ctypes.c_int)),
+        ("info", ctypes.POINTER(ctypes.c_int)),
+        ("levels", ctypes.c_int),
+        ("solves", ctypes.c_int),
+        ("wl", ctypes.c_int * GN_PYR_MAX_LEVELS),
+        ("hl", ctypes.c_int * GN_PYR_MAX_LEVELS),
+        ("ms_level", ctypes.c_double * GN_PYR_MAX_LEVELS),
+        ("ms_new", ctypes.c_double),
+        ("ms_total", ctypes.c_double),
+    ]
+
+
 FOTO_U8, FOTO_F32, FOTO_F64 = 0, 1, 2
 
 
@@ -195,6 +225,19 @@ SIGNATURES = {
     "foto_report_from_state": (_I, [_D, _D, _D, _D, _I, _I, _I, _D]),
     "foto_gn_plan_solve_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _P, _I, _I, _P,
                                     ctypes.POINTER(_I)]),
+    # coarse-to-fine GN: pyramid, warping, increment solves
+    "foto_gn_pyr_sizes": (_I, [_I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(_I)]),
+    "foto_gn_pyr_opts_default": (_I, [ctypes.POINTER(GNPyrOpts)]),
+    "foto_gn_pyr_create": (_I, [_I, _I, _Dbl, _Dbl, ctypes.POINTER(GNPyrOpts), ctypes.POINTER(_P)]),
+    "foto_gn_pyr_destroy": (None, [_P]),
+    "foto_gn_pyr_device": (_I, [_P]),
+    "foto_gn_pyr_solve": (_I, [_P, _D, _D, _D, _D, _D, ctypes.POINTER(GNPyrStats)]),
+    "foto_gn_pyr_solve_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _P, _I, _I, _P,
+                                   ctypes.POINTER(GNPyrStats)]),
+    "foto_pyr_down": (_I, [_D, _D, _I, _I, _D, _D]),
+    "foto_pyr_up": (_I, [_D, _D, _D, _I, _I, _I, _I, _D, _D, _D]),
+    "foto_gn_warp_prior": (_I, [_D, _D, _D, _D, _I, _I, _D]),
+    "foto_gn_solve_prior": (_I, [_D, _D, _I, _I, _Dbl, _Dbl, _Dbl, _I, _D, _D, _D, _D, _D, _D, ctypes.POINTER(_I)]),
     "foto_warp_dev": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "foto_flow_errors_dev": (_I, [_P, _P, _P, _P, _I, _I, _D, _P]),
     "foto_intensity_error_dev": (_I, [_P, _P, _I, _I, _D, _P]),

@@ -488,11 +488,15 @@ def bb_report(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=1
                       lambda s, st: s.report())
 
 
-def gn_flow(f0, f1, alpha, lam, *, dtype="float32", layout="planar", out=None, stream=None):
+def gn_flow(f0, f1, alpha, lam, *, dtype="float32", layout="planar", out=None, stream=None, levels=1, warps=1):
     """classical.GLLOpticalFlow.process on device frames (the plan from foto.gn's cache); returns
-    the DeviceArray (or ``out``) holding u, v, m."""
+    the DeviceArray (or ``out``) holding u, v, m.  levels / warps other than (1, 1): the
+    coarse-to-fine scheme for displacements beyond a pixel (foto.gn.Pyramid, cached likewise)."""
     from . import gn
     a, b = _pair(f0, f1)
     h, w = a.shape
+    if (int(levels), int(warps)) != (1, 1):
+        p = gn.cached_pyramid(w, h, alpha, lam, levels=levels, warps=warps)
+        return p.solve_device(a, b, out=out, dtype=dtype, layout=layout, stream=stream_handle(stream, f0, f1))[0]
     p = gn.cached_plan(w, h, alpha, lam)
     return p.solve_device(a, b, out=out, dtype=dtype, layout=layout, stream=stream_handle(stream, f0, f1))[0]

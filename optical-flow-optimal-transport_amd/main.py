@@ -42,6 +42,8 @@ def build_parser():
     # additions
     p.add_argument("--device", type=int, default=-1, help="HIP device ordinal (default: current)")
     p.add_argument("--cg-mode", type=int, default=None, help="0 stencil, 1 spectral, 2 spectral s-step, 3 Gauss-compressed spectral CG (default)")
+    p.add_argument("--gn-levels", type=int, default=1, help="GN: pyramid levels (1: the reference's single solve)")
+    p.add_argument("--gn-warps", type=int, default=1, help="GN: warped increment solves per pyramid level")
     return p
 
 
@@ -97,6 +99,9 @@ def main(argv=None, writer=None):
         gn = classical.GLLOpticalFlow(w, h)
         gn.setAlpha(args.alpha)
         gn.setLambda(args.lambdaa)
+        if (args.gn_levels, args.gn_warps) != (1, 1):
+            print(f"\t - pyramid: {args.gn_levels} levels x {args.gn_warps} warps")
+            gn.setPyramid(args.gn_levels, args.gn_warps)
         [u, v, m] = gn.assemble(rho1, rho2).process()
     else:
         # reference: `assert("not implemented")` (always true), then NameError on `u` below
