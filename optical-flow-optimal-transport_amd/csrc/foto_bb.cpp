@@ -11,70 +11,17 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstddef>
 #include <cstring>
 #include <memory>
-#include <mutex>
 #include <utility>
 
+#include "foto_devmem.h"
 #include "foto_internal.h"
 #include "foto_spectral.h"
 #include "foto_xfer.h"
 
 namespace foto {
-
-static thread_local char g_err[2048] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-static std::mutex g_pool_mu;
-static std::vector<std::pair<int, hipStream_t>> g_pool;   // (device, stream) free list
-static std::vector<std::pair<hipStream_t, int>> g_live;   // streams handed out, with their device
-
-// a stream of the current device; stream_release files it under the device it was created on
-// (not the device current at release: a context on device 1 closed while device 0 is current)
-int stream_acquire(hipStream_t* out) {
-    int dev = 0;
-    FOTO_HIP_CHECK(hipGetDevice(&dev));
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mu);
-        for (size_t i = 0; i < g_pool.size(); ++i)
-            if (g_pool[i].first == dev) {
-                *out = g_pool[i].second;
-                g_pool.erase(g_pool.begin() + i);
-                g_live.push_back({*out, dev});
-                return 0;
-            }
-    }
-    FOTO_HIP_CHECK(hipStreamCreateWithFlags(out, hipStreamNonBlocking));
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    g_live.push_back({*out, dev});
-    return 0;
-}
-
-void stream_release(hipStream_t s) {
-    if (!s) return;
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    for (size_t i = 0; i < g_live.size(); ++i)
-        if (g_live[i].first == s) {
-            g_pool.push_back({g_live[i].second, s});
-            g_live.erase(g_live.begin() + i);
-            return;
-        }
-}
-
-int stream_device(hipStream_t s) {
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    for (const auto& e : g_live)
-        if (e.first == s) return e.second;
-    return -1;
-}
 
 #define FOTO_NCCL_CHECK(call)                                                                 \
     do {                                                                                     \
@@ -124,11 +71,11 @@ struct Shard : Rot {
     RedBuf rb{};
     double* gath = nullptr;  // [0,W) rr | [W,2W) pap | [2W,4W) crit num/den
     CGScal* S = nullptr;
-    std::vector<void*> allocs;
     // the buffers a new context starts from zero in, as allocated: foto_bb_reset zeroes this list
     // again (rezero), so it cannot miss one
     std::vector<std::pair<void*, size_t>> zeroed;   // (base, bytes)
     std::unique_ptr<SpectralPlan> spec;
+    DevArena mem;   // declared after spec: the shard's blocks are freed before the plan goes
 
     double* gath_rr() { return gath; }
     double* gath_pap(int W) { return gath + W; }
@@ -136,9 +83,7 @@ struct Shard : Rot {
 
     template <class T>
     int alloc(size_t bytes, T** out) {
-        FOTO_HIP_CHECK(hipMalloc((void**)out, bytes));
-        allocs.push_back(*out);
-        return 0;
+        return mem.alloc(bytes, (void**)out);
     }
     // zeroed on the context's stream: a hipMemset (null stream) is not ordered with the
     // non-blocking stream the kernels run on -- it raced with k_init_mu
@@ -158,9 +103,6 @@ struct Shard : Rot {
     int rezero(hipStream_t st) {
         for (const auto& z : zeroed) FOTO_HIP_CHECK(hipMemsetAsync(z.first, 0, z.second, st));
         return 0;
-    }
-    ~Shard() {
-        for (void* a : allocs) (void)hipFree(a);
     }
 };
 
@@ -1354,7 +1296,6 @@ static int report_run(foto_bb_ctx* c, const Completed& k, double* out, double** 
 
 extern "C" {
 
-const char* foto_last_error(void) { return foto::g_err; }
 int foto_version(void) { return 1; }
 
 int foto_device_count(int* n) {
@@ -1422,22 +1363,10 @@ int foto_nccl_unique_id(void* out128) {
     return 0;
 }
 
-static int check_grid(int Nt, int Nx, int Ny) {
-    if (Nt < 2) {
-        set_error("Nt = %d: the reference needs Nt >= 2 (benamou_brenier.py:194 divides by Nt-1)", Nt);
-        return FOTO_ERR_ARG;
-    }
-    if (Nx < 2 || Ny < 2) {
-        set_error("Nx = %d, Ny = %d: operators need >= 2 points per axis (operators.py lap1d IndexError)", Nx, Ny);
-        return FOTO_ERR_ARG;
-    }
-    return 0;
-}
-
 // foto_bb_create and foto_bb_create_dev: the same context from either source of the densities
 static int bb_create(const RhoSrc& src, int Nt, int Nx, int Ny, double r, double reg_epsilon, const foto_bb_opts* opts,
                      foto_bb_ctx** out) {
-    FOTO_TRY(check_grid(Nt, Nx, Ny));
+    FOTO_TRY(grid_size_check(Nt, Nx, Ny, src.i0 ? "foto_bb_create_dev" : "foto_bb_create"));
     foto_bb_opts o;
     if (opts) o = *opts; else foto_bb_opts_default(&o);
     if (src.i0) {
@@ -2009,7 +1938,7 @@ int foto_bb_solve_ex(const double* rho0, const double* rhoT, int Nt, int Nx, int
 extern "C" int foto_cg(const double* b, int Nt, int Nx, int Ny, double r, double eps, double rtol, int maxiter, int mode,
                        double* x, int* iterations) {
     if (!b || !x) { set_error("null argument"); return FOTO_ERR_ARG; }
-    FOTO_TRY(check_grid(Nt, Nx, Ny));
+    FOTO_TRY(grid_size_check(Nt, Nx, Ny, "foto_cg"));
     const int64_t nxy = (int64_t)Nx * Ny, N = nxy * Nt;
     std::vector<double> z((size_t)nxy, 0.0);
     foto_bb_opts o;

@@ -9,67 +9,17 @@
 #include <memory>
 #include <mutex>
 
+#include "foto_devmem.h"
 #include "foto_internal.h"
 
 using namespace foto;
 
 namespace {
 
-struct Scope {   // one call's stream + device allocations
-    hipStream_t s = nullptr;
-    std::vector<void*> bufs;
-    int init() { return stream_acquire(&s); }
-    int dev(size_t n_doubles, double** out) {
-        void* p = nullptr;
-        FOTO_HIP_CHECK(hipMalloc(&p, std::max<size_t>(n_doubles, 1) * sizeof(double)));
-        bufs.push_back(p);
-        *out = (double*)p;
-        return 0;
-    }
-    int up(const double* h, size_t n, double** out) {
-        FOTO_TRY(dev(n, out));
-        FOTO_HIP_CHECK(hipMemcpyAsync(*out, h, n * sizeof(double), hipMemcpyHostToDevice, s));
-        return 0;
-    }
-    int down(double* h, const double* d, size_t n) {
-        FOTO_HIP_CHECK(hipMemcpyAsync(h, d, n * sizeof(double), hipMemcpyDeviceToHost, s));
-        return 0;
-    }
-    int sync() {
-        FOTO_HIP_CHECK(hipStreamSynchronize(s));
-        return 0;
-    }
-    ~Scope() {
-        if (s) (void)hipStreamSynchronize(s);
-        for (void* p : bufs) (void)hipFree(p);
-        stream_release(s);
-    }
-};
-
 Geo make_geo(int Nt, int Nx, int Ny) {
     Geo g;
     g.Nt = Nt; g.Ny = Ny; g.Nx = Nx; g.t0 = 0; g.nloc = Nt; g.nxy = (int64_t)Nx * Ny;
     return g;
-}
-
-int check3(int Nt, int Nx, int Ny) {
-    if (Nt < 2 || Nx < 2 || Ny < 2) {
-        set_error("grid (Nt=%d, Nx=%d, Ny=%d): every axis needs >= 2 points (reference raises IndexError)", Nt, Nx, Ny);
-        return FOTO_ERR_ARG;
-    }
-    return 0;
-}
-
-int check2(int Nx, int Ny) {
-    if (Nx < 2 || Ny < 2) {
-        set_error("image %dx%d: every axis needs >= 2 points", Nx, Ny);
-        return FOTO_ERR_ARG;
-    }
-    if ((int64_t)Nx * Ny >= ((int64_t)1 << 31)) {   // pixel indices are 32-bit in the kernels
-        set_error("image %dx%d: more than 2^31 pixels", Nx, Ny);
-        return FOTO_ERR_ARG;
-    }
-    return 0;
 }
 
 int bc_flag(char bc, int* bcD) {
@@ -84,8 +34,8 @@ int bc_flag(char bc, int* bcD) {
 extern "C" {
 
 int foto_grad_st(const double* phi, int Nt, int Nx, int Ny, double* out3) {
-    FOTO_TRY(check3(Nt, Nx, Ny));
-    Scope S;
+    FOTO_TRY(grid_size_check(Nt, Nx, Ny, "foto_grad_st"));
+    CallScope S;
     FOTO_TRY(S.init());
     const Geo g = make_geo(Nt, Nx, Ny);
     const size_t N = (size_t)Nt * g.nxy;
@@ -98,8 +48,8 @@ int foto_grad_st(const double* phi, int Nt, int Nx, int Ny, double* out3) {
 }
 
 int foto_div_st(const double* w3, int Nt, int Nx, int Ny, double* out) {
-    FOTO_TRY(check3(Nt, Nx, Ny));
-    Scope S;
+    FOTO_TRY(grid_size_check(Nt, Nx, Ny, "foto_div_st"));
+    CallScope S;
     FOTO_TRY(S.init());
     const Geo g = make_geo(Nt, Nx, Ny);
     const size_t N = (size_t)Nt * g.nxy;
@@ -112,8 +62,8 @@ int foto_div_st(const double* w3, int Nt, int Nx, int Ny, double* out) {
 }
 
 static int apply_common(const double* p, int Nt, int Nx, int Ny, double r, double eps, int lap, double* out) {
-    FOTO_TRY(check3(Nt, Nx, Ny));
-    Scope S;
+    FOTO_TRY(grid_size_check(Nt, Nx, Ny, lap ? "foto_laplacian_st" : "foto_apply_A"));
+    CallScope S;
     FOTO_TRY(S.init());
     const Geo g = make_geo(Nt, Nx, Ny);
     const size_t N = (size_t)Nt * g.nxy;
@@ -136,8 +86,8 @@ int foto_apply_A(const double* p, int Nt, int Nx, int Ny, double r, double eps, 
 int foto_grad2(const double* f, int Nx, int Ny, char bc, double* out2) {
     int bcD;
     FOTO_TRY(bc_flag(bc, &bcD));
-    FOTO_TRY(check2(Nx, Ny));
-    Scope S;
+    FOTO_TRY(image_size_check(Nx, Ny, 2, "foto_grad2"));
+    CallScope S;
     FOTO_TRY(S.init());
     const size_t n = (size_t)Nx * Ny;
     double *d, *o;
@@ -151,8 +101,8 @@ int foto_grad2(const double* f, int Nx, int Ny, char bc, double* out2) {
 int foto_div2(const double* uv, int Nx, int Ny, char bc, double* out) {
     int bcD;
     FOTO_TRY(bc_flag(bc, &bcD));
-    FOTO_TRY(check2(Nx, Ny));
-    Scope S;
+    FOTO_TRY(image_size_check(Nx, Ny, 2, "foto_div2"));
+    CallScope S;
     FOTO_TRY(S.init());
     const size_t n = (size_t)Nx * Ny;
     double *d, *o;
@@ -164,8 +114,8 @@ int foto_div2(const double* uv, int Nx, int Ny, char bc, double* out) {
 }
 
 int foto_grad2_forward(const double* f, int Nx, int Ny, double* out2) {
-    FOTO_TRY(check2(Nx, Ny));
-    Scope S;
+    FOTO_TRY(image_size_check(Nx, Ny, 2, "foto_grad2_forward"));
+    CallScope S;
     FOTO_TRY(S.init());
     const size_t n = (size_t)Nx * Ny;
     double *d, *o;
@@ -179,7 +129,7 @@ int foto_grad2_forward(const double* f, int Nx, int Ny, double* out2) {
 int foto_stepB(const double* p3, int64_t M, double* q3) {
     if (M < 0 || !p3 || !q3) { set_error("bad stepB arguments"); return FOTO_ERR_ARG; }
     if (M == 0) return 0;
-    Scope S;
+    CallScope S;
     FOTO_TRY(S.init());
     double *d, *o;
     FOTO_TRY(S.up(p3, 3 * (size_t)M, &d));
@@ -191,8 +141,8 @@ int foto_stepB(const double* p3, int64_t M, double* q3) {
 
 int foto_bb_rhs(const double* mu3, const double* q3, const double* rho0, const double* rhoT, int Nt, int Nx, int Ny,
                 double r, double* F) {
-    FOTO_TRY(check3(Nt, Nx, Ny));
-    Scope S;
+    FOTO_TRY(grid_size_check(Nt, Nx, Ny, "foto_bb_rhs"));
+    CallScope S;
     FOTO_TRY(S.init());
     const Geo g = make_geo(Nt, Nx, Ny);
     const size_t N = (size_t)Nt * g.nxy;
@@ -213,8 +163,8 @@ int foto_bb_rhs(const double* mu3, const double* q3, const double* rho0, const d
 }
 
 int foto_flow_from_phi(const double* phi, int Nt, int Nx, int Ny, double* u, double* v, double* m) {
-    FOTO_TRY(check3(Nt, Nx, Ny));
-    Scope S;
+    FOTO_TRY(grid_size_check(Nt, Nx, Ny, "foto_flow_from_phi"));
+    CallScope S;
     FOTO_TRY(S.init());
     const Geo g = make_geo(Nt, Nx, Ny);
     const size_t N = (size_t)Nt * g.nxy, n = (size_t)g.nxy;
@@ -234,10 +184,9 @@ int foto_flow_from_phi(const double* phi, int Nt, int Nx, int Ny, double* u, dou
 }
 
 int foto_flow_path_from_phi(const double* phi, int Nt, int Nx, int Ny, double* u, double* v, double* m) {
-    FOTO_TRY(check3(Nt, Nx, Ny));
-    FOTO_TRY(check2(Nx, Ny));
+    FOTO_TRY(grid_size_check(Nt, Nx, Ny, "foto_flow_path_from_phi"));
     if (!phi || !u || !v || !m) { set_error("foto_flow_path_from_phi: null pointer"); return FOTO_ERR_ARG; }
-    Scope S;
+    CallScope S;
     FOTO_TRY(S.init());
     const Geo g = make_geo(Nt, Nx, Ny);
     const size_t N = (size_t)Nt * g.nxy, n = (size_t)g.nxy, R = (size_t)(Nt - 1) * n;
@@ -261,11 +210,10 @@ int foto_flow_path_from_phi(const double* phi, int Nt, int Nx, int Ny, double* u
 int foto_track_from_phi(const double* phi, int Nt, int Nx, int Ny, const double* pts, int64_t M, int all_steps,
                         double* out) {
     const char* who = "foto_track_from_phi";
-    FOTO_TRY(check3(Nt, Nx, Ny));
-    FOTO_TRY(check2(Nx, Ny));
+    FOTO_TRY(grid_size_check(Nt, Nx, Ny, who));
     if (!phi) { set_error("%s: null pointer", who); return FOTO_ERR_ARG; }
     FOTO_TRY(track_arg_check(pts, out, M, all_steps, who));
-    Scope S;
+    CallScope S;
     FOTO_TRY(S.init());
     const Geo g = make_geo(Nt, Nx, Ny);
     const size_t N = (size_t)Nt * g.nxy, np = 2 * (size_t)M, nr = np * (size_t)(all_steps ? Nt - 1 : 1);
@@ -282,12 +230,8 @@ int foto_report_from_state(const double* mu3, const double* phi, const double* r
                            int Nx, int Ny, double* out) {
     const char* who = "foto_report_from_state";
     if (!mu3 || !phi || !rho0 || !rhoT || !out) { set_error("%s: null pointer", who); return FOTO_ERR_ARG; }
-    if (Nt < 2 || Nx < 1 || Ny < 1) {
-        set_error("%s: grid (Nt=%d, Nx=%d, Ny=%d) needs Nt >= 2, Nx >= 1, Ny >= 1", who, Nt, Nx, Ny);
-        return FOTO_ERR_ARG;
-    }
-    if ((int64_t)Nx * Ny >= ((int64_t)1 << 31)) { set_error("%s: more than 2^31 voxels per plane", who); return FOTO_ERR_ARG; }
-    Scope S;
+    FOTO_TRY(grid_size_check(Nt, Nx, Ny, who, 1));   // (the report's sums run on a one-voxel-wide plane too)
+    CallScope S;
     FOTO_TRY(S.init());
     const Geo g = make_geo(Nt, Nx, Ny);
     const size_t N = (size_t)Nt * g.nxy, ntab = (size_t)Nt * FOTO_REPORT_COLS;
@@ -312,8 +256,8 @@ int foto_report_from_state(const double* mu3, const double* phi, const double* r
 
 int foto_gn_apply(const double* f1, const double* f2, int w, int h, double alpha, double lam, const double* x3,
                   double* y3) {
-    FOTO_TRY(check2(w, h));
-    Scope S;
+    FOTO_TRY(image_size_check(w, h, 2, "foto_gn_apply"));
+    CallScope S;
     FOTO_TRY(S.init());
     const size_t n = (size_t)w * h;
     double *d1, *d2, *fx, *fy, *ft, *x, *y;
@@ -331,8 +275,8 @@ int foto_gn_apply(const double* f1, const double* f2, int w, int h, double alpha
 }
 
 int foto_gn_rhs(const double* f1, const double* f2, int w, int h, double* b3) {
-    FOTO_TRY(check2(w, h));
-    Scope S;
+    FOTO_TRY(image_size_check(w, h, 2, "foto_gn_rhs"));
+    CallScope S;
     FOTO_TRY(S.init());
     const size_t n = (size_t)w * h;
     double *d1, *d2, *fx, *fy, *ft, *b;
@@ -392,7 +336,7 @@ int foto_gn_solve_ex(const double* f1, const double* f2, int w, int h, double al
 
 static int gn_solve_impl(const double* f1, const double* f2, int w, int h, double alpha, double lam, double rtol,
                          int maxiter, double* u, double* v, double* m, int* iterations, foto_gn_stats* st) {
-    FOTO_TRY(check2(w, h));
+    FOTO_TRY(image_size_check(w, h, 2, "foto_gn_solve"));
     if (!(alpha > 0) || !(lam > 0)) {
         set_error("GN needs alpha > 0 and lambda > 0 (the block-Jacobi preconditioner divides by them)");
         return FOTO_ERR_ARG;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "foto_dct.h"
+#include "foto_devmem.h"
 #include "foto_devutil.h"
 #include "foto_twiddles.h"
 
@@ -989,45 +990,28 @@ extern "C" int foto_dct(const double* in, int outer, int n, int inner, int inver
         return FOTO_ERR_ARG;
     }
     const size_t tot = (size_t)outer * n * inner;
-    hipStream_t s = nullptr;
-    FOTO_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    std::vector<void*> bufs;
-    auto dev = [&](size_t nd, double** p) -> int {
-        FOTO_HIP_CHECK(hipMalloc((void**)p, std::max<size_t>(nd, 1) * 8));
-        bufs.push_back(*p);
-        return 0;
-    };
-    auto body = [&]() -> int {
-        double *din, *dout, *dtab = nullptr, *dC;
-        FOTO_TRY(dev(tot, &din));
-        FOTO_TRY(dev(tot, &dout));
-        FOTO_HIP_CHECK(hipMemcpyAsync(din, in, tot * 8, hipMemcpyHostToDevice, s));
-        int m1, m2;
-        hipError_t e = hipErrorNotSupported;
-        if (path != 2 && tn.dct_fft && fft_factors(n, &m1, &m2)) {
-            const std::vector<double> t = fft_table(n);
-            FOTO_TRY(dev(t.size(), &dtab));
-            FOTO_HIP_CHECK(hipMemcpyAsync(dtab, t.data(), t.size() * 8, hipMemcpyHostToDevice, s));
-            FOTO_HIP_CHECK(hipStreamSynchronize(s));
-            e = dct_fft_axis(outer, n, inner, inverse != 0, dtab, din, dout, s);
-        }
-        if (e == hipErrorNotSupported) {
-            if (path == 1) { set_error("foto_dct: no FFT plan for n = %d", n); return FOTO_ERR_ARG; }
-            std::vector<double> C, CT, mu;
-            dct_matrix(n, C, CT, mu);
-            FOTO_TRY(dev(C.size(), &dC));
-            FOTO_HIP_CHECK(hipMemcpyAsync(dC, inverse ? CT.data() : C.data(), C.size() * 8, hipMemcpyHostToDevice, s));
-            FOTO_HIP_CHECK(hipStreamSynchronize(s));
-            e = dct_axis(outer, n, inner, dC, din, dout, s);
-        }
-        FOTO_HIP_CHECK(e);
-        FOTO_HIP_CHECK(hipMemcpyAsync(out, dout, tot * 8, hipMemcpyDeviceToHost, s));
-        FOTO_HIP_CHECK(hipStreamSynchronize(s));
-        return 0;
-    };
-    const int rc = body();
-    (void)hipStreamSynchronize(s);
-    for (void* p : bufs) (void)hipFree(p);
-    (void)hipStreamDestroy(s);
-    return rc;
+    CallScope S;
+    FOTO_TRY(S.init());
+    double *din, *dout, *dtab = nullptr, *dC;
+    FOTO_TRY(S.up(in, tot, &din));
+    FOTO_TRY(S.dev(tot, &dout));
+    int m1, m2;
+    hipError_t e = hipErrorNotSupported;
+    if (path != 2 && tn.dct_fft && fft_factors(n, &m1, &m2)) {
+        const std::vector<double> t = fft_table(n);   // (host table: the sync below ends the copy from it)
+        FOTO_TRY(S.up(t.data(), t.size(), &dtab));
+        FOTO_TRY(S.sync());
+        e = dct_fft_axis(outer, n, inner, inverse != 0, dtab, din, dout, S.s);
+    }
+    if (e == hipErrorNotSupported) {
+        if (path == 1) { set_error("foto_dct: no FFT plan for n = %d", n); return FOTO_ERR_ARG; }
+        std::vector<double> C, CT, mu;
+        dct_matrix(n, C, CT, mu);
+        FOTO_TRY(S.up(inverse ? CT.data() : C.data(), C.size(), &dC));
+        FOTO_TRY(S.sync());
+        e = dct_axis(outer, n, inner, dC, din, dout, S.s);
+    }
+    FOTO_HIP_CHECK(e);
+    FOTO_TRY(S.down(out, dout, tot));
+    return S.sync();
 }

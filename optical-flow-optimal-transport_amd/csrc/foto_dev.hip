@@ -338,27 +338,6 @@ hipError_t launch_frames(const FrameArgs& fa, int count, int64_t n, double scale
     return hipErrorInvalidValue;
 }
 
-// ----------------------------------------------------------------------------- stream contract
-
-int StreamLink::enter(hipStream_t user, hipStream_t own) {
-    if (!in) FOTO_HIP_CHECK(hipEventCreateWithFlags(&in, hipEventDisableTiming));
-    if (!out) FOTO_HIP_CHECK(hipEventCreateWithFlags(&out, hipEventDisableTiming));
-    FOTO_HIP_CHECK(hipEventRecord(in, user));
-    FOTO_HIP_CHECK(hipStreamWaitEvent(own, in, 0));
-    return 0;
-}
-
-int StreamLink::leave(hipStream_t own, hipStream_t user) {
-    FOTO_HIP_CHECK(hipEventRecord(out, own));
-    FOTO_HIP_CHECK(hipStreamWaitEvent(user, out, 0));
-    return 0;
-}
-
-StreamLink::~StreamLink() {
-    if (in) (void)hipEventDestroy(in);
-    if (out) (void)hipEventDestroy(out);
-}
-
 }  // namespace foto
 
 using namespace foto;

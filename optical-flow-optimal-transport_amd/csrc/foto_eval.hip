@@ -13,6 +13,7 @@
 #include <mutex>
 #include <vector>
 
+#include "foto_devmem.h"
 #include "foto_devutil.h"
 #include "foto_internal.h"
 
@@ -96,14 +97,16 @@ std::mutex ev_mu;
 std::vector<EvSlots> ev_dev;   // per device (a slot is only valid on the device it was made on)
 
 struct EvScope {
+    std::unique_lock<std::mutex> lk{ev_mu};   // (first: unlocked after `call` has drained its stream)
+    CallScope call;                           // the stream: acquired, synchronised on exit, released
     hipStream_t s = nullptr;
-    std::unique_lock<std::mutex> lk{ev_mu};
     EvSlots* sl = nullptr;
     int used = 0;
     bool dev_in = false;   // the *_dev entries: inputs are device arrays already, nothing to upload
     int device = -1;
     int init() {
-        FOTO_TRY(stream_acquire(&s));
+        FOTO_TRY(call.init());
+        s = call.s;
         const int dev = stream_device(s);
         if (dev < 0) {
             set_error("evaluation: stream without a device");
@@ -148,21 +151,14 @@ struct EvScope {
         return 0;
     }
     int dev(size_t n, double** d) { return slot(n, d); }
-    ~EvScope() {
-        if (s) (void)hipStreamSynchronize(s);
-        stream_release(s);
-    }
 };
 
 // the two passes; out: mean EE, std EE, mean AE, std AE, IE (any of the inputs may be absent)
 // (on_dev: the six inputs are device arrays, used in place -- the *_dev entries)
 int ev_errors(const double* u, const double* v, const double* uG, const double* vG, const double* I,
               const double* IG, int w, int h, double* out5, bool on_dev = false, hipStream_t user = nullptr,
-              const char* who = "") {
-    if (w < 1 || h < 1) {
-        set_error("flow errors: w, h must be >= 1");
-        return FOTO_ERR_ARG;
-    }
+              const char* who = "flow errors") {
+    FOTO_TRY(image_size_check(w, h, 1, who));
     const int64_t n = (int64_t)w * h;
     EvScope S;
     if (on_dev) {
@@ -215,10 +211,11 @@ using namespace foto;
 extern "C" {
 
 int foto_warp(const double* f1, const double* u, const double* v, const double* m, int w, int h, double* out) {
-    if (!f1 || !u || !v || !out || w < 1 || h < 1) {
-        set_error("foto_warp: null buffer or w, h < 1");
+    if (!f1 || !u || !v || !out) {
+        set_error("foto_warp: null buffer");
         return FOTO_ERR_ARG;
     }
+    FOTO_TRY(image_size_check(w, h, 1, "foto_warp"));
     const int64_t n = (int64_t)w * h;
     EvScope S;
     FOTO_TRY(S.init());
@@ -237,10 +234,11 @@ int foto_warp(const double* f1, const double* u, const double* v, const double* 
 
 int foto_warp_dev(const double* f1, const double* u, const double* v, const double* m, int w, int h, double* out,
                   void* stream) {
-    if (!f1 || !u || !v || !out || w < 1 || h < 1) {
-        set_error("foto_warp_dev: null buffer or w, h < 1");
+    if (!f1 || !u || !v || !out) {
+        set_error("foto_warp_dev: null buffer");
         return FOTO_ERR_ARG;
     }
+    FOTO_TRY(image_size_check(w, h, 1, "foto_warp_dev"));
     const size_t n = (size_t)w * h;
     EvScope S;
     FOTO_TRY(S.init());

@@ -15,6 +15,7 @@
 #include <memory>
 #include <vector>
 
+#include "foto_devmem.h"
 #include "foto_gn.h"
 #include "foto_hostpool.h"
 #include "foto_internal.h"
@@ -251,25 +252,16 @@ __global__ __launch_bounds__(NT) void k_gn_pcg_upd(int w, int h, int k, const do
 // host polls the done flag between chunks of iterations.
 int gn_bj_solve(const double* f1, const double* f2, int w, int h, double alpha, double lam, double rtol, int maxiter,
                 double* u, double* v, double* m, int* iterations) {
-    struct Call {   // the call's stream, its one device allocation and the pinned scalars
-        hipStream_t s = nullptr;
-        double* base = nullptr;
-        CGScal* hS = nullptr;
-        ~Call() {
-            if (s) (void)hipStreamSynchronize(s);
-            if (base) (void)hipFree(base);
-            if (hS) (void)hipHostFree(hS);
-            stream_release(s);
-        }
-    } C;
-    FOTO_TRY(stream_acquire(&C.s));
+    CallScope C;   // the call's stream, its one device allocation and the pinned scalars
+    FOTO_TRY(C.init());
     hipStream_t s = C.s;
     const size_t n = (size_t)w * h;
     const int nb = flat_blocks((int64_t)n), grid = gn_grid((int64_t)n);
     // one allocation (a solve is ~15 ms; per-buffer hipMalloc/hipFree added up to ~1 ms)
     const size_t nscal = sizeof(CGScal) / sizeof(double) + 1;
-    FOTO_HIP_CHECK(hipMalloc((void**)&C.base, (23 * n + 2 * (size_t)nb + 8 + 8 + nscal) * sizeof(double)));
-    double *d1 = C.base, *d2 = d1 + n, *fx = d2 + n, *fy = fx + n, *ft = fy + n, *b = ft + n, *x = b + 3 * n,
+    double* base = nullptr;
+    FOTO_TRY(C.dev(23 * n + 2 * (size_t)nb + 8 + 8 + nscal, &base));
+    double *d1 = base, *d2 = d1 + n, *fx = d2 + n, *fy = fx + n, *ft = fy + n, *b = ft + n, *x = b + 3 * n,
            *r = x + 3 * n, *z = r + 3 * n, *p0 = z + 3 * n, *p1 = p0 + 3 * n, *part = p1 + 3 * n,
            *gath = part + 2 * (size_t)nb + 8;
     CGScal* dS = (CGScal*)(gath + 8);
@@ -285,7 +277,8 @@ int gn_bj_solve(const double* f1, const double* f2, int w, int h, double alpha, 
     FOTO_HIP_CHECK(launch_gn_rhs(w, h, fx, fy, d2, ft, b, s));
     k_gn_pcg_init<<<grid, NT, 0, s>>>(w, h, fx, fy, d2, alpha, lam, b, r, z, rb, g_rz);
     FOTO_HIP_CHECK(hipGetLastError());
-    FOTO_HIP_CHECK(hipHostMalloc((void**)&C.hS, sizeof(CGScal)));
+    CGScal* hS = nullptr;
+    FOTO_TRY(C.pinned(sizeof(CGScal), (void**)&hS));
     int k = 0;
     bool done = false;
     while (k < maxiter) {
@@ -298,15 +291,15 @@ int gn_bj_solve(const double* f1, const double* f2, int w, int h, double alpha, 
             k_gn_pcg_upd<<<grid, NT, 0, s>>>(w, h, k, fx, fy, d2, alpha, lam, pn, x, r, z, dS, rb, g_pq, g_rz);
             FOTO_HIP_CHECK(hipGetLastError());
         }
-        FOTO_HIP_CHECK(hipMemcpyAsync(C.hS, dS, sizeof(CGScal), hipMemcpyDeviceToHost, s));
+        FOTO_HIP_CHECK(hipMemcpyAsync(hS, dS, sizeof(CGScal), hipMemcpyDeviceToHost, s));
         FOTO_HIP_CHECK(hipStreamSynchronize(s));
-        if (C.hS->done) { done = true; break; }
+        if (hS->done) { done = true; break; }
     }
     double* const outs[3] = {u, v, m};
     for (int c = 0; c < 3; ++c)
         FOTO_HIP_CHECK(hipMemcpyAsync(outs[c], x + c * n, n * sizeof(double), hipMemcpyDeviceToHost, s));
     FOTO_HIP_CHECK(hipStreamSynchronize(s));
-    if (iterations) *iterations = done ? C.hS->iters : maxiter;
+    if (iterations) *iterations = done ? hS->iters : maxiter;
     return done ? 0 : maxiter;
 }
 
@@ -1765,7 +1758,7 @@ extern "C" {
 
 int foto_gn_plan_create(int w, int h, double alpha, double lambda_, double rtol, int maxiter, foto_gn_plan** out) {
     if (!out) { set_error("null argument"); return FOTO_ERR_ARG; }
-    if (w < 2 || h < 2) { set_error("w = %d, h = %d: GN needs >= 2 pixels per axis", w, h); return FOTO_ERR_ARG; }
+    FOTO_TRY(image_size_check(w, h, 2, "foto_gn_plan_create"));
     if (!(alpha > 0) || !(lambda_ > 0)) {
         set_error("GN needs alpha > 0 and lambda > 0 (the block-Jacobi smoother divides by them)");
         return FOTO_ERR_ARG;

@@ -11,6 +11,7 @@
 #include <memory>
 #include <vector>
 
+#include "foto_devmem.h"
 #include "foto_gn.h"
 
 namespace foto {
@@ -124,9 +125,9 @@ static hipError_t launch_pyr_warp(int w, int h, const double* f2, const double* 
 
 // ----------------------------------------------------------------------------- level sizes (host)
 
-static int pyr_sizes(int w, int h, int levels, int min_size, std::vector<int>& wl, std::vector<int>& hl) {
-    if (w < 2 || h < 2) { set_error("image %dx%d: every axis needs >= 2 points", w, h); return FOTO_ERR_ARG; }
-    if ((int64_t)w * h >= ((int64_t)1 << 31)) { set_error("image %dx%d: w h must be < 2^31", w, h); return FOTO_ERR_ARG; }
+static int pyr_sizes(int w, int h, int levels, int min_size, std::vector<int>& wl, std::vector<int>& hl,
+                     const char* who) {
+    FOTO_TRY(image_size_check(w, h, 2, who));
     if (levels < 1) { set_error("levels = %d: the pyramid needs >= 1 level", levels); return FOTO_ERR_ARG; }
     if (min_size < 2) { set_error("min_size = %d: a level needs >= 2 pixels per axis", min_size); return FOTO_ERR_ARG; }
     wl.assign(1, w);
@@ -138,37 +139,6 @@ static int pyr_sizes(int w, int h, int levels, int min_size, std::vector<int>& w
     }
     return 0;
 }
-
-// one call's stream and device allocations (the test entries below)
-struct PyrScope {
-    hipStream_t s = nullptr;
-    std::vector<void*> bufs;
-    int init() { return stream_acquire(&s); }
-    int dev(size_t n, double** out) {
-        void* p = nullptr;
-        FOTO_HIP_CHECK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(double)));
-        bufs.push_back(p);
-        *out = (double*)p;
-        return 0;
-    }
-    int up(const double* h, size_t n, double* d) {
-        FOTO_HIP_CHECK(hipMemcpyAsync(d, h, n * sizeof(double), hipMemcpyHostToDevice, s));
-        return 0;
-    }
-    int down(double* h, const double* d, size_t n) {
-        FOTO_HIP_CHECK(hipMemcpyAsync(h, d, n * sizeof(double), hipMemcpyDeviceToHost, s));
-        return 0;
-    }
-    int sync() {
-        FOTO_HIP_CHECK(hipStreamSynchronize(s));
-        return 0;
-    }
-    ~PyrScope() {
-        if (s) (void)hipStreamSynchronize(s);
-        for (void* p : bufs) (void)hipFree(p);
-        stream_release(s);
-    }
-};
 
 }  // namespace foto
 
@@ -321,7 +291,7 @@ extern "C" {
 int foto_gn_pyr_sizes(int w, int h, int levels, int min_size, int* wl, int* hl, int cap, int* n) {
     if (!wl || !hl || !n) { set_error("foto_gn_pyr_sizes: null argument"); return FOTO_ERR_ARG; }
     std::vector<int> a, b;
-    FOTO_TRY(pyr_sizes(w, h, levels, min_size, a, b));
+    FOTO_TRY(pyr_sizes(w, h, levels, min_size, a, b, "foto_gn_pyr_sizes"));
     if (cap < (int)a.size()) { set_error("foto_gn_pyr_sizes: cap = %d for %d levels", cap, (int)a.size()); return FOTO_ERR_ARG; }
     for (size_t l = 0; l < a.size(); ++l) { wl[l] = a[l]; hl[l] = b[l]; }
     *n = (int)a.size();
@@ -344,7 +314,7 @@ int foto_gn_pyr_create(int w, int h, double alpha, double lambda_, const foto_gn
     (void)foto_gn_pyr_opts_default(&o);
     if (opts) o = *opts;
     auto P = std::make_unique<foto_gn_pyr>();
-    FOTO_TRY(pyr_sizes(w, h, o.levels, o.min_size, P->wl, P->hl));
+    FOTO_TRY(pyr_sizes(w, h, o.levels, o.min_size, P->wl, P->hl, "foto_gn_pyr_create"));
     FOTO_TRY(pyr_opts_check(o));
     if (!(alpha > 0) || !(lambda_ > 0)) {
         set_error("GN needs alpha > 0 and lambda > 0 (the block-Jacobi smoother divides by them)");
@@ -396,11 +366,8 @@ int foto_gn_pyr_solve_dev(foto_gn_pyr* p, const foto_image* f1, const foto_image
 
 int foto_pyr_down(const double* f1, const double* f2, int w, int h, double* c1, double* c2) {
     if (!f1 || !f2 || !c1 || !c2) { set_error("foto_pyr_down: null argument"); return FOTO_ERR_ARG; }
-    if (w < 1 || h < 1 || (int64_t)w * h >= ((int64_t)1 << 31)) {
-        set_error("foto_pyr_down: image %dx%d", w, h);
-        return FOTO_ERR_ARG;
-    }
-    PyrScope S;
+    FOTO_TRY(image_size_check(w, h, 1, "foto_pyr_down"));
+    CallScope S;
     FOTO_TRY(S.init());
     const size_t n = (size_t)w * h, nc = (size_t)((w + 1) / 2) * ((h + 1) / 2);
     double *d1, *d2, *o1, *o2;
@@ -408,28 +375,20 @@ int foto_pyr_down(const double* f1, const double* f2, int w, int h, double* c1, 
     FOTO_TRY(S.dev(n, &d2));
     FOTO_TRY(S.dev(nc, &o1));
     FOTO_TRY(S.dev(nc, &o2));
-    FOTO_TRY(S.up(f1, n, d1));
-    FOTO_TRY(S.up(f2, n, d2));
+    FOTO_TRY(S.up_to(f1, n, d1));
+    FOTO_TRY(S.up_to(f2, n, d2));
     FOTO_HIP_CHECK(launch_pyr_down(w, h, d1, d2, o1, o2, S.s));
     FOTO_TRY(S.down(c1, o1, nc));
     FOTO_TRY(S.down(c2, o2, nc));
     return S.sync();
 }
 
-static int pyr_check2(int w, int h, const char* who) {
-    if (w < 2 || h < 2 || (int64_t)w * h >= ((int64_t)1 << 31)) {
-        set_error("%s: image %dx%d: every axis needs >= 2 points and w h < 2^31", who, w, h);
-        return FOTO_ERR_ARG;
-    }
-    return 0;
-}
-
 int foto_pyr_up(const double* u, const double* v, const double* m, int wc, int hc, int w, int h, double* uo,
                 double* vo, double* mo) {
     if (!u || !v || !m || !uo || !vo || !mo) { set_error("foto_pyr_up: null argument"); return FOTO_ERR_ARG; }
-    FOTO_TRY(pyr_check2(wc, hc, "foto_pyr_up (coarse)"));
-    FOTO_TRY(pyr_check2(w, h, "foto_pyr_up (fine)"));
-    PyrScope S;
+    FOTO_TRY(image_size_check(wc, hc, 2, "foto_pyr_up (coarse)"));
+    FOTO_TRY(image_size_check(w, h, 2, "foto_pyr_up (fine)"));
+    CallScope S;
     FOTO_TRY(S.init());
     const size_t n = (size_t)w * h, nc = (size_t)wc * hc;
     double *c, *o;
@@ -437,7 +396,7 @@ int foto_pyr_up(const double* u, const double* v, const double* m, int wc, int h
     FOTO_TRY(S.dev(3 * n, &o));
     const double* const in[3] = {u, v, m};
     double* const outs[3] = {uo, vo, mo};
-    for (int f = 0; f < 3; ++f) FOTO_TRY(S.up(in[f], nc, c + f * nc));
+    for (int f = 0; f < 3; ++f) FOTO_TRY(S.up_to(in[f], nc, c + f * nc));
     FOTO_HIP_CHECK(launch_pyr_up(wc, hc, w, h, c, o, S.s));
     for (int f = 0; f < 3; ++f) FOTO_TRY(S.down(outs[f], o + f * n, n));
     return S.sync();
@@ -445,17 +404,17 @@ int foto_pyr_up(const double* u, const double* v, const double* m, int wc, int h
 
 int foto_gn_warp_prior(const double* f2, const double* u, const double* v, const double* m, int w, int h, double* g) {
     if (!f2 || !u || !v || !m || !g) { set_error("foto_gn_warp_prior: null argument"); return FOTO_ERR_ARG; }
-    FOTO_TRY(pyr_check2(w, h, "foto_gn_warp_prior"));
-    PyrScope S;
+    FOTO_TRY(image_size_check(w, h, 2, "foto_gn_warp_prior"));
+    CallScope S;
     FOTO_TRY(S.init());
     const size_t n = (size_t)w * h;
     double *d2, *p, *o;
     FOTO_TRY(S.dev(n, &d2));
     FOTO_TRY(S.dev(3 * n, &p));
     FOTO_TRY(S.dev(n, &o));
-    FOTO_TRY(S.up(f2, n, d2));
+    FOTO_TRY(S.up_to(f2, n, d2));
     const double* const in[3] = {u, v, m};
-    for (int f = 0; f < 3; ++f) FOTO_TRY(S.up(in[f], n, p + f * n));
+    for (int f = 0; f < 3; ++f) FOTO_TRY(S.up_to(in[f], n, p + f * n));
     FOTO_HIP_CHECK(launch_pyr_warp(w, h, d2, p, o, S.s));
     FOTO_TRY(S.down(g, o, n));
     return S.sync();
@@ -467,29 +426,26 @@ int foto_gn_solve_prior(const double* f1, const double* g, int w, int h, double 
     if (!f1 || !g || !u || !v || !m) { set_error("foto_gn_solve_prior: null argument"); return FOTO_ERR_ARG; }
     const bool prior = u0 || v0 || m0;
     if (prior && (!u0 || !v0 || !m0)) { set_error("foto_gn_solve_prior: a prior needs u0, v0 and m0"); return FOTO_ERR_ARG; }
+    // (the prior's block is declared before the plan's owner, so it is freed after it: destroying
+    // the plan drains the plan's stream first, and the solve on it may still read the prior)
+    DevArena mem;
+    double* x0 = nullptr;
     foto_gn_plan* pl = nullptr;
     FOTO_TRY(foto_gn_plan_create(w, h, alpha, lambda_, rtol, maxiter, &pl));
-    struct Holder {   // (declared before the scratch: the plan's stream drains first)
-        foto_gn_plan* p;
-        double* x0 = nullptr;
-        ~Holder() {
-            foto_gn_plan_destroy(p);
-            if (x0) (void)hipFree(x0);
-        }
-    } H{pl};
+    const std::unique_ptr<foto_gn_plan, void (*)(foto_gn_plan*)> owner(pl, foto_gn_plan_destroy);
     const GnBufs B = gn_plan_bufs(pl);
     const size_t n = (size_t)w * h;
     FOTO_HIP_CHECK(hipMemcpyAsync(B.d1, f1, n * sizeof(double), hipMemcpyHostToDevice, B.s));
     FOTO_HIP_CHECK(hipMemcpyAsync(B.d2, g, n * sizeof(double), hipMemcpyHostToDevice, B.s));
     if (prior) {
-        FOTO_HIP_CHECK(hipMalloc((void**)&H.x0, 3 * n * sizeof(double)));
+        FOTO_TRY(mem.alloc_n(3 * n, &x0));
         const double* const in[3] = {u0, v0, m0};
         for (int f = 0; f < 3; ++f)
-            FOTO_HIP_CHECK(hipMemcpyAsync(H.x0 + f * n, in[f], n * sizeof(double), hipMemcpyHostToDevice, B.s));
+            FOTO_HIP_CHECK(hipMemcpyAsync(x0 + f * n, in[f], n * sizeof(double), hipMemcpyHostToDevice, B.s));
     }
     int its = 0;
     bool done = false;
-    FOTO_TRY(gn_plan_solve_prior(pl, H.x0, &its, &done));
+    FOTO_TRY(gn_plan_solve_prior(pl, x0, &its, &done));
     double* const outs[3] = {u, v, m};
     for (int f = 0; f < 3; ++f)
         FOTO_HIP_CHECK(hipMemcpyAsync(outs[f], B.x + f * n, n * sizeof(double), hipMemcpyDeviceToHost, B.s));

@@ -34,13 +34,21 @@ void set_error(const char* fmt, ...);
     } while (0)
 
 // ----------------------------------------------------------------------------- streams
-// Streams come from a process-wide pool (foto_bb.cpp): a hipStreamCreate costs ~10 ms on the
+// Streams come from a process-wide pool (foto_host.cpp): a hipStreamCreate costs ~10 ms on the
 // MI355X box (FOTO_GN_TRACE), which every BB context, GN plan and per-call scope paid -- a
 // batch of solves paid it per solve.  acquire returns a stream of the current device; release
 // takes back a stream with no work pending (callers synchronise first).  Never destroyed.
 int stream_acquire(hipStream_t* out);
 void stream_release(hipStream_t s);
 int stream_device(hipStream_t s);   // the device a pooled stream belongs to (-1: not pooled)
+
+// ----------------------------------------------------------------------------- size rules
+// (foto_host.cpp) The only copies of the rules: FOTO_ERR_ARG with a message that starts with `who`.
+// An image: both sides >= min_side (2 where a difference stencil or a bilinear tap runs, 1 for the
+// pointwise entries) and w h < 2^31 (pixel indices are 32-bit in the kernels).
+int image_size_check(int w, int h, int min_side, const char* who);
+// A space-time grid: Nt >= 2, then the plane's image rule.
+int grid_size_check(int Nt, int Nx, int Ny, const char* who, int min_side = 2);
 
 // ----------------------------------------------------------------------------- geometry
 // One time-slab shard of the (Nt, Ny, Nx) grid: local planes l in [0, nloc) are global

@@ -2,6 +2,7 @@
 // kernels alone, for bench.py's roofline figures.  Not part of the solver.
 #include <algorithm>
 
+#include "foto_devmem.h"
 #include "foto_devutil.h"
 #include "foto_internal.h"
 
@@ -52,49 +53,54 @@ __global__ __launch_bounds__(256) void k_stream_4x4(const double* __restrict__ a
 }
 }  // namespace foto
 
+namespace foto {
+struct EventPair {   // a probe's two timing events
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int init() {
+        FOTO_HIP_CHECK(hipEventCreate(&e0));
+        FOTO_HIP_CHECK(hipEventCreate(&e1));
+        return 0;
+    }
+    ~EventPair() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+}  // namespace foto
+
 extern "C" int foto_stream_probe4(int64_t n, int reps, double* us) {
     using namespace foto;
     if (!us || n < 2 || n % 2 || reps < 1) {
         set_error("foto_stream_probe4: bad arguments (n even)");
         return FOTO_ERR_ARG;
     }
-    hipStream_t s = nullptr;
+    EventPair ev;   // (declared first: released after the scope has drained the stream)
+    CallScope S;
+    FOTO_TRY(S.init());
+    hipStream_t s = S.s;
     double* f[8] = {nullptr};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto body = [&]() -> int {
-        FOTO_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        for (int i = 0; i < 8; ++i) FOTO_HIP_CHECK(hipMalloc((void**)&f[i], n * 8));
-        for (int i = 0; i < 8; i += 2) k_stream_fill<<<1024, 256, 0, s>>>(f[i], f[i + 1], n);   // non-zero data
-        FOTO_HIP_CHECK(hipGetLastError());
-        FOTO_HIP_CHECK(hipEventCreate(&e0));
-        FOTO_HIP_CHECK(hipEventCreate(&e1));
-        const int nb = 4 * cus_count();
-        float best = 1e30f;
-        for (int rep = 0; rep < 3; ++rep) {
-            FOTO_HIP_CHECK(hipEventRecord(e0, s));
-            for (int k = 0; k < reps; ++k) {
-                double** A = (k & 1) ? f + 4 : f;
-                double** B = (k & 1) ? f : f + 4;
-                k_stream_4x4<<<nb, 256, 0, s>>>(A[0], A[1], A[2], A[3], B[0], B[1], B[2], B[3], n / 2, 1e-9);
-            }
-            FOTO_HIP_CHECK(hipGetLastError());
-            FOTO_HIP_CHECK(hipEventRecord(e1, s));
-            FOTO_HIP_CHECK(hipEventSynchronize(e1));
-            float t = 0.f;
-            FOTO_HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-            best = std::min(best, t);
+    for (int i = 0; i < 8; ++i) FOTO_TRY(S.dev((size_t)n, &f[i]));
+    for (int i = 0; i < 8; i += 2) k_stream_fill<<<1024, 256, 0, s>>>(f[i], f[i + 1], n);   // non-zero data
+    FOTO_HIP_CHECK(hipGetLastError());
+    FOTO_TRY(ev.init());
+    const int nb = 4 * cus_count();
+    float best = 1e30f;
+    for (int rep = 0; rep < 3; ++rep) {
+        FOTO_HIP_CHECK(hipEventRecord(ev.e0, s));
+        for (int k = 0; k < reps; ++k) {
+            double** A = (k & 1) ? f + 4 : f;
+            double** B = (k & 1) ? f : f + 4;
+            k_stream_4x4<<<nb, 256, 0, s>>>(A[0], A[1], A[2], A[3], B[0], B[1], B[2], B[3], n / 2, 1e-9);
         }
-        us[0] = 1e3 * best / reps;
-        return 0;
-    };
-    const int rc = body();
-    if (s) (void)hipStreamSynchronize(s);
-    for (double* p : f)
-        if (p) (void)hipFree(p);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (s) (void)hipStreamDestroy(s);
-    return rc;
+        FOTO_HIP_CHECK(hipGetLastError());
+        FOTO_HIP_CHECK(hipEventRecord(ev.e1, s));
+        FOTO_HIP_CHECK(hipEventSynchronize(ev.e1));
+        float t = 0.f;
+        FOTO_HIP_CHECK(hipEventElapsedTime(&t, ev.e0, ev.e1));
+        best = std::min(best, t);
+    }
+    us[0] = 1e3 * best / reps;
+    return 0;
 }
 
 extern "C" int foto_stream_probe(int64_t n, int reps, double* us) {
@@ -103,43 +109,34 @@ extern "C" int foto_stream_probe(int64_t n, int reps, double* us) {
         set_error("foto_stream_probe: bad arguments (n even, n * 8 < 2^31)");
         return FOTO_ERR_ARG;
     }
-    hipStream_t s = nullptr;
+    EventPair ev;   // (declared first: released after the scope has drained the stream)
+    CallScope S;
+    FOTO_TRY(S.init());
+    hipStream_t s = S.s;
     double *r = nullptr, *q = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto body = [&]() -> int {
-        FOTO_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        FOTO_HIP_CHECK(hipMalloc((void**)&r, n * 8));
-        FOTO_HIP_CHECK(hipMalloc((void**)&q, n * 8));
-        // non-zero data: zero-filled buffers let the chip hold a higher clock (MI355X_MICROARCH.md,
-        // DVFS give-back) and read 15-20 % faster than the solver's vectors do
-        k_stream_fill<<<1024, 256, 0, s>>>(r, q, n);
-        FOTO_HIP_CHECK(hipGetLastError());
-        FOTO_HIP_CHECK(hipEventCreate(&e0));
-        FOTO_HIP_CHECK(hipEventCreate(&e1));
-        for (int wt = 0; wt < 2; ++wt) {
-            float best = 1e30f;
-            for (int rep = 0; rep < 3; ++rep) {
-                FOTO_HIP_CHECK(hipEventRecord(e0, s));
-                for (int k = 0; k < reps; ++k) {
-                    if (wt) k_stream_rq<true><<<1024, 256, 0, s>>>(r, q, n / 2, 1e-9, 1e-9);
-                    else k_stream_rq<false><<<1024, 256, 0, s>>>(r, q, n / 2, 1e-9, 1e-9);
-                }
-                FOTO_HIP_CHECK(hipGetLastError());
-                FOTO_HIP_CHECK(hipEventRecord(e1, s));
-                FOTO_HIP_CHECK(hipEventSynchronize(e1));
-                float t = 0.f;
-                FOTO_HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-                best = std::min(best, t);
+    FOTO_TRY(S.dev((size_t)n, &r));
+    FOTO_TRY(S.dev((size_t)n, &q));
+    // non-zero data: zero-filled buffers let the chip hold a higher clock (MI355X_MICROARCH.md,
+    // DVFS give-back) and read 15-20 % faster than the solver's vectors do
+    k_stream_fill<<<1024, 256, 0, s>>>(r, q, n);
+    FOTO_HIP_CHECK(hipGetLastError());
+    FOTO_TRY(ev.init());
+    for (int wt = 0; wt < 2; ++wt) {
+        float best = 1e30f;
+        for (int rep = 0; rep < 3; ++rep) {
+            FOTO_HIP_CHECK(hipEventRecord(ev.e0, s));
+            for (int k = 0; k < reps; ++k) {
+                if (wt) k_stream_rq<true><<<1024, 256, 0, s>>>(r, q, n / 2, 1e-9, 1e-9);
+                else k_stream_rq<false><<<1024, 256, 0, s>>>(r, q, n / 2, 1e-9, 1e-9);
             }
-            us[wt] = 1e3 * best / reps;
+            FOTO_HIP_CHECK(hipGetLastError());
+            FOTO_HIP_CHECK(hipEventRecord(ev.e1, s));
+            FOTO_HIP_CHECK(hipEventSynchronize(ev.e1));
+            float t = 0.f;
+            FOTO_HIP_CHECK(hipEventElapsedTime(&t, ev.e0, ev.e1));
+            best = std::min(best, t);
         }
-        return 0;
-    };
-    const int rc = body();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (r) (void)hipFree(r);
-    if (q) (void)hipFree(q);
-    if (s) (void)hipStreamDestroy(s);
-    return rc;
+        us[wt] = 1e3 * best / reps;
+    }
+    return 0;
 }

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "foto_dct.h"
+#include "foto_devmem.h"
 #include "foto_devutil.h"
 #include "foto_reduce.h"
 #include "foto_spectral.h"
@@ -1300,7 +1301,7 @@ struct SpecImpl {
     int npend = 0;
     int sstep = 1;
     Tuning tn;                    // the knobs as the owning context read them (init's argument)
-    std::vector<void*> allocs;
+    DevArena mem;                 // every device block of the plan
     int nblocks = 0;
     double c0 = 0, c1 = 1;
     // Gauss-compressed CG (cg_mode 3, foto_gauss.inc); gauss_active: the solve in flight uses it
@@ -1328,13 +1329,9 @@ struct SpecImpl {
     // the solve done in its tail
     int late_plan() const { return ring ? 1 : 0; }
 
-    int alloc(size_t bytes, void** p) {
-        FOTO_HIP_CHECK(hipMalloc(p, bytes));
-        allocs.push_back(*p);
-        return 0;
-    }
+    int alloc(size_t bytes, void** p) { return mem.alloc(bytes, p); }
     ~SpecImpl() {
-        for (void* p : allocs) (void)hipFree(p);
+        mem.clear();   // (here, not as a member's destructor: the device blocks go before the pinned ones)
         if (hS) (void)hipHostFree(hS);
         if (hS2) (void)hipHostFree(hS2);
         for (GqState* h : hgq2)
@@ -1527,39 +1524,32 @@ static int gq_perm_lists(SpecImpl* P, const SpecTab& T, unsigned* perm, double* 
     const int64_t N = (int64_t)rows * T.Nx;
     k_gq_rowmu<<<(rows + 255) / 256, 256, 0, s>>>(T, rowmu);
     FOTO_HIP_CHECK(hipGetLastError());
+    DevArena scratch;   // (freed on every return)
     int* cnt = nullptr;
     const size_t ncnt = (size_t)GQ_NB * rows;
-    FOTO_HIP_CHECK(hipMalloc((void**)&cnt, sizeof(int) * ncnt));
-    int rc = 0;
+    FOTO_TRY(scratch.alloc_n(ncnt, &cnt));
     htot.assign(GQ_NB, 0);
     hfirst.assign(GQ_NB + 1, 0);
-    do {
-        if (hipMemsetAsync(cnt, 0, sizeof(int) * ncnt, s) != hipSuccess) { rc = -1; break; }
-        k_gq_perm_count<<<(rows + 255) / 256, 256, 0, s>>>(T, P->gq_bins, rowmu, 1.0 / P->c1, cnt);
-        k_gq_perm_scan<<<GQ_NB, 256, 0, s>>>(rows, cnt, tot_d);
-        if (hipMemcpyAsync(htot.data(), tot_d, sizeof(int) * GQ_NB, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) { rc = -1; break; }
-        int64_t acc = 0;
-        for (int bb = 0; bb < GQ_NB; ++bb) {
-            hfirst[bb] = (int)acc;
-            acc += htot[bb];
-        }
-        hfirst[GQ_NB] = (int)acc;
-        if (acc != N) {
-            set_error("gauss perm: %lld voxels binned, box has %lld", (long long)acc, (long long)N);
-            rc = -1;
-            break;
-        }
-        if (hipMemcpyAsync(first_d, hfirst.data(), sizeof(int) * (GQ_NB + 1), hipMemcpyHostToDevice, s) != hipSuccess) {
-            rc = -1;
-            break;
-        }
-        k_gq_perm_fill<<<(rows + 255) / 256, 256, 0, s>>>(T, P->gq_bins, rowmu, 1.0 / P->c1, cnt, first_d, perm);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) rc = -1;
-    } while (false);
-    (void)hipFree(cnt);
-    if (rc) set_error("gauss perm build failed");
-    return rc ? -1 : 0;
+    FOTO_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * ncnt, s));
+    k_gq_perm_count<<<(rows + 255) / 256, 256, 0, s>>>(T, P->gq_bins, rowmu, 1.0 / P->c1, cnt);
+    k_gq_perm_scan<<<GQ_NB, 256, 0, s>>>(rows, cnt, tot_d);
+    FOTO_HIP_CHECK(hipMemcpyAsync(htot.data(), tot_d, sizeof(int) * GQ_NB, hipMemcpyDeviceToHost, s));
+    FOTO_HIP_CHECK(hipStreamSynchronize(s));
+    int64_t acc = 0;
+    for (int bb = 0; bb < GQ_NB; ++bb) {
+        hfirst[bb] = (int)acc;
+        acc += htot[bb];
+    }
+    hfirst[GQ_NB] = (int)acc;
+    if (acc != N) {
+        set_error("gauss perm: %lld voxels binned, box has %lld", (long long)acc, (long long)N);
+        return FOTO_ERR_STATE;
+    }
+    FOTO_HIP_CHECK(hipMemcpyAsync(first_d, hfirst.data(), sizeof(int) * (GQ_NB + 1), hipMemcpyHostToDevice, s));
+    k_gq_perm_fill<<<(rows + 255) / 256, 256, 0, s>>>(T, P->gq_bins, rowmu, 1.0 / P->c1, cnt, first_d, perm);
+    FOTO_HIP_CHECK(hipGetLastError());
+    FOTO_HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
 }
 
 // The chunk list in dispatch order.  Neighbouring bins share the cache lines of b^ (a 16-voxel
@@ -1573,26 +1563,18 @@ static int gq_order_chunks(SpecImpl* P, std::vector<GqChunk>& ch, int rows, hipS
     const int nx = 8;
     const int n = (int)ch.size();
     if (n < 4 * nx) return 0;
-    void* b = nullptr;
-    GqChunk* dch = nullptr;
-    int* drow = nullptr;
-    FOTO_HIP_CHECK(hipMalloc(&b, sizeof(GqChunk) * n + sizeof(int) * n));
-    dch = (GqChunk*)b;
-    drow = (int*)(dch + n);
     std::vector<int> row(n);
-    int rc = 0;
-    if (hipMemcpyAsync(dch, ch.data(), sizeof(GqChunk) * n, hipMemcpyHostToDevice, s) != hipSuccess) rc = -1;
-    if (!rc) {
+    {
+        DevArena scratch;   // (freed on every return and before the host-side ordering)
+        void* b = nullptr;
+        FOTO_TRY(scratch.alloc(sizeof(GqChunk) * n + sizeof(int) * n, &b));
+        GqChunk* dch = (GqChunk*)b;
+        int* drow = (int*)(dch + n);
+        FOTO_HIP_CHECK(hipMemcpyAsync(dch, ch.data(), sizeof(GqChunk) * n, hipMemcpyHostToDevice, s));
         k_gq_chunk_rows<<<(n + 255) / 256, 256, 0, s>>>(dch, n, P->gq_permv, drow);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(row.data(), drow, sizeof(int) * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            rc = -1;
-    }
-    (void)hipFree(b);
-    if (rc) {
-        set_error("gauss chunk order: device step failed");
-        return FOTO_ERR_HIP;
+        FOTO_HIP_CHECK(hipGetLastError());
+        FOTO_HIP_CHECK(hipMemcpyAsync(row.data(), drow, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+        FOTO_HIP_CHECK(hipStreamSynchronize(s));
     }
     std::vector<std::vector<int>> L(nx);
     for (int c = 0; c < n; ++c) L[std::min(nx - 1, (int)((int64_t)row[c] * nx / std::max(1, rows)))].push_back(c);
@@ -1660,28 +1642,18 @@ static int gq_build_perm(SpecImpl* P, hipStream_t s) {
     TG.y0 = 0;
     TG.nyl = P->g.Ny;
     const int grows = P->g.Nt * P->g.Ny;
+    DevArena scratch;   // (freed on every return)
     unsigned* gperm = nullptr;
     double* growmu = nullptr;
     int* gidx = nullptr;
-    int rc = 0;
-    if (hipMalloc((void**)&gperm, sizeof(unsigned) * (size_t)grows * P->g.Nx) != hipSuccess ||
-        hipMalloc((void**)&growmu, sizeof(double) * grows) != hipSuccess ||
-        hipMalloc((void**)&gidx, sizeof(int) * (2 * GQ_NB + 1)) != hipSuccess) {
-        set_error("gauss exact bins: scratch allocation failed");
-        rc = -1;
-    }
-    if (!rc) rc = gq_perm_lists(P, TG, gperm, growmu, gidx, gidx + GQ_NB + 1, htot, hfirst, s);
-    if (!rc) {
-        k_gq_exact<<<GQ_NB / 64, 64, 0, s>>>(TG, gperm, gidx, gidx + GQ_NB + 1, growmu, 1.0 / P->c1, xmax, P->gq_exact);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-            set_error("gauss exact bins: kernel failed");
-            rc = -1;
-        }
-    }
-    if (gperm) (void)hipFree(gperm);
-    if (growmu) (void)hipFree(growmu);
-    if (gidx) (void)hipFree(gidx);
-    return rc ? -1 : 0;
+    FOTO_TRY(scratch.alloc_n((size_t)grows * P->g.Nx, &gperm));
+    FOTO_TRY(scratch.alloc_n((size_t)grows, &growmu));
+    FOTO_TRY(scratch.alloc_n((size_t)(2 * GQ_NB + 1), &gidx));
+    FOTO_TRY(gq_perm_lists(P, TG, gperm, growmu, gidx, gidx + GQ_NB + 1, htot, hfirst, s));
+    k_gq_exact<<<GQ_NB / 64, 64, 0, s>>>(TG, gperm, gidx, gidx + GQ_NB + 1, growmu, 1.0 / P->c1, xmax, P->gq_exact);
+    FOTO_HIP_CHECK(hipGetLastError());
+    FOTO_HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
 }
 
 SpectralPlan::~SpectralPlan() { delete (SpecImpl*)impl; }
