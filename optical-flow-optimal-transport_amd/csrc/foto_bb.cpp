@@ -135,7 +135,6 @@ struct foto_bb_ctx {
     std::vector<std::unique_ptr<Shard>> sh;   // local shards
     CGScal* hS = nullptr;                     // pinned host mirror of shard 0's CG scalars
     int last_cg = 0;
-    int last_passes = 0;   // s-step passes of the previous sharded spectral solve
     int have_phi = 0;
     // prox fused with the next RHS (k_prox_rhs); F in rv is then produced by the previous
     // outer iteration (f_ready), mu rotates through Shard::mu / nu (/ xi)
@@ -662,27 +661,14 @@ static int sharded_sstep(foto_bb_ctx* c, int* iters, int* info) {
     for (auto& sp : c->sh) FOTO_TRY(sp->spec->cg_begin(rtol, maxiter, kt, c->s));
     FOTO_TRY(allgather(c, [](Shard& s) { return s.spec->gath(); }, M));
     for (auto& sp : c->sh) FOTO_TRY(sp->spec->cg_plan(1, rtol, maxiter, c->s));
-    int passes = 0, done = 0, its = 0, planned = 0;
-    const int first = c->last_passes > 0 ? c->last_passes + 2 : 8;   // over-predict (see solve_s2)
-    while (true) {
-        const int chunk = (passes == 0) ? first : 2;
-        for (int j = 0; j < chunk; ++j, ++passes) {
-            for (auto& sp : c->sh) FOTO_TRY(sp->spec->cg_pass(rtol, maxiter, kt, c->s));
-            FOTO_TRY(allgather(c, [](Shard& s) { return s.spec->gath(); }, M));
-            for (auto& sp : c->sh) FOTO_TRY(sp->spec->cg_plan(0, rtol, maxiter, c->s));
-        }
-        FOTO_TRY(c->sh[0]->spec->poll(&done, &its, &planned, c->s));
-        if (done) break;
-        if (passes > maxiter + 4) {
-            set_error("sharded spectral CG did not terminate");
-            return FOTO_ERR_STATE;
-        }
-    }
-    *iters = its;
-    *info = (done == 1) ? 0 : maxiter;
-    c->last_passes = planned;
-    kt->discard_last(FOTO_K_SPEC, std::max(0, passes - planned) * (int)c->sh.size());   // no-op passes
-    return 0;
+    auto pass = [&]() -> int {
+        for (auto& sp : c->sh) FOTO_TRY(sp->spec->cg_pass(rtol, maxiter, kt, c->s));
+        FOTO_TRY(allgather(c, [](Shard& s) { return s.spec->gath(); }, M));
+        for (auto& sp : c->sh) FOTO_TRY(sp->spec->cg_plan(0, rtol, maxiter, c->s));
+        return 0;
+    };
+    // every shard's state is the same (same gathered moments): the first local shard's plan polls
+    return c->sh[0]->spec->sstep_passes(pass, (int)c->sh.size(), maxiter, iters, info, kt, c->s);
 }
 
 // the whole sharded solve, waiting for it on the host (FOTO_CG_DEFER=0, or the s-step CG)
@@ -725,27 +711,12 @@ static int cg_solve(foto_bb_ctx* c, int* iters, int* info) {
         return 0;
     }
     for (auto& sp : c->sh) FOTO_HIP_CHECK(hipMemsetAsync(sp->S, 0, sizeof(CGScal), c->s));
-    int k = 0;
     bool done = false;
-    const int first = c->last_cg > 4 ? c->last_cg - 3 : 6;
-    while (k < maxiter) {
-        int chunk = (k == 0) ? first : 2;
-        chunk = std::min(chunk, maxiter - k);
-        for (int j = 0; j < chunk; ++j, ++k) FOTO_TRY(cg_iteration(c, k));
-        FOTO_HIP_CHECK(hipMemcpyAsync(c->hS, c->sh[0]->S, sizeof(CGScal), hipMemcpyDeviceToHost, c->s));
-        FOTO_HIP_CHECK(hipStreamSynchronize(c->s));
-        if (c->hS->done) { done = true; break; }
-    }
-    if (done) {
-        *iters = c->hS->iters;
-        *info = 0;
-        if (*iters == 0)
-            for (auto& sp : c->sh)
-                FOTO_HIP_CHECK(hipMemsetAsync(sp->phi, 0, sizeof(double) * sp->g.nloc * sp->g.nxy, c->s));
-    } else {
-        *iters = maxiter;
-        *info = maxiter;
-    }
+    FOTO_TRY(cg_poll_chunks(c->last_cg > 4 ? c->last_cg - 3 : 6, maxiter, [&](int k) { return cg_iteration(c, k); },
+                            c->sh[0]->S, c->hS, c->s, &done, iters, info));
+    if (done && *iters == 0)
+        for (auto& sp : c->sh)
+            FOTO_HIP_CHECK(hipMemsetAsync(sp->phi, 0, sizeof(double) * sp->g.nloc * sp->g.nxy, c->s));
     c->last_cg = *iters;
     return 0;
 }
@@ -1544,7 +1515,6 @@ static int bb_reset(foto_bb_ctx* c, const RhoSrc& src) {
     }
     // the host side of the loop state, as a new context has it
     c->last_cg = 0;
-    c->last_passes = 0;
     c->have_phi = 0;
     c->f_ready = false;
     for (auto& sp : c->sh)

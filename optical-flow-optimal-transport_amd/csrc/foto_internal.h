@@ -97,6 +97,26 @@ struct CGScal {
     int pad[2];
 };
 
+// The host loop of a CG that takes one step per launch (the stencil CG of foto_bb.cpp, the
+// one-step spectral CG): step(k) enqueues iteration k; after the first `first` iterations, then
+// after every 2, the scalars S are copied to the pinned hS and the host waits for them.  Ends at
+// the done flag or at maxiter, with scipy's (iterations, info).
+template <class Step>
+int cg_poll_chunks(int first, int maxiter, Step&& step, const CGScal* S, CGScal* hS, hipStream_t s, bool* done,
+                   int* iters, int* info) {
+    *done = false;
+    for (int k = 0; k < maxiter && !*done;) {
+        const int chunk = std::min(k == 0 ? first : 2, maxiter - k);
+        for (int j = 0; j < chunk; ++j, ++k) FOTO_TRY(step(k));
+        FOTO_HIP_CHECK(hipMemcpyAsync(hS, S, sizeof(CGScal), hipMemcpyDeviceToHost, s));
+        FOTO_HIP_CHECK(hipStreamSynchronize(s));
+        *done = hS->done != 0;
+    }
+    *iters = *done ? hS->iters : maxiter;
+    *info = *done ? 0 : maxiter;
+    return 0;
+}
+
 // Per-shard reduction scratch: `partials` holds one value per block per quantity,
 // `ticket` is the last-block counter, `gath` holds one slot per rank (allgathered).
 struct RedBuf {

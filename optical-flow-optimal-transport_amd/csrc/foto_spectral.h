@@ -1,8 +1,12 @@
 // Spectral (DCT-II basis) CG for A = -r L_st + r eps I.  See foto_spectral.hip.
 #pragma once
+#include <functional>
+
 #include "foto_internal.h"
 
 namespace foto {
+
+struct SpecImpl;
 
 struct SpectralPlan {
     // rank / world: the shard's place in the time-slab decomposition (world > 1 needs
@@ -36,7 +40,11 @@ struct SpectralPlan {
     int cg_begin(double rtol, int maxiter, KTimer* kt, hipStream_t s);   // r^ = b^, moments -> gath
     int cg_pass(double rtol, int maxiter, KTimer* kt, hipStream_t s);    // planned CG steps, moments -> gath
     int cg_plan(int init, double rtol, int maxiter, hipStream_t s);      // after the all-gather
-    int poll(int* done, int* iters, int* passes, hipStream_t s);
+    // The s-step pass loop (after cg_begin, the all-gather and cg_plan(1)): pass() enqueues one pass --
+    // cg_pass on each of the `shards` local shards, the all-gather, cg_plan(0) -- and the plan
+    // launches passes in chunks, polling this shard's state in between, until the solve is done.
+    int sstep_passes(const std::function<int()>& pass, int shards, int maxiter, int* iters, int* info, KTimer* kt,
+                     hipStream_t s);
     int inv_t(KTimer* kt, hipStream_t s);                   // x^ = (b^ - r^)/lam, inverse t-DCT -> box_out
     // inverse y, x of planes [lo, hi) of scratch (the all-to-all's target) -> x; lo = -1 / hi =
     // nloc + 1: the halo plane below / above too (scratch and x halo-padded)
@@ -67,7 +75,7 @@ struct SpectralPlan {
     int reset(hipStream_t s);
 
     ~SpectralPlan();
-    void* impl = nullptr;
+    SpecImpl* impl = nullptr;
 };
 
 }  // namespace foto

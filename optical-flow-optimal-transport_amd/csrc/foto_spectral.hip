@@ -957,16 +957,27 @@ __global__ __launch_bounds__(S2_NTH) __attribute__((amdgpu_waves_per_eu(S2_WPE))
 constexpr bool ring_fits(int D) { return (RING_NW * D * RING_SLOT + RING_TAB) * 8 <= 150 * 1024; }
 static_assert(ring_fits(RING_D), "ring + tables exceed the LDS");
 
+// Run-time booleans to template arguments: with_bools(f, a, b) calls f(A, B) with A, B
+// std::true_type / std::false_type objects (A() is a constant expression), so a launcher names
+// its kernel once instead of once per combination.
+template <class F>
+static auto with_bools(F&& f) {
+    return f();
+}
+template <class F, class... B>
+static auto with_bools(F&& f, bool b, B... rest) {
+    return b ? with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+             : with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+
 // host launcher
 static hipError_t launch_s2_ring(const SpecTab& T, double* rh, double* ph, const double* bh, SStep* Sg, RedBuf rb,
                                  double rtol, int maxiter, double* gath, int rank, bool init, bool fuse,
                                  int nb = 256, hipStream_t s = 0, int world = 1) {
-#define FOTO_RL(I, F) \
-    k_spec_s2r<RING_D, I, F><<<nb, S2_NTH, 0, s>>>(T, rh, ph, bh, Sg, rb, rtol, maxiter, gath, rank, world)
-    if (init) { if (fuse) FOTO_RL(true, true); else FOTO_RL(true, false); }
-    else { if (fuse) FOTO_RL(false, true); else FOTO_RL(false, false); }
-#undef FOTO_RL
-    return hipGetLastError();
+    return with_bools([&](auto I, auto F) {
+        k_spec_s2r<RING_D, I(), F()><<<nb, S2_NTH, 0, s>>>(T, rh, ph, bh, Sg, rb, rtol, maxiter, gath, rank, world);
+        return hipGetLastError();
+    }, init, fuse);
 }
 
 // Multi-shard planning step (one wave): moments summed over ranks in rank order.
@@ -1347,170 +1358,28 @@ struct SpecImpl {
     bool vec() const { return (g.Nx % 2) == 0; }
     double nbox() const { return (double)g.Nt * nyl * g.Nx; }
 };
-static int gq_pub_clear(SpecImpl* P, hipStream_t s);
 
-static int reset_s2(SpecImpl* P, hipStream_t s);
+// the s-step state as a fresh plan has it (c0, c1 for the column kernels' fused INIT)
+static int reset_s2(SpecImpl* P, hipStream_t s) {
+    SStep h{};
+    h.c0 = P->c0;
+    h.c1 = P->c1;
+    h.gc0 = P->c0;
+    h.gc1 = P->c1;
+    h.ic0 = P->c0;   // the first solve's INIT moments: the whole spectrum
+    h.ic1 = P->c1;
+    h.flags = P->tn.sadapt ? 0 : 1;   // FOTO_SADAPT=0: whole-spectrum interval for every pass (A/B runs)
+    *P->hS2 = h;
+    FOTO_HIP_CHECK(hipMemcpyAsync(P->S2, P->hS2, sizeof(SStep), hipMemcpyHostToDevice, s));
+    FOTO_HIP_CHECK(hipStreamSynchronize(s));   // hS2 is reused by polling
+    return 0;
+}
 
-static int gq_build_perm(SpecImpl* P, hipStream_t s);
-
-int SpectralPlan::init(const Geo& g, int rank, int world, double r, double eps, int sstep, const Tuning& tn,
-                       hipStream_t s) {
-    // cg_mode 3: the Gauss-compressed CG, with the s-step machinery kept for the (rare) redo
-    const bool gauss = (sstep == 3);
-    if (gauss) sstep = 2;
-    if (sstep != 1 && sstep != 2) {
-        set_error("spectral CG: s-step must be 1 or 2");
-        return FOTO_ERR_ARG;
-    }
-    if (world > 1 && sstep != 2) {
-        set_error("sharded spectral CG needs cg_mode = 2 (s-step)");
-        return FOTO_ERR_ARG;
-    }
-    if (world > g.Ny) {
-        set_error("sharded spectral CG needs Ny >= world (rows are split over ranks)");
-        return FOTO_ERR_ARG;
-    }
-    if (!(eps > 0.0)) {
-        set_error("spectral CG needs reg_epsilon > 0 (x = (b - r) / lam)");
-        return FOTO_ERR_ARG;
-    }
-    auto* P = new SpecImpl();
-    impl = P;
-    P->sstep = sstep;
-    P->tn = tn;
-    P->g = g;
-    P->rank = rank;
-    P->world = world;
-    P->y0 = split_start_h(g.Ny, world, rank);
-    P->nyl = split_start_h(g.Ny, world, rank + 1) - P->y0;
-    P->r = r;
-    P->eps = eps;
-    const size_t NB = (size_t)g.Nt * P->nyl * g.Nx;          // spectral box
-    const size_t NS = (size_t)g.nloc * g.nxy;                // physical slab
-    void* b;
-    FOTO_TRY(P->alloc(NB * 8, &b)); P->bh = (double*)b;
-    FOTO_TRY(P->alloc(NB * 8, &b)); P->rh = (double*)b;
-    FOTO_TRY(P->alloc(NB * 8, &b)); P->ph = (double*)b;
-    FOTO_TRY(P->alloc(std::max(NB, NS) * 8, &b)); P->tmp = (double*)b;
-    if (world > 1) {
-        FOTO_TRY(P->alloc((NS + 2 * (size_t)g.nxy) * 8, &b)); P->tmpp = (double*)b + g.nxy;
-    }
-    std::vector<double> C, CT, mu;
-    // the n x n matrices only for an axis the FFT kernels do not take (dct_fft_axis's rule):
-    // 2 x 3.3 MB of host cosines and blocking copies per 640-axis saved at context creation
-    auto up = [&](int n, double** Cd, double** CTd, double** mud) -> int {
-        int m1, m2;
-        const bool fft = tn.dct_fft && n >= 64 && fft_factors(n, &m1, &m2);
-        if (fft) dct_eigen(n, mu);
-        else dct_matrix(n, C, CT, mu);
-        void* p;
-        if (!fft) {
-            FOTO_TRY(P->alloc(C.size() * 8, &p)); *Cd = (double*)p;
-            FOTO_TRY(P->alloc(CT.size() * 8, &p)); *CTd = (double*)p;
-            FOTO_HIP_CHECK(hipMemcpy(*Cd, C.data(), C.size() * 8, hipMemcpyHostToDevice));
-            FOTO_HIP_CHECK(hipMemcpy(*CTd, CT.data(), CT.size() * 8, hipMemcpyHostToDevice));
-        }
-        FOTO_TRY(P->alloc(mu.size() * 8, &p)); *mud = (double*)p;
-        FOTO_HIP_CHECK(hipMemcpy(*mud, mu.data(), mu.size() * 8, hipMemcpyHostToDevice));
-        return (int)0;
-    };
-    FOTO_TRY(up(g.Nx, &P->Cx, &P->CxT, &P->mx));
-    const double mx_max = mu.back();
-    FOTO_TRY(up(g.Ny, &P->Cy, &P->CyT, &P->my));
-    const double my_max = mu.back();
-    FOTO_TRY(up(g.Nt, &P->Ct, &P->CtT, &P->mt));
-    const double mt_max = mu.back();
-    auto upf = [&](int n, double** Fd) -> int {
-        int m1, m2;
-        if (!tn.dct_fft || !fft_factors(n, &m1, &m2)) return 0;   // (no table: dct_pass takes the GEMM kernels)
-        const std::vector<double> t = fft_table(n);
-        void* p;
-        FOTO_TRY(P->alloc(t.size() * 8, &p));
-        *Fd = (double*)p;
-        FOTO_HIP_CHECK(hipMemcpy(*Fd, t.data(), t.size() * 8, hipMemcpyHostToDevice));
-        return 0;
-    };
-    FOTO_TRY(upf(g.Nx, &P->Fx));
-    FOTO_TRY(upf(g.Ny, &P->Fy));
-    FOTO_TRY(upf(g.Nt, &P->Ft));
-    // Chebyshev scaling of lam: global spectrum bounds (identical on every rank)
-    const double lmin = r * eps, lmax = r * eps + r * (mt_max + my_max + mx_max);
-    P->c0 = 0.5 * (lmax + lmin);
-    P->c1 = 0.5 * (lmax - lmin);
-    const int rows = g.Nt * P->nyl;
-    const int ntiles = ((g.Nx + 127) / 128) * ((rows + 3) / 4);
-    P->nblocks = std::min(ntiles, 2048);
-    {
-        // one resident wave of blocks: blocks per CU at the pass kernel's occupancy x CUs
-        const int ntiles2 = ((g.Nx + 127) / 128) * ((rows + S2_NTH / 64 - 1) / (S2_NTH / 64));
-        int dev = 0, cus = 256, per_cu = 0;
-        FOTO_HIP_CHECK(hipGetDevice(&dev));
-        FOTO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        FOTO_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spec_s2<true, false, true>, S2_NTH, 0));
-        P->nblocks2 = std::min(ntiles2, std::max(1, per_cu) * cus);
-        // ring-fed pass (k_spec_s2r): one 1024-thread block per CU (its LDS ring), at most one
-        // block per 16 wave tiles; FOTO_RING=0 selects the register-fed pass (A/B runs)
-        P->ring = ring_ok(P->tab()) && tn.ring;
-        const int nwt = ((g.Nx + 127) / 128) * rows;
-        P->nb_ring = std::max(1, std::min({P->nblocks2, cus, (nwt + RING_NW - 1) / RING_NW}));
-    }
-    // FOTO_TCOL=0: t axis by dct_pass + separate INIT / xhat passes (A/B runs)
-    P->tcol = sstep == 2 && tcol_supported(g.Nt) && tn.tcol;
-    if (P->tcol) {
-        const int H = g.Nt / 2;
-        dct_matrix(g.Nt, C, CT, mu);
-        std::vector<double> ch((size_t)2 * H * H);
-        for (int m = 0; m < H; ++m)
-            for (int j = 0; j < H; ++j) {
-                ch[(size_t)m * H + j] = C[(size_t)(2 * m) * g.Nt + j];
-                ch[(size_t)H * H + m * H + j] = C[(size_t)(2 * m + 1) * g.Nt + j];
-            }
-        FOTO_TRY(P->alloc(ch.size() * 8, &b));
-        P->Cth = (double*)b;
-        FOTO_HIP_CHECK(hipMemcpy(P->Cth, ch.data(), ch.size() * 8, hipMemcpyHostToDevice));
-        const int per_block = tpair_size(g.Nt) ? TC_NTH / 2 : TC_NTH;   // wave pairs: 64 columns per 2 waves
-        P->tcol_nb = (int)(((int64_t)P->nyl * g.Nx + per_block - 1) / per_block);
-    }
-    const int cap = std::max({2 * P->nblocks, NACC * P->nblocks2, NMOM * P->tcol_nb});
-    FOTO_TRY(P->alloc(sizeof(double) * (cap + 8), &b));
-    P->rb.partials = (double*)b;
-    P->rb.ticket = (unsigned*)((double*)b + cap);
-    P->rb.cap = cap;
-    FOTO_HIP_CHECK(hipMemsetAsync(P->rb.ticket, 0, 8 * sizeof(double), s));
-    FOTO_TRY(P->alloc(sizeof(double) * std::max(4, NACC * world), &b)); P->gath = (double*)b;
-    FOTO_TRY(P->alloc(sizeof(CGScal), &b)); P->S = (CGScal*)b;
-    FOTO_HIP_CHECK(hipHostMalloc((void**)&P->hS, sizeof(CGScal)));
-    FOTO_TRY(P->alloc(sizeof(SStep), &b)); P->S2 = (SStep*)b;
-    FOTO_HIP_CHECK(hipHostMalloc((void**)&P->hS2, sizeof(SStep)));
-    FOTO_TRY(reset_s2(P, s));   // c0, c1 for the fused INIT (solve_tcol)
-    // the Gauss-compressed CG needs the bin-ordered voxel list; boxes its packing does not
-    // cover run the s-step CG (decided on the whole grid, so every rank agrees)
-    P->gauss = gauss && gq_perm_ok(g.Nx, g.Nt * g.Ny);
-    if (P->gauss) {
-        FOTO_TRY(P->alloc(sizeof(GqState), &b)); P->gq = (GqState*)b;
-        FOTO_HIP_CHECK(hipMemsetAsync(P->gq, 0, sizeof(GqState), s));
-        for (int k = 0; k < 2; ++k) {
-            FOTO_HIP_CHECK(hipHostMalloc((void**)&P->hgq2[k], sizeof(GqState), hipHostMallocMapped | hipHostMallocCoherent));
-            std::memset((void*)P->hgq2[k], 0, sizeof(GqState));
-            FOTO_HIP_CHECK(hipHostGetDevicePointer((void**)&P->dgq2[k], P->hgq2[k], 0));
-        }
-        FOTO_TRY(P->alloc(sizeof(GqNodes), &b)); P->gqn = (GqNodes*)b;
-        FOTO_TRY(P->alloc(sizeof(double) * GQ_HIST * world, &b)); P->gq_hist = (double*)b;
-        FOTO_TRY(P->alloc(GQ_TAB_BYTES, &b)); P->gq_tab = (double*)b;
-        // k_gq_xhat holds the whole table (128 KB) in dynamic LDS, beside its 10 KB bin tables
-        FOTO_HIP_CHECK(hipFuncSetAttribute((const void*)k_gq_xhat, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)GQ_TAB_BYTES));
-        FOTO_TRY(P->alloc(sizeof(GqBins), &b)); P->gq_bins = (GqBins*)b;
-        k_gq_bins<<<1, 256, 0, s>>>(P->gq_bins);
-        FOTO_TRY(P->alloc(sizeof(GqQCos), &b)); P->gq_qcos = (GqQCos*)b;
-        k_gq_qcos<<<1, 256, 0, s>>>(P->gq_qcos);
-        FOTO_TRY(P->alloc(sizeof(GqPub), &b)); P->gq_pub = (GqPub*)b;
-        FOTO_TRY(gq_pub_clear(P, s));
-        FOTO_HIP_CHECK(hipGetLastError());
-        FOTO_TRY(P->alloc(sizeof(GqExact), &b)); P->gq_exact = (GqExact*)b;
-        FOTO_TRY(gq_build_perm(P, s));
-        FOTO_HIP_CHECK(hipStreamSynchronize(s));
-    }
+// k_gq_cgtab's slots as a fresh plan has them: every (alpha, beta) NaN, kdone -1, ticket 0
+static int gq_pub_clear(SpecImpl* P, hipStream_t s) {
+    if (!P->gq_pub) return 0;
+    FOTO_HIP_CHECK(hipMemsetAsync(P->gq_pub, 0xff, sizeof(GqPub), s));   // (all-ones: NaN, -1)
+    FOTO_HIP_CHECK(hipMemsetAsync(&P->gq_pub->ticket, 0, sizeof(unsigned), s));
     return 0;
 }
 
@@ -1656,7 +1525,170 @@ static int gq_build_perm(SpecImpl* P, hipStream_t s) {
     return 0;
 }
 
-SpectralPlan::~SpectralPlan() { delete (SpecImpl*)impl; }
+int SpectralPlan::init(const Geo& g, int rank, int world, double r, double eps, int sstep, const Tuning& tn,
+                       hipStream_t s) {
+    // cg_mode 3: the Gauss-compressed CG, with the s-step machinery kept for the (rare) redo
+    const bool gauss = (sstep == 3);
+    if (gauss) sstep = 2;
+    if (sstep != 1 && sstep != 2) {
+        set_error("spectral CG: s-step must be 1 or 2");
+        return FOTO_ERR_ARG;
+    }
+    if (world > 1 && sstep != 2) {
+        set_error("sharded spectral CG needs cg_mode = 2 (s-step)");
+        return FOTO_ERR_ARG;
+    }
+    if (world > g.Ny) {
+        set_error("sharded spectral CG needs Ny >= world (rows are split over ranks)");
+        return FOTO_ERR_ARG;
+    }
+    if (!(eps > 0.0)) {
+        set_error("spectral CG needs reg_epsilon > 0 (x = (b - r) / lam)");
+        return FOTO_ERR_ARG;
+    }
+    auto* P = new SpecImpl();
+    impl = P;
+    P->sstep = sstep;
+    P->tn = tn;
+    P->g = g;
+    P->rank = rank;
+    P->world = world;
+    P->y0 = split_start_h(g.Ny, world, rank);
+    P->nyl = split_start_h(g.Ny, world, rank + 1) - P->y0;
+    P->r = r;
+    P->eps = eps;
+    const size_t NB = (size_t)g.Nt * P->nyl * g.Nx;          // spectral box
+    const size_t NS = (size_t)g.nloc * g.nxy;                // physical slab
+    void* b;
+    FOTO_TRY(P->alloc(NB * 8, &b)); P->bh = (double*)b;
+    FOTO_TRY(P->alloc(NB * 8, &b)); P->rh = (double*)b;
+    FOTO_TRY(P->alloc(NB * 8, &b)); P->ph = (double*)b;
+    FOTO_TRY(P->alloc(std::max(NB, NS) * 8, &b)); P->tmp = (double*)b;
+    if (world > 1) {
+        FOTO_TRY(P->alloc((NS + 2 * (size_t)g.nxy) * 8, &b)); P->tmpp = (double*)b + g.nxy;
+    }
+    std::vector<double> C, CT, mu;
+    // the n x n matrices only for an axis the FFT kernels do not take (dct_fft_axis's rule):
+    // 2 x 3.3 MB of host cosines and blocking copies per 640-axis saved at context creation
+    auto up = [&](int n, double** Cd, double** CTd, double** mud) -> int {
+        int m1, m2;
+        const bool fft = tn.dct_fft && n >= 64 && fft_factors(n, &m1, &m2);
+        if (fft) dct_eigen(n, mu);
+        else dct_matrix(n, C, CT, mu);
+        void* p;
+        if (!fft) {
+            FOTO_TRY(P->alloc(C.size() * 8, &p)); *Cd = (double*)p;
+            FOTO_TRY(P->alloc(CT.size() * 8, &p)); *CTd = (double*)p;
+            FOTO_HIP_CHECK(hipMemcpy(*Cd, C.data(), C.size() * 8, hipMemcpyHostToDevice));
+            FOTO_HIP_CHECK(hipMemcpy(*CTd, CT.data(), CT.size() * 8, hipMemcpyHostToDevice));
+        }
+        FOTO_TRY(P->alloc(mu.size() * 8, &p)); *mud = (double*)p;
+        FOTO_HIP_CHECK(hipMemcpy(*mud, mu.data(), mu.size() * 8, hipMemcpyHostToDevice));
+        return (int)0;
+    };
+    FOTO_TRY(up(g.Nx, &P->Cx, &P->CxT, &P->mx));
+    const double mx_max = mu.back();
+    FOTO_TRY(up(g.Ny, &P->Cy, &P->CyT, &P->my));
+    const double my_max = mu.back();
+    FOTO_TRY(up(g.Nt, &P->Ct, &P->CtT, &P->mt));
+    const double mt_max = mu.back();
+    auto upf = [&](int n, double** Fd) -> int {
+        int m1, m2;
+        if (!tn.dct_fft || !fft_factors(n, &m1, &m2)) return 0;   // (no table: dct_pass takes the GEMM kernels)
+        const std::vector<double> t = fft_table(n);
+        void* p;
+        FOTO_TRY(P->alloc(t.size() * 8, &p));
+        *Fd = (double*)p;
+        FOTO_HIP_CHECK(hipMemcpy(*Fd, t.data(), t.size() * 8, hipMemcpyHostToDevice));
+        return 0;
+    };
+    FOTO_TRY(upf(g.Nx, &P->Fx));
+    FOTO_TRY(upf(g.Ny, &P->Fy));
+    FOTO_TRY(upf(g.Nt, &P->Ft));
+    // Chebyshev scaling of lam: global spectrum bounds (identical on every rank)
+    const double lmin = r * eps, lmax = r * eps + r * (mt_max + my_max + mx_max);
+    P->c0 = 0.5 * (lmax + lmin);
+    P->c1 = 0.5 * (lmax - lmin);
+    const int rows = g.Nt * P->nyl;
+    const int ntiles = ((g.Nx + 127) / 128) * ((rows + 3) / 4);
+    P->nblocks = std::min(ntiles, 2048);
+    {
+        // one resident wave of blocks: blocks per CU at the pass kernel's occupancy x CUs
+        const int ntiles2 = ((g.Nx + 127) / 128) * ((rows + S2_NTH / 64 - 1) / (S2_NTH / 64));
+        int dev = 0, cus = 256, per_cu = 0;
+        FOTO_HIP_CHECK(hipGetDevice(&dev));
+        FOTO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        FOTO_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spec_s2<true, false, true>, S2_NTH, 0));
+        P->nblocks2 = std::min(ntiles2, std::max(1, per_cu) * cus);
+        // ring-fed pass (k_spec_s2r): one 1024-thread block per CU (its LDS ring), at most one
+        // block per 16 wave tiles; FOTO_RING=0 selects the register-fed pass (A/B runs)
+        P->ring = ring_ok(P->tab()) && tn.ring;
+        const int nwt = ((g.Nx + 127) / 128) * rows;
+        P->nb_ring = std::max(1, std::min({P->nblocks2, cus, (nwt + RING_NW - 1) / RING_NW}));
+    }
+    // FOTO_TCOL=0: t axis by dct_pass + separate INIT / xhat passes (A/B runs)
+    P->tcol = sstep == 2 && tcol_supported(g.Nt) && tn.tcol;
+    if (P->tcol) {
+        const int H = g.Nt / 2;
+        dct_matrix(g.Nt, C, CT, mu);
+        std::vector<double> ch((size_t)2 * H * H);
+        for (int m = 0; m < H; ++m)
+            for (int j = 0; j < H; ++j) {
+                ch[(size_t)m * H + j] = C[(size_t)(2 * m) * g.Nt + j];
+                ch[(size_t)H * H + m * H + j] = C[(size_t)(2 * m + 1) * g.Nt + j];
+            }
+        FOTO_TRY(P->alloc(ch.size() * 8, &b));
+        P->Cth = (double*)b;
+        FOTO_HIP_CHECK(hipMemcpy(P->Cth, ch.data(), ch.size() * 8, hipMemcpyHostToDevice));
+        const int per_block = tpair_size(g.Nt) ? TC_NTH / 2 : TC_NTH;   // wave pairs: 64 columns per 2 waves
+        P->tcol_nb = (int)(((int64_t)P->nyl * g.Nx + per_block - 1) / per_block);
+    }
+    const int cap = std::max({2 * P->nblocks, NACC * P->nblocks2, NMOM * P->tcol_nb});
+    FOTO_TRY(P->alloc(sizeof(double) * (cap + 8), &b));
+    P->rb.partials = (double*)b;
+    P->rb.ticket = (unsigned*)((double*)b + cap);
+    P->rb.cap = cap;
+    FOTO_HIP_CHECK(hipMemsetAsync(P->rb.ticket, 0, 8 * sizeof(double), s));
+    FOTO_TRY(P->alloc(sizeof(double) * std::max(4, NACC * world), &b)); P->gath = (double*)b;
+    FOTO_TRY(P->alloc(sizeof(CGScal), &b)); P->S = (CGScal*)b;
+    FOTO_HIP_CHECK(hipHostMalloc((void**)&P->hS, sizeof(CGScal)));
+    FOTO_TRY(P->alloc(sizeof(SStep), &b)); P->S2 = (SStep*)b;
+    FOTO_HIP_CHECK(hipHostMalloc((void**)&P->hS2, sizeof(SStep)));
+    FOTO_TRY(reset_s2(P, s));
+    // the Gauss-compressed CG needs the bin-ordered voxel list; boxes its packing does not
+    // cover run the s-step CG (decided on the whole grid, so every rank agrees)
+    P->gauss = gauss && gq_perm_ok(g.Nx, g.Nt * g.Ny);
+    if (P->gauss) {
+        FOTO_TRY(P->alloc(sizeof(GqState), &b)); P->gq = (GqState*)b;
+        FOTO_HIP_CHECK(hipMemsetAsync(P->gq, 0, sizeof(GqState), s));
+        for (int k = 0; k < 2; ++k) {
+            FOTO_HIP_CHECK(hipHostMalloc((void**)&P->hgq2[k], sizeof(GqState), hipHostMallocMapped | hipHostMallocCoherent));
+            std::memset((void*)P->hgq2[k], 0, sizeof(GqState));
+            FOTO_HIP_CHECK(hipHostGetDevicePointer((void**)&P->dgq2[k], P->hgq2[k], 0));
+        }
+        FOTO_TRY(P->alloc(sizeof(GqNodes), &b)); P->gqn = (GqNodes*)b;
+        FOTO_TRY(P->alloc(sizeof(double) * GQ_HIST * world, &b)); P->gq_hist = (double*)b;
+        FOTO_TRY(P->alloc(GQ_TAB_BYTES, &b)); P->gq_tab = (double*)b;
+        // k_gq_xhat holds the whole table (128 KB) in dynamic LDS, beside its 10 KB bin tables
+        FOTO_HIP_CHECK(hipFuncSetAttribute((const void*)k_gq_xhat, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)GQ_TAB_BYTES));
+        FOTO_TRY(P->alloc(sizeof(GqBins), &b)); P->gq_bins = (GqBins*)b;
+        k_gq_bins<<<1, 256, 0, s>>>(P->gq_bins);
+        FOTO_TRY(P->alloc(sizeof(GqQCos), &b)); P->gq_qcos = (GqQCos*)b;
+        k_gq_qcos<<<1, 256, 0, s>>>(P->gq_qcos);
+        FOTO_TRY(P->alloc(sizeof(GqPub), &b)); P->gq_pub = (GqPub*)b;
+        FOTO_TRY(gq_pub_clear(P, s));
+        FOTO_HIP_CHECK(hipGetLastError());
+        FOTO_TRY(P->alloc(sizeof(GqExact), &b)); P->gq_exact = (GqExact*)b;
+        FOTO_TRY(gq_build_perm(P, s));
+        FOTO_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
+SpectralPlan::~SpectralPlan() { delete impl; }
+
+// ---------------------------------------------------------------------------- launchers
 
 // one axis of [outer][n][inner]: FFT kernels where the length has an instantiation, GEMM otherwise
 static hipError_t dct_pass(const SpecImpl* P, int axis, bool inv, int outer, int inner, const double* in, double* out,
@@ -1669,119 +1701,44 @@ static hipError_t dct_pass(const SpecImpl* P, int axis, bool inv, int outer, int
     return dct_axis(outer, n, inner, C, in, out, s);
 }
 
-// 3-D transforms of a single shard: forward = (Ct (x) Cy (x) Cx), inverse = transpose.
-static int forward3(SpecImpl* P, double* in, double* scratch, double* out, KTimer* kt, hipStream_t s) {
-    const Geo& g = P->g;
-    const double N = (double)g.Nt * (double)g.nxy;
-    hipEvent_t e = kt ? kt->start(s) : nullptr;
-    // in -x-> scratch -y-> in -t-> out   (in is clobbered)
-    FOTO_HIP_CHECK(dct_pass(P, 0, false, g.Nt * g.Ny, 1, in, scratch, s));
-    FOTO_HIP_CHECK(dct_pass(P, 1, false, g.Nt, g.Nx, scratch, in, s));
-    FOTO_HIP_CHECK(dct_pass(P, 2, false, 1, (int)g.nxy, in, out, s));
-    if (kt) kt->stop(e, s, FOTO_K_DCT, 6.0 * 8.0 * N);
-    return 0;
-}
-
-static int inverse3(SpecImpl* P, double* in, double* scratch, double* out, KTimer* kt, hipStream_t s) {
-    const Geo& g = P->g;
-    const double N = (double)g.Nt * (double)g.nxy;
-    hipEvent_t e = kt ? kt->start(s) : nullptr;
-    // in -t-> scratch -y-> in -x-> out   (in is clobbered)
-    FOTO_HIP_CHECK(dct_pass(P, 2, true, 1, (int)g.nxy, in, scratch, s));
-    FOTO_HIP_CHECK(dct_pass(P, 1, true, g.Nt, g.Nx, scratch, in, s));
-    FOTO_HIP_CHECK(dct_pass(P, 0, true, g.Nt * g.Ny, 1, in, out, s));
-    if (kt) kt->stop(e, s, FOTO_K_DCT, 6.0 * 8.0 * N);
-    return 0;
-}
-
-static hipError_t launch_s2(SpecImpl* P, bool init, double rtol, int maxiter, double* gath, hipStream_t s) {
+// One s-step pass (init: r^ = b^ and r_0's moments).  Single shard: the pass plans the next one
+// itself; sharded: its moments go to gath for the all-gather and cg_plan -- except the working
+// ring passes, which plan at their start from the moments gathered from all `world` ranks (LATE).
+static hipError_t launch_s2(SpecImpl* P, bool init, double rtol, int maxiter, hipStream_t s) {
     const SpecTab T = P->tab();
-    const int nb = P->nblocks2;
-    // gath == nullptr: single shard, the pass plans itself; otherwise the moments go to gath
-    // for the all-gather and cg_plan
-    const bool fuse = (gath == nullptr);
-    double* gw = gath ? gath : P->gath;
+    const bool fuse = P->world == 1;
     if (P->ring)
-        return launch_s2_ring(T, P->rh, P->ph, P->bh, P->S2, P->rb, rtol, maxiter, gw, P->rank, init, fuse,
-                              P->nb_ring, s);
-#define FOTO_S2_LAUNCH(V, I, F) \
-    k_spec_s2<V, I, F><<<nb, S2_NTH, 0, s>>>(T, P->rh, P->ph, P->bh, P->S2, P->rb, rtol, maxiter, gw, P->rank)
-    if (P->vec()) {
-        if (init) { if (fuse) FOTO_S2_LAUNCH(true, true, true); else FOTO_S2_LAUNCH(true, true, false); }
-        else { if (fuse) FOTO_S2_LAUNCH(true, false, true); else FOTO_S2_LAUNCH(true, false, false); }
-    } else {
-        if (init) { if (fuse) FOTO_S2_LAUNCH(false, true, true); else FOTO_S2_LAUNCH(false, true, false); }
-        else { if (fuse) FOTO_S2_LAUNCH(false, false, true); else FOTO_S2_LAUNCH(false, false, false); }
-    }
-#undef FOTO_S2_LAUNCH
-    return hipGetLastError();
+        return launch_s2_ring(T, P->rh, P->ph, P->bh, P->S2, P->rb, rtol, maxiter, P->gath, P->rank, init,
+                              fuse || !init, P->nb_ring, s, init ? 1 : P->world);
+    return with_bools([&](auto V, auto I, auto F) {
+        k_spec_s2<V(), I(), F()><<<P->nblocks2, S2_NTH, 0, s>>>(T, P->rh, P->ph, P->bh, P->S2, P->rb, rtol, maxiter,
+                                                                 P->gath, P->rank);
+        return hipGetLastError();
+    }, P->vec(), init, fuse);
 }
 
-static int reset_s2(SpecImpl* P, hipStream_t s) {
-    SStep h{};
-    h.c0 = P->c0;
-    h.c1 = P->c1;
-    h.gc0 = P->c0;
-    h.gc1 = P->c1;
-    h.ic0 = P->c0;   // the first solve's INIT moments: the whole spectrum
-    h.ic1 = P->c1;
-    h.flags = P->tn.sadapt ? 0 : 1;   // FOTO_SADAPT=0: whole-spectrum interval for every pass (A/B runs)
-    *P->hS2 = h;
-    FOTO_HIP_CHECK(hipMemcpyAsync(P->S2, P->hS2, sizeof(SStep), hipMemcpyHostToDevice, s));
-    FOTO_HIP_CHECK(hipStreamSynchronize(s));   // hS2 is reused by polling
-    return 0;
+// the one-step CG's r^ = b^ and iteration k
+static hipError_t launch_init(SpecImpl* P, hipStream_t s) {
+    return with_bools([&](auto V) {
+        k_spec_init<V()><<<P->nblocks, NT, 0, s>>>(P->tab(), P->bh, P->rh, P->rb, P->gath);
+        return hipGetLastError();
+    }, P->vec());
+}
+static hipError_t launch_cg(SpecImpl* P, int k, double rtol, hipStream_t s) {
+    return with_bools([&](auto V) {
+        k_spec_cg<V()><<<P->nblocks, NT, 0, s>>>(P->tab(), k, P->rh, P->ph, P->S, P->rb, P->gath, rtol);
+        return hipGetLastError();
+    }, P->vec());
 }
 
-// init_done: the fused t-axis kernel already reset the state, took r_0's moments and planned
-static int solve_s2(SpecImpl* P, double rtol, int maxiter, int predicted, int* iters, int* info, KTimer* kt,
-                    hipStream_t s, bool init_done = false) {
-    const double N = P->nbox();
-    if (!init_done) {
-        hipEvent_t e = kt ? kt->start(s) : nullptr;
-        FOTO_HIP_CHECK(launch_s2(P, true, rtol, maxiter, nullptr, s));
-        if (kt) kt->stop(e, s, FOTO_K_SPEC, 16.0 * N);
-    }
-    // Host polls the done flag between chunks.  A poll idles the GPU for the host's wake-up
-    // (measured up to ~1 ms per solve when polling every pass), while a pass launched after
-    // the solve finished exits in a few us -- so over-predict: the first chunk is the previous
-    // solve's pass count + 2, then chunks of 2.
-    int passes = 0;
-    (void)predicted;
-    const int first = P->last_passes > 0 ? P->last_passes + 2 : 8;
-    while (true) {
-        const int chunk = (passes == 0) ? first : 2;
-        for (int j = 0; j < chunk; ++j, ++passes) {
-            hipEvent_t e = kt ? kt->start(s) : nullptr;
-            FOTO_HIP_CHECK(launch_s2(P, false, rtol, maxiter, nullptr, s));
-            if (kt) kt->stop(e, s, FOTO_K_SPEC, 32.0 * N);
-        }
-        FOTO_HIP_CHECK(hipMemcpyAsync(P->hS2, P->S2, sizeof(SStep), hipMemcpyDeviceToHost, s));
-        FOTO_HIP_CHECK(hipStreamSynchronize(s));
-        if (P->hS2->done) break;
-        if (passes > maxiter + 4) {
-            set_error("spectral s-step CG did not terminate");
-            return FOTO_ERR_STATE;
-        }
-    }
-    *iters = P->hS2->iters;
-    *info = (P->hS2->done == 1) ? 0 : maxiter;
-    P->last_passes = P->hS2->passes;
-    // S.passes counts the plans (INIT's and every working pass's but the last), i.e. the
-    // passes that applied steps; the launches beyond them exited at once -- keep them out of
-    // the per-kernel timing
-    if (kt) kt->discard_last(FOTO_K_SPEC, std::max(0, passes - P->hS2->passes));
-    return 0;
+// x^ = (b^ - r^) / lam into a box buffer
+static hipError_t launch_xhat(SpecImpl* P, double* out, hipStream_t s) {
+    return with_bools([&](auto V) {
+        k_spec_xhat<V()><<<P->nblocks, NT, 0, s>>>(P->tab(), P->bh, P->rh, out);
+        return hipGetLastError();
+    }, P->vec());
 }
 
-static hipError_t launch_xhat(SpecImpl* P, hipStream_t s) {
-    const SpecTab T = P->tab();
-    if (P->vec()) k_spec_xhat<true><<<P->nblocks, NT, 0, s>>>(T, P->bh, P->rh, P->tmp);
-    else k_spec_xhat<false><<<P->nblocks, NT, 0, s>>>(T, P->bh, P->rh, P->tmp);
-    return hipGetLastError();
-}
-
-// plan (forward): single shard, the kernel plans the first pass; sharded, it leaves this rank's INIT
-// moments in gath for the all-gather
 // x^ = Q(lam) b^ (the Gauss-compressed CG's solution table) into a box buffer: persistent
 // 1024-thread blocks, the table in LDS.  Sized for the whole table (32 rows, 128 KB) one block
 // fits a CU; sized for the first GQ_XQL = 17 rows (68 KB, what K <= ~200 needs; the table
@@ -1799,54 +1756,192 @@ static hipError_t gq_xhat(SpecImpl* P, double* out, hipStream_t s) {
     return hipGetLastError();
 }
 
-// inv: x^ = (b^ - r^)/lam (s-step) or, with P->gauss, Q(lam) b^ from the Gauss-compressed CG's table
+// The t-axis column kernels.  Forward (in -> b^) in one of the TC_* modes: TC_PLAN, a single
+// shard, the kernel plans the first pass; TC_GATH, sharded, it leaves this rank's INIT moments in
+// gath for the all-gather; TC_PLAIN, b^ only.  Inverse (-> out): in == nullptr forms
+// x^ = (b^ - r^)/lam in the kernel (s-step); otherwise in holds x^ itself (gq_xhat's output).
 static hipError_t launch_tcol(SpecImpl* P, bool inv, const double* in, double* out, double rtol, int maxiter,
                               hipStream_t s, int mode = TC_PLAN) {
     const SpecTab T = P->tab();
     const int nb = P->tcol_nb;
-    const bool gq = inv && P->gauss_active;
-    if (gq) {   // x^ -> rh, then the plain inverse below
-        const hipError_t e = gq_xhat(P, P->rh, s);
-        if (e != hipSuccess) return e;
+#define FOTO_TCOL_FWD(NN, FWD, M) \
+    FWD<NN, M><<<nb, TC_NTH, 0, s>>>(T, P->Cth, in, P->bh, P->S2, P->rb, rtol, maxiter, P->gath, P->rank)
+#define FOTO_TCOL_LAUNCH(NN, FWD, INV)                                                                  \
+    if (P->g.Nt == NN) {                                                                                \
+        if (inv && in) INV<NN, true><<<nb, TC_NTH, 0, s>>>(T, P->Cth, in, nullptr, nullptr, out);       \
+        else if (inv) INV<NN><<<nb, TC_NTH, 0, s>>>(T, P->Cth, P->bh, P->rh, P->S2, out);               \
+        else if (mode == TC_PLAN) FOTO_TCOL_FWD(NN, FWD, TC_PLAN);                                      \
+        else if (mode == TC_GATH) FOTO_TCOL_FWD(NN, FWD, TC_GATH);                                      \
+        else FOTO_TCOL_FWD(NN, FWD, TC_PLAIN);                                                          \
+        return hipGetLastError();                                                                       \
     }
-#define FOTO_TCOL_FWD(NN, K, M) K<NN, M><<<nb, TC_NTH, 0, s>>>(T, P->Cth, in, P->bh, P->S2, P->rb, rtol, maxiter, \
-                                                                P->gath, P->rank)
-#define FOTO_TCOL_LAUNCH(NN)                                                                                       \
-    if (P->g.Nt == NN) {                                                                                           \
-        if (gq) k_dct_t_inv_xhat<NN, true><<<nb, TC_NTH, 0, s>>>(T, P->Cth, P->rh, nullptr, nullptr, out);         \
-        else if (inv) k_dct_t_inv_xhat<NN><<<nb, TC_NTH, 0, s>>>(T, P->Cth, P->bh, P->rh, P->S2, out);             \
-        else if (mode == TC_PLAN) FOTO_TCOL_FWD(NN, k_dct_t_fwd_init, TC_PLAN);                                    \
-        else if (mode == TC_GATH) FOTO_TCOL_FWD(NN, k_dct_t_fwd_init, TC_GATH);                                    \
-        else FOTO_TCOL_FWD(NN, k_dct_t_fwd_init, TC_PLAIN);                                                        \
-        return hipGetLastError();                                                                                  \
-    }
-    FOTO_TCOL_SIZES(FOTO_TCOL_LAUNCH)
+#define FOTO_TCOL_ONE(NN) FOTO_TCOL_LAUNCH(NN, k_dct_t_fwd_init, k_dct_t_inv_xhat)
+#define FOTO_TCOL_PAIR(NN) FOTO_TCOL_LAUNCH(NN, k_dct_tp_fwd_init, k_dct_tp_inv_xhat)
+    FOTO_TCOL_SIZES(FOTO_TCOL_ONE)
+    FOTO_TPAIR_SIZES(FOTO_TCOL_PAIR)
+#undef FOTO_TCOL_PAIR
+#undef FOTO_TCOL_ONE
 #undef FOTO_TCOL_LAUNCH
-#define FOTO_TPAIR_LAUNCH(NN)                                                                                      \
-    if (P->g.Nt == NN) {                                                                                           \
-        if (gq) k_dct_tp_inv_xhat<NN, true><<<nb, TC_NTH, 0, s>>>(T, P->Cth, P->rh, nullptr, nullptr, out);        \
-        else if (inv) k_dct_tp_inv_xhat<NN><<<nb, TC_NTH, 0, s>>>(T, P->Cth, P->bh, P->rh, P->S2, out);            \
-        else if (mode == TC_PLAN) FOTO_TCOL_FWD(NN, k_dct_tp_fwd_init, TC_PLAN);                                   \
-        else if (mode == TC_GATH) FOTO_TCOL_FWD(NN, k_dct_tp_fwd_init, TC_GATH);                                   \
-        else FOTO_TCOL_FWD(NN, k_dct_tp_fwd_init, TC_PLAIN);                                                       \
-        return hipGetLastError();                                                                                  \
-    }
-    FOTO_TPAIR_SIZES(FOTO_TPAIR_LAUNCH)
-#undef FOTO_TPAIR_LAUNCH
 #undef FOTO_TCOL_FWD
     return hipErrorNotSupported;
 }
 
-// (b^, r^) -t(+xhat)-> b -y-> tmp -x-> x
-static int tcol_inverse(SpecImpl* P, double* b, double* x, double rtol, int maxiter, KTimer* kt, hipStream_t s) {
+// ---------------------------------------------------------------------------- the transform chain
+// forward = (Ct (x) Cy (x) Cx): x and y over a range of physical planes, then t over the spectral
+// box; inverse = transpose: x^, t^-1 over the box, then y^-1 and x^-1 over planes.  The four
+// stages below are the only places that launch a transform.  Which buffers a stage reads and
+// writes is the caller's route (a single shard's s-step solve may clobber b, the Gauss CG's must
+// not; a shard's planes pass through the all-to-all between the stages).
+//
+// A Span is one KTimer interval of class cls around the stages run under it; each stage adds the
+// bytes it moves (8 per element read or written).
+struct Span {
+    KTimer* kt;
+    hipStream_t s;
+    int cls;
+    hipEvent_t e;
+    double bytes = 0.0;
+    Span(KTimer* kt, hipStream_t s, int cls) : kt(kt), s(s), cls(cls), e(kt ? kt->start(s) : nullptr) {}
+    int close() {
+        if (kt) kt->stop(e, s, cls, bytes);
+        return 0;
+    }
+};
+
+// np planes: src -x-> mid -y-> dst
+static int chain_fwd_xy(SpecImpl* P, Span& sp, int np, const double* src, double* mid, double* dst) {
     const Geo& g = P->g;
-    const double N = (double)g.Nt * (double)g.nxy;
-    hipEvent_t e = kt ? kt->start(s) : nullptr;
-    FOTO_HIP_CHECK(launch_tcol(P, true, nullptr, b, rtol, maxiter, s));
-    FOTO_HIP_CHECK(dct_pass(P, 1, true, g.Nt, g.Nx, b, P->tmp, s));
-    FOTO_HIP_CHECK(dct_pass(P, 0, true, g.Nt * g.Ny, 1, P->tmp, x, s));
-    if (kt) kt->stop(e, s, FOTO_K_DCT, 7.0 * 8.0 * N);
+    FOTO_HIP_CHECK(dct_pass(P, 0, false, np * g.Ny, 1, src, mid, sp.s));
+    FOTO_HIP_CHECK(dct_pass(P, 1, false, np, g.Nx, mid, dst, sp.s));
+    sp.bytes += 4.0 * 8.0 * (double)np * (double)g.nxy;
     return 0;
+}
+
+// box src -t-> b^: the column kernel in the given TC_* mode where the plan has one
+static int chain_fwd_t(SpecImpl* P, Span& sp, int mode, const double* src, double rtol, int maxiter) {
+    if (P->tcol) FOTO_HIP_CHECK(launch_tcol(P, false, src, nullptr, rtol, maxiter, sp.s, mode));
+    else FOTO_HIP_CHECK(dct_pass(P, 2, false, 1, P->nyl * P->g.Nx, src, P->bh, sp.s));
+    sp.bytes += 2.0 * 8.0 * P->nbox();
+    return 0;
+}
+
+// x^ -t^-1-> box out.  x^ is the s-step CG's (b^ - r^)/lam, the Gauss CG's Q(lam) b^, or already
+// in xh.  The column kernel forms the s-step's x^ itself; every other x^ goes through xh.
+enum XHat { XH_NONE, XH_SSTEP, XH_GAUSS };
+static int chain_inv_t(SpecImpl* P, Span& sp, XHat src, double* xh, double* out) {
+    if (src == XH_GAUSS) FOTO_HIP_CHECK(gq_xhat(P, xh, sp.s));
+    else if (src == XH_SSTEP && !P->tcol) FOTO_HIP_CHECK(launch_xhat(P, xh, sp.s));
+    if (P->tcol) FOTO_HIP_CHECK(launch_tcol(P, true, src == XH_SSTEP ? nullptr : xh, out, 0.0, 0, sp.s));
+    else FOTO_HIP_CHECK(dct_pass(P, 2, true, 1, P->nyl * P->g.Nx, xh, out, sp.s));
+    sp.bytes += (P->tcol ? 3.0 : 2.0) * 8.0 * P->nbox();
+    return 0;
+}
+
+// np planes: src -y^-1-> mid -x^-1-> dst
+static int chain_inv_yx(SpecImpl* P, Span& sp, int np, const double* src, double* mid, double* dst) {
+    const Geo& g = P->g;
+    FOTO_HIP_CHECK(dct_pass(P, 1, true, np, g.Nx, src, mid, sp.s));
+    FOTO_HIP_CHECK(dct_pass(P, 0, true, np * g.Ny, 1, mid, dst, sp.s));
+    sp.bytes += 4.0 * 8.0 * (double)np * (double)g.nxy;
+    return 0;
+}
+
+// single shard: b (physical) -x-> tmp -y-> mid -t-> b^
+static int forward(SpecImpl* P, const double* b, double* mid, int mode, double rtol, int maxiter, KTimer* kt,
+                   hipStream_t s) {
+    Span sp(kt, s, FOTO_K_DCT);
+    FOTO_TRY(chain_fwd_xy(P, sp, P->g.Nt, b, P->tmp, mid));
+    FOTO_TRY(chain_fwd_t(P, sp, mode, mid, rtol, maxiter));
+    return sp.close();
+}
+
+// single shard: x^ -t^-1-> tb -y^-1-> mid -x^-1-> x (physical)
+static int inverse(SpecImpl* P, XHat src, double* xh, double* tb, double* mid, double* x, KTimer* kt, hipStream_t s) {
+    Span sp(kt, s, FOTO_K_DCT);
+    FOTO_TRY(chain_inv_t(P, sp, src, xh, tb));
+    // (bytes_k as it has been reported: here k_gq_xhat's read of b^ counts without the column
+    // kernel too, which the sharded inv_t does not do)
+    if (src == XH_GAUSS && !P->tcol) sp.bytes += 8.0 * P->nbox();
+    FOTO_TRY(chain_inv_yx(P, sp, P->g.Nt, tb, mid, x));
+    return sp.close();
+}
+
+// single shard, after the s-step or the one-step CG: (b^, r^) -> x with b as scratch.  Without
+// the column kernels k_spec_xhat runs ahead of the timed chain.
+static int inverse_sstep(SpecImpl* P, double* b, double* x, KTimer* kt, hipStream_t s) {
+    if (!P->tcol) FOTO_HIP_CHECK(launch_xhat(P, P->tmp, s));
+    return inverse(P, P->tcol ? XH_SSTEP : XH_NONE, P->tmp, b, P->tmp, x, kt, s);
+}
+
+// ---------------------------------------------------------------------------- s-step and one-step CG (host)
+
+static int s2_launch(SpecImpl* P, bool init, double rtol, int maxiter, KTimer* kt, hipStream_t s) {
+    hipEvent_t e = kt ? kt->start(s) : nullptr;
+    FOTO_HIP_CHECK(launch_s2(P, init, rtol, maxiter, s));
+    if (kt) kt->stop(e, s, FOTO_K_SPEC, (init ? 16.0 : 32.0) * P->nbox());
+    return 0;
+}
+
+// n passes and, behind them, the copy of the state to the pinned hS2
+template <class Pass>
+static int enqueue_passes(SpecImpl* P, int n, Pass&& pass, hipStream_t s) {
+    for (int j = 0; j < n; ++j) FOTO_TRY(pass());
+    FOTO_HIP_CHECK(hipMemcpyAsync(P->hS2, P->S2, sizeof(SStep), hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+// The s-step pass loop: the host polls the done flag between chunks of passes.  A poll idles the
+// GPU for the host's wake-up (measured up to ~1 ms per solve when polling every pass), while a
+// pass launched after the solve finished exits in a few us -- so over-predict: the first chunk is
+// the previous solve's pass count + 2 (8 without one), then chunks of 2.  launched > 0: a
+// deferred solve, whose passes and state copy the stream has passed; the loop only continues it.
+// pass() enqueues one pass on each of `shards` local shards.
+template <class Pass>
+static int pass_loop(SpecImpl* P, int launched, int shards, int maxiter, Pass&& pass, int* iters, int* info,
+                     KTimer* kt, hipStream_t s) {
+    int passes = launched;
+    while (passes == 0 || !P->hS2->done) {
+        const int chunk = passes > 0 ? 2 : P->last_passes > 0 ? P->last_passes + 2 : 8;
+        FOTO_TRY(enqueue_passes(P, chunk, pass, s));
+        FOTO_HIP_CHECK(hipStreamSynchronize(s));
+        passes += chunk;
+        if (!P->hS2->done && passes > maxiter + 4) {
+            set_error("spectral s-step CG did not terminate");
+            return FOTO_ERR_STATE;
+        }
+    }
+    *iters = P->hS2->iters;
+    *info = (P->hS2->done == 1) ? 0 : maxiter;
+    P->last_passes = P->hS2->passes;
+    // S.passes counts the plans (INIT's and every working pass's but the last), i.e. the
+    // passes that applied steps; the launches beyond them exited at once -- keep them out of
+    // the per-kernel timing
+    if (kt) kt->discard_last(FOTO_K_SPEC, std::max(0, passes - P->hS2->passes) * shards);
+    return 0;
+}
+
+// b^ -> r^ by the s-step CG, waited for.  init_done: the fused t-axis kernel already reset the
+// state, took r_0's moments and planned (no reset_s2, a host wait per solve: the INIT plan
+// rewrites every field but the constant c0, c1, which init() set)
+static int solve_s2(SpecImpl* P, double rtol, int maxiter, int* iters, int* info, KTimer* kt, hipStream_t s,
+                    bool init_done) {
+    if (!init_done) FOTO_TRY(s2_launch(P, true, rtol, maxiter, kt, s));
+    return pass_loop(P, 0, 1, maxiter, [&] { return s2_launch(P, false, rtol, maxiter, kt, s); }, iters, info, kt, s);
+}
+
+// b^ -> r^ by the one-step CG (Chronopoulos-Gear), polled in chunks from `predicted` iterations
+static int solve_s1(SpecImpl* P, double rtol, int maxiter, int predicted, int* iters, int* info, KTimer* kt,
+                    hipStream_t s) {
+    FOTO_HIP_CHECK(launch_init(P, s));
+    FOTO_HIP_CHECK(hipMemsetAsync(P->S, 0, sizeof(CGScal), s));
+    auto step = [&](int k) -> int {
+        hipEvent_t e = kt ? kt->start(s) : nullptr;
+        FOTO_HIP_CHECK(launch_cg(P, k, rtol, s));
+        if (kt) kt->stop(e, s, FOTO_K_SPEC, (k == 0 ? 24.0 : 32.0) * P->nbox());
+        return 0;
+    };
+    bool done = false;
+    return cg_poll_chunks(predicted > 4 ? predicted - 3 : 8, maxiter, step, P->S, P->hS, s, &done, iters, info);
 }
 
 // ---------------------------------------------------------------------------- Gauss-compressed CG (host)
@@ -1867,14 +1962,6 @@ static int gq_measure(SpecImpl* P, KTimer* kt, hipStream_t s) {
         FOTO_HIP_CHECK(hipGetLastError());
     }
     if (kt) kt->stop(e, s, FOTO_K_SPEC, 8.0 * P->nbox());
-    return 0;
-}
-
-// k_gq_cgtab's slots as a fresh plan has them: every (alpha, beta) NaN, kdone -1, ticket 0
-static int gq_pub_clear(SpecImpl* P, hipStream_t s) {
-    if (!P->gq_pub) return 0;
-    FOTO_HIP_CHECK(hipMemsetAsync(P->gq_pub, 0xff, sizeof(GqPub), s));   // (all-ones: NaN, -1)
-    FOTO_HIP_CHECK(hipMemsetAsync(&P->gq_pub->ticket, 0, sizeof(unsigned), s));
     return 0;
 }
 
@@ -1919,84 +2006,69 @@ static int gq_unbreak(SpecImpl* P, hipStream_t s) {
     return 0;
 }
 
+// How the Gauss solve in header slot h ended, once the stream has passed its header store.
+// !*ok (K beyond the table, or a breakdown): the solve is over and its done chain mended; the
+// caller redoes it with the s-step CG from b^, which is still intact.  A good solve stays
+// active -- its x^ comes from the table -- unless `end`: nothing of it is left to enqueue.
+static int gq_outcome(SpecImpl* P, int h, int maxiter, bool end, int* ok, int* iters, int* info, hipStream_t s) {
+    const GqState* H = P->hgq2[h];
+    *ok = H->status == 0;
+    *iters = H->K;
+    *info = H->conv ? 0 : maxiter;
+    if (!*ok || end) P->gauss_active = false;
+    if (!*ok) FOTO_TRY(gq_unbreak(P, s));
+    return 0;
+}
 
 // single shard: b (physical) -> b^ -> measure -> CG -> x, all enqueued.  b is only read: the
-// transforms run through the box buffers (b -x-> tmp -y-> rh -t-> b^; x^ -> rh / tmp ... -> x),
-// so F survives a solve whose prox was skipped -- a failed solve with the next outer iteration
-// already enqueued behind it (foto_bb.cpp) then finds its right-hand side intact.
+// transforms run through the box buffers (b -x-> tmp -y-> rh -t-> b^; x^ -> rh -t-> tmp -y-> rh
+// -x-> x), so F survives a solve whose prox was skipped -- a failed solve with the next outer
+// iteration already enqueued behind it (foto_bb.cpp) then finds its right-hand side intact.
 static int gq_enqueue(SpecImpl* P, const double* b, double* x, double rtol, int maxiter, KTimer* kt, hipStream_t s) {
-    const Geo& g = P->g;
-    const double N = (double)g.Nt * (double)g.nxy;
-    hipEvent_t e = kt ? kt->start(s) : nullptr;
-    FOTO_HIP_CHECK(dct_pass(P, 0, false, g.Nt * g.Ny, 1, b, P->tmp, s));
-    FOTO_HIP_CHECK(dct_pass(P, 1, false, g.Nt, g.Nx, P->tmp, P->rh, s));
-    if (P->tcol) FOTO_HIP_CHECK(launch_tcol(P, false, P->rh, nullptr, rtol, maxiter, s, TC_PLAIN));
-    else FOTO_HIP_CHECK(dct_pass(P, 2, false, 1, (int)g.nxy, P->rh, P->bh, s));
-    if (kt) kt->stop(e, s, FOTO_K_DCT, 6.0 * 8.0 * N);
+    FOTO_TRY(forward(P, b, P->rh, TC_PLAIN, rtol, maxiter, kt, s));
     FOTO_TRY(gq_measure(P, kt, s));
     FOTO_TRY(gq_solve(P, rtol, maxiter, kt, s));
-    e = kt ? kt->start(s) : nullptr;
-    if (P->tcol) {
-        FOTO_HIP_CHECK(launch_tcol(P, true, nullptr, P->tmp, rtol, maxiter, s));   // x^ -> rh, t^-1 -> tmp
-    } else {
-        FOTO_HIP_CHECK(gq_xhat(P, P->rh, s));
-        FOTO_HIP_CHECK(dct_pass(P, 2, true, 1, (int)g.nxy, P->rh, P->tmp, s));
-    }
-    FOTO_HIP_CHECK(dct_pass(P, 1, true, g.Nt, g.Nx, P->tmp, P->rh, s));
-    FOTO_HIP_CHECK(dct_pass(P, 0, true, g.Nt * g.Ny, 1, P->rh, x, s));
-    if (kt) kt->stop(e, s, FOTO_K_DCT, 7.0 * 8.0 * N);
-    return 0;
+    return inverse(P, XH_GAUSS, P->rh, P->tmp, P->rh, x, kt, s);
 }
 
 // the s-step CG from b^ (still intact) when the tables could not represent the solve
 static int gq_redo(SpecImpl* P, double* b, double* x, double rtol, int maxiter, int* iters, int* info, KTimer* kt,
                    hipStream_t s) {
-    P->gauss_active = false;
-    FOTO_TRY(gq_unbreak(P, s));
-    FOTO_TRY(solve_s2(P, rtol, maxiter, 0, iters, info, kt, s, false));
-    if (P->tcol) return tcol_inverse(P, b, x, rtol, maxiter, kt, s);
-    FOTO_HIP_CHECK(launch_xhat(P, s));
-    return inverse3(P, P->tmp, b, x, kt, s);
+    FOTO_TRY(solve_s2(P, rtol, maxiter, iters, info, kt, s, false));
+    return inverse_sstep(P, b, x, kt, s);
 }
 
-// after the stream has passed the header copy of the solve in ring slot h
-static void gq_result(const SpecImpl* P, int h, int maxiter, int* iters, int* info) {
-    *iters = P->hgq2[h]->K;
-    *info = P->hgq2[h]->conv ? 0 : maxiter;
-}
+// ---------------------------------------------------------------------------- single shard
 
-// single shard, s-step, column-kernel t axis: b -x-> tmp -y-> b -t(+INIT)-> b^; CG passes;
-// (b^, r^) -t(+xhat)-> b -y-> tmp -x-> x
-static int solve_tcol(SpecImpl* P, double* b, double* x, double rtol, int maxiter, int predicted, int* iters,
-                      int* info, KTimer* kt, hipStream_t s) {
-    const Geo& g = P->g;
-    const double N = (double)g.Nt * (double)g.nxy;
-    // no reset_s2 here (a host wait per solve): the INIT plan rewrites every field but the
-    // constant c0, c1, which init() set
-    hipEvent_t e = kt ? kt->start(s) : nullptr;
-    FOTO_HIP_CHECK(dct_pass(P, 0, false, g.Nt * g.Ny, 1, b, P->tmp, s));
-    FOTO_HIP_CHECK(dct_pass(P, 1, false, g.Nt, g.Nx, P->tmp, b, s));
-    FOTO_HIP_CHECK(launch_tcol(P, false, b, nullptr, rtol, maxiter, s));
-    if (kt) kt->stop(e, s, FOTO_K_DCT, 6.0 * 8.0 * N);
-    FOTO_TRY(solve_s2(P, rtol, maxiter, predicted, iters, info, kt, s, true));
-    return tcol_inverse(P, b, x, rtol, maxiter, kt, s);
+int SpectralPlan::solve(double* b, double* x, double rtol, int maxiter, int predicted, int* iters, int* info,
+                        KTimer* kt, hipStream_t s) {
+    SpecImpl* P = impl;
+    if (P->gauss) {
+        FOTO_TRY(gq_enqueue(P, b, x, rtol, maxiter, kt, s));
+        FOTO_HIP_CHECK(hipStreamSynchronize(s));
+        int ok = 0;
+        FOTO_TRY(gq_outcome(P, P->hlast, maxiter, true, &ok, iters, info, s));
+        return ok ? 0 : gq_redo(P, b, x, rtol, maxiter, iters, info, kt, s);
+    }
+    // b (physical) -> b^ (with the column kernels: and the INIT plan); b is scratch afterwards
+    FOTO_TRY(forward(P, b, b, TC_PLAN, rtol, maxiter, kt, s));
+    if (P->sstep == 2) FOTO_TRY(solve_s2(P, rtol, maxiter, iters, info, kt, s, P->tcol));
+    else FOTO_TRY(solve_s1(P, rtol, maxiter, predicted, iters, info, kt, s));
+    return inverse_sstep(P, b, x, kt, s);
 }
 
 bool SpectralPlan::deferrable() const {
-    const SpecImpl* P = (const SpecImpl*)impl;
+    const SpecImpl* P = impl;
     if (P->gauss) return P->world == 1 && P->npend < 2;   // fixed work: nothing to predict
     return P->tcol && P->sstep == 2 && P->world == 1 && P->last_passes > 0 && P->npend == 0;
 }
 
-const int* SpectralPlan::done_flag() const {
-    const SpecImpl* P = (const SpecImpl*)impl;
-    return P->gauss ? &P->gq->done : &P->S2->done;
-}
+const int* SpectralPlan::done_flag() const { return impl->gauss ? &impl->gq->done : &impl->S2->done; }
 
-int SpectralPlan::pending() const { return ((const SpecImpl*)impl)->npend; }
+int SpectralPlan::pending() const { return impl->npend; }
 
 int SpectralPlan::solve_deferred(double* b, double* x, double rtol, int maxiter, KTimer* kt, hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
+    SpecImpl* P = impl;
     if (!deferrable()) {
         set_error("spectral CG: deferred solve needs a single-shard plan with a free slot (s-step: after a finished solve)");
         return FOTO_ERR_STATE;
@@ -2013,37 +2085,25 @@ int SpectralPlan::solve_deferred(double* b, double* x, double rtol, int maxiter,
         ++P->npend;
         return 0;
     }
-    const Geo& g = P->g;
-    const double N = (double)g.Nt * (double)g.nxy;
-    hipEvent_t e = kt ? kt->start(s) : nullptr;
-    FOTO_HIP_CHECK(dct_pass(P, 0, false, g.Nt * g.Ny, 1, b, P->tmp, s));
-    FOTO_HIP_CHECK(dct_pass(P, 1, false, g.Nt, g.Nx, P->tmp, b, s));
-    FOTO_HIP_CHECK(launch_tcol(P, false, b, nullptr, rtol, maxiter, s));
-    if (kt) kt->stop(e, s, FOTO_K_DCT, 6.0 * 8.0 * N);
+    FOTO_TRY(forward(P, b, b, TC_PLAN, rtol, maxiter, kt, s));
     // the previous solve's pass count + margin (passes past the end exit at once);
     // FOTO_CG_MARGIN overrides the default 2 (tests force the redo path with a negative one)
-    const int n = std::max(1, P->last_passes + P->tn.cg_margin);
-    for (int j = 0; j < n; ++j) {
-        hipEvent_t ep = kt ? kt->start(s) : nullptr;
-        FOTO_HIP_CHECK(launch_s2(P, false, rtol, maxiter, nullptr, s));
-        if (kt) kt->stop(ep, s, FOTO_K_SPEC, 32.0 * N);
-    }
-    FOTO_HIP_CHECK(hipMemcpyAsync(P->hS2, P->S2, sizeof(SStep), hipMemcpyDeviceToHost, s));
-    FOTO_TRY(tcol_inverse(P, b, x, rtol, maxiter, kt, s));
-    d.launched = n;
+    d.launched = std::max(1, P->last_passes + P->tn.cg_margin);
+    FOTO_TRY(enqueue_passes(P, d.launched, [&] { return s2_launch(P, false, rtol, maxiter, kt, s); }, s));
+    FOTO_TRY(inverse_sstep(P, b, x, kt, s));
     ++P->npend;
     return 0;
 }
 
 bool SpectralPlan::oldest_needs_redo() const {
-    const SpecImpl* P = (const SpecImpl*)impl;
+    const SpecImpl* P = impl;
     if (P->npend == 0) return false;
     if (P->gauss) return P->hgq2[P->pq[0].hslot]->status != 0;
     return !P->hS2->done;
 }
 
 int SpectralPlan::drop_newest(hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
+    SpecImpl* P = impl;
     if (P->npend == 0 || !P->gauss) {
         set_error("spectral CG: no Gauss solve in flight to drop");
         return FOTO_ERR_STATE;
@@ -2054,105 +2114,29 @@ int SpectralPlan::drop_newest(hipStream_t s) {
 }
 
 int SpectralPlan::finish(int* iters, int* info, int* redo, KTimer* kt, hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
+    SpecImpl* P = impl;
     if (P->npend == 0) {
         set_error("spectral CG: no deferred solve to finish");
+        return FOTO_ERR_STATE;
+    }
+    if (P->npend > 1 && oldest_needs_redo()) {
+        set_error("spectral CG: a failed solve must be redone before the next one runs (drop it first)");
         return FOTO_ERR_STATE;
     }
     const SpecImpl::Pend d = P->pq[0];
     P->pq[0] = P->pq[1];
     --P->npend;
-    *redo = 0;
     if (P->gauss) {
-        if (P->hgq2[d.hslot]->status != 0) {   // K beyond the table or a breakdown: the s-step CG from b^
-            if (P->npend != 0) {
-                set_error("spectral CG: a failed solve must be redone before the next one runs (drop it first)");
-                return FOTO_ERR_STATE;
-            }
-            *redo = 1;
-            return gq_redo(P, d.b, d.x, d.rtol, d.maxiter, iters, info, kt, s);
-        }
-        gq_result(P, d.hslot, d.maxiter, iters, info);
-        if (P->npend == 0) P->gauss_active = false;
-        return 0;
+        int ok = 0;
+        FOTO_TRY(gq_outcome(P, d.hslot, d.maxiter, P->npend == 0, &ok, iters, info, s));
+        *redo = !ok;
+        return ok ? 0 : gq_redo(P, d.b, d.x, d.rtol, d.maxiter, iters, info, kt, s);
     }
-    int passes = d.launched;
-    if (!P->hS2->done) {   // the predicted passes were not enough: continue, polling, and redo x
-        *redo = 1;
-        const double N = P->nbox();
-        while (!P->hS2->done) {
-            for (int j = 0; j < 2; ++j, ++passes) {
-                hipEvent_t e = kt ? kt->start(s) : nullptr;
-                FOTO_HIP_CHECK(launch_s2(P, false, d.rtol, d.maxiter, nullptr, s));
-                if (kt) kt->stop(e, s, FOTO_K_SPEC, 32.0 * N);
-            }
-            FOTO_HIP_CHECK(hipMemcpyAsync(P->hS2, P->S2, sizeof(SStep), hipMemcpyDeviceToHost, s));
-            FOTO_HIP_CHECK(hipStreamSynchronize(s));
-            if (passes > d.maxiter + 4) {
-                set_error("spectral s-step CG did not terminate");
-                return FOTO_ERR_STATE;
-            }
-        }
-        FOTO_TRY(tcol_inverse(P, d.b, d.x, d.rtol, d.maxiter, kt, s));
-    }
-    *iters = P->hS2->iters;
-    *info = (P->hS2->done == 1) ? 0 : d.maxiter;
-    P->last_passes = P->hS2->passes;
-    if (kt) kt->discard_last(FOTO_K_SPEC, std::max(0, passes - P->hS2->passes));
-    return 0;
-}
-
-int SpectralPlan::solve(double* b, double* x, double rtol, int maxiter, int predicted, int* iters, int* info,
-                        KTimer* kt, hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
-    const Geo& g = P->g;
-    const SpecTab T = P->tab();
-    const double N = (double)g.Nt * (double)g.nxy;
-    const bool vec = P->vec();
-    if (P->gauss) {
-        FOTO_TRY(gq_enqueue(P, b, x, rtol, maxiter, kt, s));
-        FOTO_HIP_CHECK(hipStreamSynchronize(s));
-        if (P->hgq2[P->hlast]->status != 0) return gq_redo(P, b, x, rtol, maxiter, iters, info, kt, s);
-        gq_result(P, P->hlast, maxiter, iters, info);
-        P->gauss_active = false;
-        return 0;
-    }
-    if (P->tcol) return solve_tcol(P, b, x, rtol, maxiter, predicted, iters, info, kt, s);
-    // b (physical) -> b^ ; b is scratch afterwards
-    FOTO_TRY(forward3(P, b, P->tmp, P->bh, kt, s));
-    if (P->sstep == 2) {
-        FOTO_TRY(solve_s2(P, rtol, maxiter, predicted, iters, info, kt, s));
-        FOTO_HIP_CHECK(launch_xhat(P, s));
-        FOTO_TRY(inverse3(P, P->tmp, b, x, kt, s));
-        return 0;
-    }
-    if (vec) k_spec_init<true><<<P->nblocks, NT, 0, s>>>(T, P->bh, P->rh, P->rb, P->gath);
-    else k_spec_init<false><<<P->nblocks, NT, 0, s>>>(T, P->bh, P->rh, P->rb, P->gath);
-    FOTO_HIP_CHECK(hipGetLastError());
-    FOTO_HIP_CHECK(hipMemsetAsync(P->S, 0, sizeof(CGScal), s));
-    int k = 0;
-    bool done = false;
-    const int first = predicted > 4 ? predicted - 3 : 8;
-    while (k < maxiter) {
-        int chunk = (k == 0) ? first : 2;
-        chunk = std::min(chunk, maxiter - k);
-        for (int j = 0; j < chunk; ++j, ++k) {
-            hipEvent_t e = kt ? kt->start(s) : nullptr;
-            if (vec) k_spec_cg<true><<<P->nblocks, NT, 0, s>>>(T, k, P->rh, P->ph, P->S, P->rb, P->gath, rtol);
-            else k_spec_cg<false><<<P->nblocks, NT, 0, s>>>(T, k, P->rh, P->ph, P->S, P->rb, P->gath, rtol);
-            FOTO_HIP_CHECK(hipGetLastError());
-            if (kt) kt->stop(e, s, FOTO_K_SPEC, (k == 0 ? 24.0 : 32.0) * N);
-        }
-        FOTO_HIP_CHECK(hipMemcpyAsync(P->hS, P->S, sizeof(CGScal), hipMemcpyDeviceToHost, s));
-        FOTO_HIP_CHECK(hipStreamSynchronize(s));
-        if (P->hS->done) { done = true; break; }
-    }
-    *iters = done ? P->hS->iters : maxiter;
-    *info = done ? 0 : maxiter;
-    if (vec) k_spec_xhat<true><<<P->nblocks, NT, 0, s>>>(T, P->bh, P->rh, P->tmp);
-    else k_spec_xhat<false><<<P->nblocks, NT, 0, s>>>(T, P->bh, P->rh, P->tmp);
-    FOTO_HIP_CHECK(hipGetLastError());
-    FOTO_TRY(inverse3(P, P->tmp, b, x, kt, s));
+    // the predicted passes were not enough: continue, polling, and redo x
+    *redo = !P->hS2->done;
+    FOTO_TRY(pass_loop(P, d.launched, 1, d.maxiter, [&] { return s2_launch(P, false, d.rtol, d.maxiter, kt, s); },
+                       iters, info, kt, s));
+    if (*redo) FOTO_TRY(inverse_sstep(P, d.b, d.x, kt, s));
     return 0;
 }
 
@@ -2160,139 +2144,90 @@ int SpectralPlan::solve(double* b, double* x, double rtol, int maxiter, int pred
 // Physical slab [tl][y][x] (planes t0..t0+nloc) <-> spectral box [kt][ky - y0][kx].
 
 int SpectralPlan::fwd_local(double* b, int lo, int hi, KTimer* kt, hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
-    const Geo& g = P->g;
+    const Geo& g = impl->g;
     if (lo < 0 || hi > g.nloc || hi <= lo) {
         set_error("spectral CG: fwd_local planes [%d, %d) outside the slab", lo, hi);
         return FOTO_ERR_ARG;
     }
-    const int np = hi - lo;
     const int64_t o = (int64_t)lo * g.nxy;
-    hipEvent_t e = kt ? kt->start(s) : nullptr;
-    FOTO_HIP_CHECK(dct_pass(P, 0, false, np * g.Ny, 1, b + o, P->tmpp + o, s));   // x
-    FOTO_HIP_CHECK(dct_pass(P, 1, false, np, g.Nx, P->tmpp + o, b + o, s));       // y (b: the all-to-all's source)
-    if (kt) kt->stop(e, s, FOTO_K_SLAB, 4.0 * 8.0 * (double)np * (double)g.nxy);
-    return 0;
+    Span sp(kt, s, FOTO_K_SLAB);
+    FOTO_TRY(chain_fwd_xy(impl, sp, hi - lo, b + o, impl->tmpp + o, b + o));   // (b: the all-to-all's source)
+    return sp.close();
 }
 
 int SpectralPlan::fwd_t(KTimer* kt, hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
-    const Geo& g = P->g;
-    hipEvent_t e = kt ? kt->start(s) : nullptr;
-    if (P->tcol)   // box tmp -> b^ and this rank's INIT moments -> gath (cg_begin then launches nothing)
-        FOTO_HIP_CHECK(launch_tcol(P, false, P->tmp, nullptr, 0.0, 0, s, P->gauss ? TC_PLAIN : TC_GATH));
-    else
-        FOTO_HIP_CHECK(dct_pass(P, 2, false, 1, P->nyl * g.Nx, P->tmp, P->bh, s));   // box tmp -> b^
-    if (kt) kt->stop(e, s, FOTO_K_DCT, 2.0 * 8.0 * P->nbox());
-    return 0;
+    Span sp(kt, s, FOTO_K_DCT);
+    // box tmp -> b^; the column kernel also leaves this rank's INIT moments in gath (cg_begin then
+    // launches nothing) unless the Gauss CG takes its own measure of b^
+    FOTO_TRY(chain_fwd_t(impl, sp, impl->gauss ? TC_PLAIN : TC_GATH, impl->tmp, 0.0, 0));
+    return sp.close();
 }
 
 int SpectralPlan::cg_begin(double rtol, int maxiter, KTimer* kt, hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
-    if (P->tcol && !P->gauss) return 0;   // the column kernel of fwd_t took the INIT moments
-    hipEvent_t e = kt ? kt->start(s) : nullptr;
-    FOTO_HIP_CHECK(launch_s2(P, true, rtol, maxiter, P->gath, s));
-    if (kt) kt->stop(e, s, FOTO_K_SPEC, 16.0 * P->nbox());
-    return 0;
+    if (impl->tcol && !impl->gauss) return 0;   // the column kernel of fwd_t took the INIT moments
+    return s2_launch(impl, true, rtol, maxiter, kt, s);
 }
 
 int SpectralPlan::cg_pass(double rtol, int maxiter, KTimer* kt, hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
-    hipEvent_t e = kt ? kt->start(s) : nullptr;
-    if (P->late_plan())   // plans at its start from the all-gathered moments (no cg_plan after it)
-        FOTO_HIP_CHECK(launch_s2_ring(P->tab(), P->rh, P->ph, P->bh, P->S2, P->rb, rtol, maxiter, P->gath, P->rank,
-                                      false, true, P->nb_ring, s, P->world));
-    else
-        FOTO_HIP_CHECK(launch_s2(P, false, rtol, maxiter, P->gath, s));
-    if (kt) kt->stop(e, s, FOTO_K_SPEC, 32.0 * P->nbox());
-    return 0;
+    return s2_launch(impl, false, rtol, maxiter, kt, s);
 }
 
 int SpectralPlan::cg_plan(int init, double rtol, int maxiter, hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
-    if (!init && P->late_plan()) return 0;   // the next cg_pass plans at its start
-    k_spec_s2_plan<<<1, 64, 0, s>>>(P->S2, P->gath, P->world, init, rtol, maxiter);
+    if (!init && impl->late_plan()) return 0;   // the next cg_pass plans at its start
+    k_spec_s2_plan<<<1, 64, 0, s>>>(impl->S2, impl->gath, impl->world, init, rtol, maxiter);
     FOTO_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-int SpectralPlan::poll(int* done, int* iters, int* passes, hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
-    FOTO_HIP_CHECK(hipMemcpyAsync(P->hS2, P->S2, sizeof(SStep), hipMemcpyDeviceToHost, s));
-    FOTO_HIP_CHECK(hipStreamSynchronize(s));
-    *done = P->hS2->done;
-    *iters = P->hS2->iters;
-    *passes = P->hS2->passes;
-    return 0;
+int SpectralPlan::sstep_passes(const std::function<int()>& pass, int shards, int maxiter, int* iters, int* info,
+                               KTimer* kt, hipStream_t s) {
+    return pass_loop(impl, 0, shards, maxiter, pass, iters, info, kt, s);
 }
 
 int SpectralPlan::inv_t(KTimer* kt, hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
-    const Geo& g = P->g;
-    hipEvent_t e = kt ? kt->start(s) : nullptr;
-    if (P->tcol) {   // x^ and the inverse t-DCT in one column kernel: tmp = box of x~ (box_out)
-        FOTO_HIP_CHECK(launch_tcol(P, true, nullptr, P->tmp, 0.0, 0, s));
-        if (kt) kt->stop(e, s, FOTO_K_DCT, 3.0 * 8.0 * P->nbox());
-        return 0;
-    }
-    if (P->gauss_active) FOTO_HIP_CHECK(gq_xhat(P, P->tmp, s));                     // tmp = x^
-    else FOTO_HIP_CHECK(launch_xhat(P, s));
-    FOTO_HIP_CHECK(dct_pass(P, 2, true, 1, P->nyl * g.Nx, P->tmp, P->rh, s));    // rh = box of x~
-    if (kt) kt->stop(e, s, FOTO_K_DCT, 2.0 * 8.0 * P->nbox());
-    return 0;
+    SpecImpl* P = impl;
+    Span sp(kt, s, FOTO_K_DCT);
+    // x^ through the box buffer that box_out() is not, the box of x~ to box_out()
+    FOTO_TRY(chain_inv_t(P, sp, P->gauss_active ? XH_GAUSS : XH_SSTEP, P->tcol ? P->rh : P->tmp, box_out()));
+    return sp.close();
 }
 
 int SpectralPlan::inv_local(double* scratch, double* x, int lo, int hi, KTimer* kt, hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
-    const Geo& g = P->g;
+    const Geo& g = impl->g;
     if (lo < -1 || hi > g.nloc + 1 || hi <= lo) {   // (one halo plane per side: phi's halo)
         set_error("spectral CG: inv_local planes [%d, %d) outside the slab and its halo", lo, hi);
         return FOTO_ERR_ARG;
     }
-    const int np = hi - lo;
     const int64_t o = (int64_t)lo * g.nxy;
-    hipEvent_t e = kt ? kt->start(s) : nullptr;
-    FOTO_HIP_CHECK(dct_pass(P, 1, true, np, g.Nx, scratch + o, P->tmpp + o, s));   // y (scratch: the all-to-all's target)
-    FOTO_HIP_CHECK(dct_pass(P, 0, true, np * g.Ny, 1, P->tmpp + o, x + o, s));     // x
-    if (kt) kt->stop(e, s, FOTO_K_SLAB, 4.0 * 8.0 * (double)np * (double)g.nxy);
-    return 0;
+    Span sp(kt, s, FOTO_K_SLAB);
+    // (scratch: the all-to-all's target)
+    FOTO_TRY(chain_inv_yx(impl, sp, hi - lo, scratch + o, impl->tmpp + o, x + o));
+    return sp.close();
 }
 
-bool SpectralPlan::gauss() const { return ((const SpecImpl*)impl)->gauss; }
+bool SpectralPlan::gauss() const { return impl->gauss; }
 int SpectralPlan::gauss_hist_size() { return GQ_HIST; }
-double* SpectralPlan::gauss_hist() const { return ((const SpecImpl*)impl)->gq_hist; }
+double* SpectralPlan::gauss_hist() const { return impl->gq_hist; }
 
-int SpectralPlan::gauss_measure(KTimer* kt, hipStream_t s) { return gq_measure((SpecImpl*)impl, kt, s); }
+int SpectralPlan::gauss_measure(KTimer* kt, hipStream_t s) { return gq_measure(impl, kt, s); }
 
 int SpectralPlan::gauss_solve(double rtol, int maxiter, KTimer* kt, hipStream_t s) {
-    return gq_solve((SpecImpl*)impl, rtol, maxiter, kt, s);
+    return gq_solve(impl, rtol, maxiter, kt, s);
 }
 
 int SpectralPlan::gauss_wait(int maxiter, int* ok, int* iters, int* info, hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
     FOTO_HIP_CHECK(hipStreamSynchronize(s));
-    *ok = P->hgq2[P->hlast]->status == 0;
-    gq_result(P, P->hlast, maxiter, iters, info);
-    if (!*ok) {
-        P->gauss_active = false;
-        FOTO_TRY(gq_unbreak(P, s));   // the s-step CG redoes this solve (foto_bb.cpp)
-    }
-    return 0;
+    return gq_outcome(impl, impl->hlast, maxiter, false, ok, iters, info, s);   // (ok: inv_t is still to come)
 }
 
 int SpectralPlan::gauss_result(int maxiter, int* ok, int* iters, int* info, hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
-    *ok = P->hgq2[P->hlast]->status == 0;
-    gq_result(P, P->hlast, maxiter, iters, info);
-    P->gauss_active = false;
-    if (!*ok) FOTO_TRY(gq_unbreak(P, s));
-    return 0;
+    return gq_outcome(impl, impl->hlast, maxiter, true, ok, iters, info, s);
 }
 
-void SpectralPlan::gauss_end() { ((SpecImpl*)impl)->gauss_active = false; }
+void SpectralPlan::gauss_end() { impl->gauss_active = false; }
 
 int SpectralPlan::reset(hipStream_t s) {
-    SpecImpl* P = (SpecImpl*)impl;
+    SpecImpl* P = impl;
     P->npend = 0;
     P->gauss_active = false;
     if (P->gq) FOTO_HIP_CHECK(hipMemsetAsync(P->gq, 0, sizeof(GqState), s));
@@ -2303,14 +2238,11 @@ int SpectralPlan::reset(hipStream_t s) {
     return reset_s2(P, s);
 }
 
-double* SpectralPlan::box_in() const { return ((SpecImpl*)impl)->tmp; }
-double* SpectralPlan::box_out() const {
-    const SpecImpl* P = (const SpecImpl*)impl;
-    return P->tcol ? P->tmp : P->rh;
-}
-double* SpectralPlan::gath() const { return ((SpecImpl*)impl)->gath; }
+double* SpectralPlan::box_in() const { return impl->tmp; }
+double* SpectralPlan::box_out() const { return impl->tcol ? impl->tmp : impl->rh; }
+double* SpectralPlan::gath() const { return impl->gath; }
 int SpectralPlan::moments() { return NACC; }
-int SpectralPlan::y0() const { return ((SpecImpl*)impl)->y0; }
-int SpectralPlan::nyl() const { return ((SpecImpl*)impl)->nyl; }
+int SpectralPlan::y0() const { return impl->y0; }
+int SpectralPlan::nyl() const { return impl->nyl; }
 
 }  // namespace foto
