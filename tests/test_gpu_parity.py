@@ -379,7 +379,9 @@ def test_bb_fused_prox_rhs_matches_separate(gold, monkeypatch, name, mode):
     kernels (FOTO_FUSE_PR=0) mu, phi, q (recomputed by state()) and the flow are bit-identical;
     only the crit sums are grouped differently (1e-14).  These goldens have Nt <= 8, one chunk
     at the default 16 planes per block; test_bb_fused_prox_rhs_chunks covers the chunk seams
-    (1 and 3 planes, and the default 16 on a 20-plane grid) and the t = 0 / Nt - 1 terms."""
+    (1 and 3 planes, and the default 16 on a 20-plane grid) and the t = 0 / Nt - 1 terms.  They
+    also have Nx <= 64, one tile column and no interior tile: x seams between tiles and the
+    INTERIOR body (from 130 x 18) are covered by tests/test_gpu_tile_seams.py."""
     d = gold(name)
     Nt, Ny, Nx = (int(v) for v in d["shape"])
     r, _, eps, _ = d["params"]
