@@ -81,6 +81,16 @@ int foto_flow_path_from_phi(const double* phi, int Nt, int Nx, int Ny, double* u
  * M < 1 or > 2^31 - 1, all_steps not 0 / 1.                                                      */
 int foto_track_from_phi(const double* phi, int Nt, int Nx, int Ny, const double* pts, int64_t M,
                         int all_steps, double* out);
+/* Test entries: the records of foto_bb_maps and the images of foto_bb_interp_dev (below, "maps and
+ * in-betweens") from a caller's phi, without a context; host float64 throughout.  s: count plane
+ * positions in [0, Nt-1].  Maps: out[count][4][Ny][Nx].  In-betweens: f0, f1 are [Ny][Nx][channels]
+ * (HWC, divisor 1), out is [count][Ny][Nx][channels].  FOTO_ERR_ARG (before any device is touched):
+ * a null pointer, Nt < 2, Nx or Ny < 2, count < 1, channels < 1, an s[k] outside [0, Nt-1] or not
+ * finite, inv_iters outside [1, FOTO_INV_ITERS_MAX].                                             */
+int foto_maps_from_phi(const double* phi, int Nt, int Nx, int Ny, const double* s, int count, int inv_iters,
+                       double* out);
+int foto_interp_from_phi(const double* phi, int Nt, int Nx, int Ny, const double* f0, const double* f1,
+                         int channels, const double* s, int count, int inv_iters, double* out);
 
 /* ------------------------------------------------------------------ BB solver context
  * benamou_brenier.solve (benamou_brenier.py:151-271) split into create / iterate /
@@ -419,6 +429,66 @@ int foto_bb_flow_path_dev(foto_bb_ctx* c, void* out, int dtype, int layout, void
 int foto_bb_track(foto_bb_ctx* c, const double* pts, int64_t M, int all_steps, double* out);          /* host f64 */
 int foto_bb_track_dev(foto_bb_ctx* c, const void* pts, int pts_dtype, int64_t M, int all_steps, void* out,
                       int dtype, void* stream);
+
+/* Maps and in-betweens: the transport read from an arbitrary time s in [0, Nt-1], in BOTH
+ * directions -- which pixel of frame 1 came from where in frame 0, and the caller's own frames
+ * (colour, masks, depth: anything defined on them) half-way.  No reference counterpart: utils.py
+ * reads the transport from frame 0 forward only (utils.py:44-99).
+ *
+ * Definitions.  Pixel (i, j) has centre p = (x, y) = (i, j).  V_n(z), n = 0..Nt-2, is plane n's
+ * interpolated velocity at z: exactly the pair of sums one step of utils.reconstructTrajectory
+ * (utils.py:63-97) adds to (x, y) -- the truncated, clamped cell, the weights w1..w4, the grad('N')
+ * taps with their zeroed border columns and rows, the sum order w1 u00 + w2 u01 + w3 u11 + w4 u10.
+ *   forward step    F_n(z) = z + V_n(z)                    (the step of foto_bb_flow / _track)
+ *   inverse step    inv(n, theta, p), theta in (0, 1]: z <- p, then z <- p - theta V_n(z) exactly
+ *                   inv_iters times.  A fixed count, no convergence test: deterministic, and exact
+ *                   to the contraction rate of theta V_n per round (DESIGN.md has measured rates).
+ *                   Where theta V_n is no contraction (a velocity that changes by a pixel or more
+ *                   per pixel) the rounds diverge and, the cell extrapolating bilinearly outside
+ *                   the frame, may overflow: such records are non-finite, never an out-of-range read.
+ *   maps at s       n = (int)s, theta = s - n (theta > 0 implies n <= Nt-2);
+ *                   p_n = theta > 0 ? inv(n, theta, p) : p;
+ *                   b = p_n pushed forward through the steps n, n+1, .., Nt-2 (none for n = Nt-1);
+ *                   a = p_n pulled back: a <- inv(m, 1, a) for m = n-1, .., 0;
+ *                   record (4 planes) = (a_x - x, a_y - y, b_x - x, b_y - y).
+ * Positions are float64 throughout.  At s = 0 the a-planes are +0.0 and the b-planes are
+ * foto_bb_flow's (u, v), bit for bit; at s = Nt-1 the b-planes are +0.0 and -a is the backward
+ * flow, frame 1 -> frame 0, without a second solve.
+ *   in-between      w_t = s / (Nt-1); per channel c:
+ *                   I_s(p) = (1 - w_t) S(I0_c; a) + w_t S(I1_c; b),
+ *                   S the clamped bilinear sample of the coarse-to-fine GN section below (a NaN
+ *                   coordinate gives NaN, read from in-frame taps), frame values = pixel / divisor.
+ *                   Output: FOTO_F64 x; FOTO_F32 (float)x; FOTO_U8 (uint8)(255 clip(x, 0, 1) + 0.5),
+ *                   NaN -> 0 -- foto_bb_frames' to-nearest rule, not the renderer's truncation, so
+ *                   that s = 0 and s = Nt-1 give a u8 frame back unchanged.  Both end frames come
+ *                   back bit for bit (finite frames).  The weights and taps of a and b are computed
+ *                   once per pixel and time and reused for every channel.
+ * s is a HOST array of `count` positions; inv_iters in [1, FOTO_INV_ITERS_MAX].  One launch per 128
+ * times, one thread per (pixel, time).  State rules, stream contract and pointer checks: those of
+ * foto_bb_flow_path[_dev] and foto_bb_frames_dev -- the last COMPLETED outer iteration's phi (from
+ * the default loop's callback: the iteration it reports; from the one-in-flight loop's callback
+ * FOTO_ERR_STATE); FOTO_ERR_STATE before any outer iteration, on an RCCL or a broken context;
+ * virtual_ranks > 1 works (a table of Nt plane pointers, built per call in a grow-only scratch of
+ * the context, finds each plane in the shard that owns it).  Nothing the next foto_bb_iterate
+ * reads is changed.
+ *   foto_bb_maps       host float64 out[count][4][Ny][Nx], staged through a grow-only scratch.
+ *   foto_bb_maps_dev   device out[count][4][Ny][Nx] of FOTO_F32 | FOTO_F64 ((float)x, to nearest even).
+ *   foto_bb_interp_dev f0 / f1 describe channel 0 of the two device frames (w = Nx, h = Ny); channel
+ *                      c starts c * stride_c0 / stride_c1 ELEMENTS further on, as in
+ *                      foto_render_warp_dev; out[count][Ny][Nx][channels] of out_dtype, which must
+ *                      not overlap a frame.
+ * FOTO_ERR_ARG, with `out` untouched and nothing enqueued: a null pointer, count < 1, an s[k] outside
+ * [0, Nt-1] or not finite, inv_iters outside [1, FOTO_INV_ITERS_MAX], a dtype outside {F32, F64}
+ * (maps) or 0..2 (in-betweens), channels < 1, a stride_c <= 0, anything foto_image_check rejects for
+ * any channel, an `out` not aligned to its element, a pointer that is not device memory of the
+ * context's device, an `out` that overlaps a frame.                                               */
+#define FOTO_INV_ITERS_MAX 64
+#define FOTO_INV_ITERS_DEFAULT 6
+int foto_bb_maps(foto_bb_ctx* c, const double* s, int count, int inv_iters, double* out);          /* host f64 */
+int foto_bb_maps_dev(foto_bb_ctx* c, const double* s, int count, int inv_iters, void* out, int dtype, void* stream);
+int foto_bb_interp_dev(foto_bb_ctx* c, const foto_image* f0, const foto_image* f1, int channels, int64_t stride_c0,
+                       int64_t stride_c1, const double* s, int count, int inv_iters, void* out, int out_dtype,
+                       void* stream);
 
 /* Transport report: how good the transport behind the exports above is, and what it costs -- per
  * time plane n = 0..Nt-1 the sums, over the plane's Nx*Ny voxels, of FOTO_REPORT_COLS terms of the

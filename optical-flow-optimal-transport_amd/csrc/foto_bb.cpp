@@ -191,12 +191,18 @@ struct foto_bb_ctx {
     // the transport report (foto_bb_report / _dev), grow-only, made on first use: the host entry's
     // staged table [Nt][8] | the plane partials [Nt][8][pieces] | Nt tickets (zero between launches)
     DevScratch rep;
+    // maps and in-betweens (foto_bb_maps / _dev, foto_bb_interp_dev), grow-only, made on first use:
+    // the table of Nt phi plane pointers, rebuilt by every call from the completed iteration's
+    // state, and the host entry's staged records [count][4][Ny][Nx]
+    enum { ITP_TAB = 0, ITP_OUT = 1 };
+    DevScratch itp[2];
     ~foto_bb_ctx() {
         if (sc) (void)hipStreamSynchronize(sc);
         if (s) (void)hipStreamSynchronize(s);   // (before the shards free their buffers)
         sh.clear();
         for (DevScratch& b : trk) if (b.p) (void)hipFree(b.p);
         if (rep.p) (void)hipFree(rep.p);
+        for (DevScratch& b : itp) if (b.p) (void)hipFree(b.p);
         if (nc) (void)ncclCommDestroy(nc);
         if (hS) (void)hipHostFree(hS);
         for (double* h : hgath) if (h) (void)hipHostFree(h);
@@ -1659,6 +1665,124 @@ int foto_bb_track_dev(foto_bb_ctx* c, const void* pts, int pts_dtype, int64_t M,
         FOTO_TRY(c->trk[foto_bb_ctx::TRK_POS].reserve(np * sizeof(double), c->s));
     FOTO_TRY(c->link.enter((hipStream_t)stream, c->s));   // (before the first read of `pts` / write of `out`)
     FOTO_TRY(track_run(c, k, pts, pts_dtype, M, all_steps, out, dtype));
+    return c->link.leave(c->s, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ maps and in-betweens
+// The table of phi's Nt plane pointers for this call: plane m lives in the shard that owns it, in
+// whichever of its two phi buffers holds the completed iteration (k.of(): shard 0's record of the
+// iteration in flight, when the default loop's callback calls).  Filled on the stream, ahead of the
+// launches that read it; an earlier call's launches are ahead of the refill on the same stream.
+static int plane_table(foto_bb_ctx* c, const Completed& k, const double* const** table) {
+    DevScratch& tab = c->itp[foto_bb_ctx::ITP_TAB];
+    FOTO_TRY(tab.reserve((size_t)c->Nt * sizeof(double*), c->s));
+    int covered = 0;
+    PlaneSegs sg;
+    sg.n = 0;
+    for (auto& sp : c->sh) {
+        sg.base[sg.n] = k.of(*sp).phi;
+        sg.t0[sg.n] = sp->g.t0;
+        sg.nloc[sg.n] = sp->g.nloc;
+        covered += sp->g.nloc;
+        if (++sg.n == PLANE_SEGS || sp == c->sh.back()) {
+            FOTO_HIP_CHECK(launch_plane_table(sg, (int64_t)c->Nx * c->Ny, (const double**)tab.p, c->s));
+            sg.n = 0;
+        }
+    }
+    if (covered != c->Nt) { set_error("maps: the local shards own %d of %d planes", covered, c->Nt); return FOTO_ERR_STATE; }
+    *table = (const double* const*)tab.p;
+    return 0;
+}
+
+// records [k0, k0 + cnt) of every launch: MAPS_MAX times each
+static int maps_run(foto_bb_ctx* c, const double* const* table, const double* s, int count, int inv_iters, void* out,
+                    int dtype) {
+    const size_t rec = 4 * (size_t)c->Nx * c->Ny * dtype_bytes(dtype);
+    for (int k0 = 0; k0 < count; k0 += MAPS_MAX)
+        FOTO_HIP_CHECK(launch_maps(table, c->Nt, c->Nx, c->Ny, s + k0, std::min(MAPS_MAX, count - k0), inv_iters,
+                                   (char*)out + (size_t)k0 * rec, dtype, c->s));
+    return 0;
+}
+
+int foto_bb_maps(foto_bb_ctx* c, const double* s, int count, int inv_iters, double* out) {
+    const char* who = "foto_bb_maps";
+    FOTO_TRY(path_state_check(c, who));
+    FOTO_TRY(maps_arg_check(s, out, count, inv_iters, c->Nt, who));
+    Completed k;
+    FOTO_TRY(completed_state(c, who, &k));
+    const size_t bytes = (size_t)count * 4 * (size_t)c->Nx * c->Ny * sizeof(double);
+    FOTO_TRY(c->itp[foto_bb_ctx::ITP_OUT].reserve(bytes, c->s));
+    const double* const* table = nullptr;
+    FOTO_TRY(plane_table(c, k, &table));
+    void* dout = c->itp[foto_bb_ctx::ITP_OUT].p;
+    FOTO_TRY(maps_run(c, table, s, count, inv_iters, dout, FOTO_F64));
+    FOTO_HIP_CHECK(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, c->s));
+    FOTO_HIP_CHECK(hipStreamSynchronize(c->s));
+    return 0;
+}
+
+int foto_bb_maps_dev(foto_bb_ctx* c, const double* s, int count, int inv_iters, void* out, int dtype, void* stream) {
+    const char* who = "foto_bb_maps_dev";
+    FOTO_TRY(path_state_check(c, who));
+    FOTO_TRY(maps_arg_check(s, out, count, inv_iters, c->Nt, who));
+    if (dtype != FOTO_F32 && dtype != FOTO_F64) {
+        set_error("%s: dtype %d is not FOTO_F32 / FOTO_F64", who, dtype);
+        return FOTO_ERR_ARG;
+    }
+    if ((uintptr_t)out % dtype_bytes(dtype) != 0) {
+        set_error("%s: out %p is not aligned to its %zu-byte element", who, out, dtype_bytes(dtype));
+        return FOTO_ERR_ARG;
+    }
+    FOTO_TRY(dev_ptr_check(out, (size_t)count * 4 * (size_t)c->Nx * c->Ny * dtype_bytes(dtype), stream_device(c->s),
+                           who, "out"));
+    Completed k;
+    FOTO_TRY(completed_state(c, who, &k));
+    const double* const* table = nullptr;
+    FOTO_TRY(plane_table(c, k, &table));
+    FOTO_TRY(c->link.enter((hipStream_t)stream, c->s));   // (before the first write of `out`)
+    FOTO_TRY(maps_run(c, table, s, count, inv_iters, out, dtype));
+    return c->link.leave(c->s, (hipStream_t)stream);
+}
+
+int foto_bb_interp_dev(foto_bb_ctx* c, const foto_image* f0, const foto_image* f1, int channels, int64_t stride_c0,
+                       int64_t stride_c1, const double* s, int count, int inv_iters, void* out, int out_dtype,
+                       void* stream) {
+    const char* who = "foto_bb_interp_dev";
+    FOTO_TRY(path_state_check(c, who));
+    // ---- host-only checks
+    if (!f0 || !f1) { set_error("%s: null pointer", who); return FOTO_ERR_ARG; }
+    FOTO_TRY(maps_arg_check(s, out, count, inv_iters, c->Nt, who));
+    FOTO_TRY(interp_frame_check(f0, channels, stride_c0, c->Nx, c->Ny, who));
+    FOTO_TRY(interp_frame_check(f1, channels, stride_c1, c->Nx, c->Ny, who));
+    if (out_dtype < FOTO_U8 || out_dtype > FOTO_F64) {
+        set_error("%s: out_dtype %d is not FOTO_U8 / FOTO_F32 / FOTO_F64", who, out_dtype);
+        return FOTO_ERR_ARG;
+    }
+    if ((uintptr_t)out % dtype_bytes(out_dtype) != 0) {
+        set_error("%s: out %p is not aligned to its %zu-byte element", who, out, dtype_bytes(out_dtype));
+        return FOTO_ERR_ARG;
+    }
+    // ---- the pointer queries, before anything is enqueued
+    const int dev = stream_device(c->s);
+    const size_t b0 = interp_frame_bytes(f0, channels, stride_c0, c->Nx, c->Ny);
+    const size_t b1 = interp_frame_bytes(f1, channels, stride_c1, c->Nx, c->Ny);
+    const size_t img = (size_t)c->Nx * c->Ny * (size_t)channels * dtype_bytes(out_dtype);
+    FOTO_TRY(dev_ptr_check(f0->data, b0, dev, who, "frame 0 (all channels)"));
+    FOTO_TRY(dev_ptr_check(f1->data, b1, dev, who, "frame 1 (all channels)"));
+    FOTO_TRY(dev_ptr_check(out, (size_t)count * img, dev, who, "out"));
+    if (overlaps(out, (size_t)count * img, f0->data, b0) || overlaps(out, (size_t)count * img, f1->data, b1)) {
+        set_error("%s: out may not overlap a frame (the in-between gathers)", who);
+        return FOTO_ERR_ARG;
+    }
+    Completed k;
+    FOTO_TRY(completed_state(c, who, &k));
+    const double* const* table = nullptr;
+    FOTO_TRY(plane_table(c, k, &table));
+    FOTO_TRY(c->link.enter((hipStream_t)stream, c->s));   // (before the first read of a frame / write of `out`)
+    for (int k0 = 0; k0 < count; k0 += MAPS_MAX)
+        FOTO_HIP_CHECK(launch_interp(table, c->Nt, c->Nx, c->Ny, *f0, stride_c0, *f1, stride_c1, channels, s + k0,
+                                     std::min(MAPS_MAX, count - k0), inv_iters, (char*)out + (size_t)k0 * img, out_dtype,
+                                     c->s));
     return c->link.leave(c->s, (hipStream_t)stream);
 }
 

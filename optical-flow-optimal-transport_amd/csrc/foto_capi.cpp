@@ -226,6 +226,68 @@ int foto_track_from_phi(const double* phi, int Nt, int Nx, int Ny, const double*
     return S.sync();
 }
 
+// the plane table of a contiguous phi[Nt][Ny][Nx] at d, in call scratch
+static int one_buffer_table(CallScope& S, const double* d, int Nt, int64_t nxy, const double* const** table) {
+    double* t = nullptr;   // (Nt pointers in Nt doubles' room)
+    static_assert(sizeof(double*) == sizeof(double), "a plane pointer per double");
+    FOTO_TRY(S.dev((size_t)Nt, &t));
+    PlaneSegs sg;
+    sg.n = 1;
+    sg.base[0] = d; sg.t0[0] = 0; sg.nloc[0] = Nt;
+    FOTO_HIP_CHECK(launch_plane_table(sg, nxy, (const double**)t, S.s));
+    *table = (const double* const*)t;
+    return 0;
+}
+
+int foto_maps_from_phi(const double* phi, int Nt, int Nx, int Ny, const double* s, int count, int inv_iters,
+                       double* out) {
+    const char* who = "foto_maps_from_phi";
+    FOTO_TRY(grid_size_check(Nt, Nx, Ny, who));
+    if (!phi) { set_error("%s: null pointer", who); return FOTO_ERR_ARG; }
+    FOTO_TRY(maps_arg_check(s, out, count, inv_iters, Nt, who));
+    CallScope S;
+    FOTO_TRY(S.init());
+    const int64_t nxy = (int64_t)Nx * Ny;
+    const size_t rec = 4 * (size_t)nxy;
+    double *d, *dout;
+    FOTO_TRY(S.up(phi, (size_t)Nt * nxy, &d));
+    FOTO_TRY(S.dev((size_t)count * rec, &dout));
+    const double* const* table = nullptr;
+    FOTO_TRY(one_buffer_table(S, d, Nt, nxy, &table));
+    for (int k0 = 0; k0 < count; k0 += MAPS_MAX)
+        FOTO_HIP_CHECK(launch_maps(table, Nt, Nx, Ny, s + k0, std::min(MAPS_MAX, count - k0), inv_iters,
+                                   dout + (size_t)k0 * rec, FOTO_F64, S.s));
+    FOTO_TRY(S.down(out, dout, (size_t)count * rec));
+    return S.sync();
+}
+
+int foto_interp_from_phi(const double* phi, int Nt, int Nx, int Ny, const double* f0, const double* f1, int channels,
+                         const double* s, int count, int inv_iters, double* out) {
+    const char* who = "foto_interp_from_phi";
+    FOTO_TRY(grid_size_check(Nt, Nx, Ny, who));
+    if (!phi || !f0 || !f1) { set_error("%s: null pointer", who); return FOTO_ERR_ARG; }
+    if (channels < 1) { set_error("%s: channels = %d must be >= 1", who, channels); return FOTO_ERR_ARG; }
+    FOTO_TRY(maps_arg_check(s, out, count, inv_iters, Nt, who));
+    CallScope S;
+    FOTO_TRY(S.init());
+    const int64_t nxy = (int64_t)Nx * Ny;
+    const size_t img = (size_t)nxy * (size_t)channels;
+    double *d, *d0, *d1, *dout;
+    FOTO_TRY(S.up(phi, (size_t)Nt * nxy, &d));
+    FOTO_TRY(S.up(f0, img, &d0));
+    FOTO_TRY(S.up(f1, img, &d1));
+    FOTO_TRY(S.dev((size_t)count * img, &dout));
+    const double* const* table = nullptr;
+    FOTO_TRY(one_buffer_table(S, d, Nt, nxy, &table));
+    const foto_image i0{d0, FOTO_F64, (int64_t)Nx * channels, channels, 1.0};   // interleaved HWC
+    const foto_image i1{d1, FOTO_F64, (int64_t)Nx * channels, channels, 1.0};
+    for (int k0 = 0; k0 < count; k0 += MAPS_MAX)
+        FOTO_HIP_CHECK(launch_interp(table, Nt, Nx, Ny, i0, 1, i1, 1, channels, s + k0, std::min(MAPS_MAX, count - k0),
+                                     inv_iters, dout + (size_t)k0 * img, FOTO_F64, S.s));
+    FOTO_TRY(S.down(out, dout, (size_t)count * img));
+    return S.sync();
+}
+
 int foto_report_from_state(const double* mu3, const double* phi, const double* rho0, const double* rhoT, int Nt,
                            int Nx, int Ny, double* out) {
     const char* who = "foto_report_from_state";

@@ -1,7 +1,8 @@
 // Device helpers shared between units: the spectral units' stores and loads (foto_spectral.hip,
 // foto_dct.hip, foto_probe.hip), the fixed-order block sum (foto_dev.hip, foto_eval.hip), the
-// trajectory step (k_traj, k_track: foto_kernels.hip) and the backward warp (k_warp:
-// foto_eval.hip, k_render_warp: foto_render.hip).  Outputs that are documented as bit-identical
+// trajectory step (k_traj, k_track: foto_kernels.hip; k_maps, k_interp: foto_interp.hip), the
+// backward warp (k_warp: foto_eval.hip, k_render_warp: foto_render.hip) and the clamped bilinear
+// sample (the pyramid: foto_gn_pyr.hip; k_interp).  Outputs that are documented as bit-identical
 // to each other are so because they run the one definition here.  The sums across blocks and
 // the wave primitives under them are shared the same way in foto_reduce.h.
 #pragma once
@@ -67,7 +68,10 @@ __device__ __forceinline__ int trunc_clamp(double v, int hi) {
 // the edge zeros selected afterwards: tx in [0, Nx-2] and ty in [0, Ny-2] for every x, y
 // (trunc_clamp maps NaN to 0 and clamps +-inf), so every load is inside the plane whatever the
 // position -- a non-finite position gives a non-finite position and nothing else.
-__device__ __forceinline__ void traj_step(const double* __restrict__ P, int Nx, int Ny, double& x, double& y) {
+// traj_vel is the sample alone, (vx, vy) = V(x, y): the step adds it, the inverse step of the
+// maps (inv_step below) subtracts a fraction of it.
+__device__ __forceinline__ void traj_vel(const double* __restrict__ P, int Nx, int Ny, double x, double y, double& vx,
+                                         double& vy) {
     const int tx = trunc_clamp(x, Nx - 2), ty = trunc_clamp(y, Ny - 2);
     const int xm = tx > 0 ? tx - 1 : 0, xp = tx + 2 < Nx ? tx + 2 : Nx - 1;
     const int ym = ty > 0 ? ty - 1 : 0, yp = ty + 2 < Ny ? ty + 2 : Ny - 1;
@@ -88,8 +92,30 @@ __device__ __forceinline__ void traj_step(const double* __restrict__ P, int Nx, 
     const double u11 = xr ? 0.0 : 0.5 * (d1 - b1), u10 = xl ? 0.0 : 0.5 * (c1 - a1);
     const double v00 = yl ? 0.0 : 0.5 * (b1 - bm), v01 = yl ? 0.0 : 0.5 * (c1 - cm);
     const double v11 = yr ? 0.0 : 0.5 * (cp - c0), v10 = yr ? 0.0 : 0.5 * (bp - b0);
-    x += w1 * u00 + w2 * u01 + w3 * u11 + w4 * u10;
-    y += w1 * v00 + w2 * v01 + w3 * v11 + w4 * v10;
+    vx = w1 * u00 + w2 * u01 + w3 * u11 + w4 * u10;
+    vy = w1 * v00 + w2 * v01 + w3 * v11 + w4 * v10;
+}
+
+__device__ __forceinline__ void traj_step(const double* __restrict__ P, int Nx, int Ny, double& x, double& y) {
+    double vx, vy;
+    traj_vel(P, Nx, Ny, x, y, vx, vy);
+    x += vx;
+    y += vy;
+}
+
+// The inverse of a (fraction theta of a) step: the z with z + theta V(z) = (px, py), by `iters`
+// rounds of z <- p - theta V(z) from z = p.  A fixed count and no convergence test: the result is
+// a function of the inputs alone, and restatable.  It converges where theta V is a contraction
+// (DESIGN.md 3.12 has the measured rates); elsewhere it is still inside every bound above.
+__device__ __forceinline__ void inv_step(const double* __restrict__ P, int Nx, int Ny, double theta, int iters,
+                                         double& x, double& y) {
+    const double px = x, py = y;
+    for (int k = 0; k < iters; ++k) {
+        double vx, vy;
+        traj_vel(P, Nx, Ny, x, y, vx, vy);
+        x = px - theta * vx;
+        y = py - theta * vy;
+    }
 }
 
 // ----------------------------------------------------------------------------- backward warp
@@ -134,6 +160,44 @@ __device__ __forceinline__ double warp_sum(const WarpTaps& T, double f1, double 
 __device__ __forceinline__ double warp_sum(const WarpTaps& T, double g1, double g2, double g3, double g4, double f1,
                                            double f2, double f3, double f4) {
     return warp_sum(T, g1 * f1, g2 * f2, g3 * f3, g4 * f4);
+}
+
+// ----------------------------------------------------------------------------- clamped sample
+// S(f; x, y): bilinear on a w x h field (w, h >= 2), the coordinate clamped into the frame; a NaN
+// coordinate gives NaN, read from in-frame taps (foto_warp's rule).  The cell and the two
+// fractions depend on the coordinate alone: a caller with several fields (the channels of
+// k_interp) computes them once.
+struct SampleTaps {
+    int i0, j0;      // the cell's upper-left tap, i0 in [0, w-2], j0 in [0, h-2]
+    double ax, ay;
+    bool bad;        // a NaN coordinate
+};
+
+__device__ __forceinline__ SampleTaps sample_taps(int w, int h, double x, double y) {
+    SampleTaps T;
+    T.bad = isnan(x) || isnan(y);
+    const double xc = T.bad ? 0.0 : fmin(fmax(x, 0.0), (double)(w - 1));
+    const double yc = T.bad ? 0.0 : fmin(fmax(y, 0.0), (double)(h - 1));
+    T.i0 = min((int)floor(xc), w - 2);
+    T.j0 = min((int)floor(yc), h - 2);
+    T.ax = xc - (double)T.i0;
+    T.ay = yc - (double)T.j0;
+    return T;
+}
+
+// f00 = f(j0, i0), f01 = f(j0, i0 + 1), f10 = f(j0 + 1, i0), f11 = f(j0 + 1, i0 + 1)
+__device__ __forceinline__ double sample_sum(const SampleTaps& T, double f00, double f01, double f10, double f11) {
+    const double t = (1.0 - T.ax) * f00 + T.ax * f01;
+    const double b = (1.0 - T.ax) * f10 + T.ax * f11;
+    const double v = (1.0 - T.ay) * t + T.ay * b;
+    return T.bad ? NAN : v;
+}
+
+__device__ __forceinline__ double pyr_sample(const double* __restrict__ f, int w, int h, double x, double y) {
+    const SampleTaps T = sample_taps(w, h, x, y);
+    const double* r0 = f + (int64_t)T.j0 * w + T.i0;
+    const double* r1 = r0 + w;
+    return sample_sum(T, r0[0], r0[1], r1[0], r1[1]);
 }
 
 }  // namespace foto

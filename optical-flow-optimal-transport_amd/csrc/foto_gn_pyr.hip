@@ -12,27 +12,14 @@
 #include <vector>
 
 #include "foto_devmem.h"
+#include "foto_devutil.h"
 #include "foto_gn.h"
 
 namespace foto {
 
 // ----------------------------------------------------------------------------- kernels
 
-// S(f; x, y): bilinear on a w x h field (w, h >= 2), the coordinate clamped into the frame; a NaN
-// coordinate gives NaN, read from in-frame taps (foto_warp's rule)
-__device__ __forceinline__ double pyr_sample(const double* __restrict__ f, int w, int h, double x, double y) {
-    const bool bad = isnan(x) || isnan(y);
-    const double xc = bad ? 0.0 : fmin(fmax(x, 0.0), (double)(w - 1));
-    const double yc = bad ? 0.0 : fmin(fmax(y, 0.0), (double)(h - 1));
-    const int i0 = min((int)floor(xc), w - 2), j0 = min((int)floor(yc), h - 2);
-    const double ax = xc - (double)i0, ay = yc - (double)j0;
-    const double* r0 = f + (int64_t)j0 * w + i0;
-    const double* r1 = r0 + w;
-    const double t = (1.0 - ax) * r0[0] + ax * r0[1];
-    const double b = (1.0 - ax) * r1[0] + ax * r1[1];
-    const double v = (1.0 - ay) * t + ay * b;
-    return bad ? NAN : v;
-}
+// (S(f; x, y), the clamped bilinear sample of the prolongation and the warp: pyr_sample, foto_devutil.h)
 
 // Restriction of both frames of a level, one thread per coarse pixel.  A lane reads the two
 // neighbouring doubles of each of its two rows, so a wave's loads cover one contiguous 1 KB span

@@ -362,6 +362,41 @@ struct FrameArgs {
 hipError_t launch_frames(const FrameArgs& fa, int count, int64_t n, double scale, void* out, int dtype,
                          hipStream_t s);
 
+// Maps and in-betweens (foto_interp.hip; foto_bb_maps / _dev, foto_bb_interp_dev, the *_from_phi
+// test entries).  A launch covers count <= MAPS_MAX times, passed by value, and the pixels in
+// MT_W x MT_H tiles.  Plane m of phi is table[m], a device array of Nt pointers that
+// launch_plane_table fills from up to PLANE_SEGS buffers (segment k: planes [t0, t0 + nloc) at
+// base; more buffers: more launches).
+constexpr int MAPS_MAX = 128;
+constexpr int MT_W = 32, MT_H = 8;
+constexpr int PLANE_SEGS = 32;
+struct MapTimes {
+    double s[MAPS_MAX];
+};
+struct PlaneSegs {
+    const double* base[PLANE_SEGS];
+    int t0[PLANE_SEGS], nloc[PLANE_SEGS];
+    int n;
+};
+hipError_t launch_plane_table(const PlaneSegs& sg, int64_t nxy, const double** table, hipStream_t s);
+// out[count][4][Ny][Nx] = (a_x - x, a_y - y, b_x - x, b_y - y) of dtype FOTO_F32 | FOTO_F64; s: a host array
+hipError_t launch_maps(const double* const* table, int Nt, int Nx, int Ny, const double* s, int count, int inv_iters,
+                       void* out, int dtype, hipStream_t st);
+// out[count][Ny][Nx][channels] of FOTO_U8 | FOTO_F32 | FOTO_F64; f0 / f1 describe channel 0, channel c
+// starts c * sc0 / sc1 elements further on
+hipError_t launch_interp(const double* const* table, int Nt, int Nx, int Ny, const foto_image& f0, int64_t sc0,
+                         const foto_image& f1, int64_t sc1, int channels, const double* s, int count, int inv_iters,
+                         void* out, int out_dtype, hipStream_t st);
+// host-only rules: non-null s and out, count >= 1, inv_iters in [1, FOTO_INV_ITERS_MAX], every s[k]
+// finite and in [0, Nt - 1]; a frame of `channels` channels: foto_render_warp_dev's rules
+int maps_arg_check(const double* s, const void* out, int count, int inv_iters, int Nt, const char* who);
+int interp_frame_check(const foto_image* f, int channels, int64_t stride_c, int w, int h, const char* who);
+size_t interp_frame_bytes(const foto_image* f, int channels, int64_t stride_c, int w, int h);   // all channels
+inline bool overlaps(const void* a, size_t na, const void* b, size_t nb) {   // byte ranges
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
 // A grow-only device scratch (the holder frees p).  Growing waits for `s` first: an earlier
 // call's launches there may still read the buffer being replaced.
 struct DevScratch {

@@ -309,11 +309,6 @@ size_t flow_bytes(const foto_flow* fl, int w, int h) {
     return (size_t)fl->records * (fl->layout == 0 ? 3 : 2) * (size_t)w * (size_t)h * dtype_bytes(fl->dtype);
 }
 
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
 // One stream, link and maxrad scratch per device, kept for the process like the EvSlots of
 // foto_eval.hip.  The calls only enqueue: the stream is never handed back to the pool, so nothing
 // waits on the host (but a scratch that has to grow).

@@ -123,6 +123,7 @@ class GNPyrStats(ctypes.Structure):
 
 
 FOTO_U8, FOTO_F32, FOTO_F64 = 0, 1, 2
+FOTO_INV_ITERS_MAX, FOTO_INV_ITERS_DEFAULT = 64, 6   # (include/foto.h, maps and in-betweens)
 
 
 class Image(ctypes.Structure):
@@ -219,6 +220,13 @@ SIGNATURES = {
     "foto_track_from_phi": (_I, [_D, _I, _I, _I, _D, ctypes.c_int64, _I, _D]),
     "foto_bb_track": (_I, [_P, _D, ctypes.c_int64, _I, _D]),
     "foto_bb_track_dev": (_I, [_P, _P, _I, ctypes.c_int64, _I, _P, _I, _P]),
+    # maps and in-betweens: the transport read from a time s in both directions
+    "foto_maps_from_phi": (_I, [_D, _I, _I, _I, _D, _I, _I, _D]),
+    "foto_interp_from_phi": (_I, [_D, _I, _I, _I, _D, _D, _I, _D, _I, _I, _D]),
+    "foto_bb_maps": (_I, [_P, _D, _I, _I, _D]),
+    "foto_bb_maps_dev": (_I, [_P, _D, _I, _I, _P, _I, _P]),
+    "foto_bb_interp_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _I, ctypes.c_int64, ctypes.c_int64,
+                                _D, _I, _I, _P, _I, _P]),
     # the transport report: per-plane mass, action, continuity and HJ residual sums
     "foto_bb_report": (_I, [_P, _D]),
     "foto_bb_report_dev": (_I, [_P, _P, _P]),

@@ -203,6 +203,59 @@ class BBSolver:
                                               ctypes.c_void_p(D.stream_handle(stream, out, points))))
         return out
 
+    # -------------------------------------------------------------- maps and in-betweens
+    def maps(self, times, inv_iters=_lib.FOTO_INV_ITERS_DEFAULT):
+        """The transport read from plane positions ``times`` in [0, Nt-1] (an int K:
+        np.linspace(0, Nt-1, K)) in both directions (foto_bb_maps): float64 (K, 4, Ny, Nx), per
+        time the planes (a_x - x, a_y - y, b_x - x, b_y - y) -- the pixel of the time-s image at
+        (x, y) came from a in frame 0 and goes to b in frame 1.  At time 0 the b-planes are
+        flow()'s (u, v) bit for bit; at Nt-1 the negated a-planes are the backward flow, frame 1
+        to frame 0.  ``inv_iters`` (1..64): rounds of the fixed-count inverse step."""
+        from . import device as D
+        pos = D.frame_positions(times, self.Nt)
+        out = np.empty((pos.size, 4, self.Ny, self.Nx))
+        self._check(self._L.foto_bb_maps(self._ctx, dptr(pos), int(pos.size), int(inv_iters), dptr(out)))
+        return out
+
+    def maps_device(self, times, inv_iters=_lib.FOTO_INV_ITERS_DEFAULT, out=None, dtype="float32", stream=None):
+        """maps() left on the device (foto_bb_maps_dev): a DeviceArray (or ``out``, any contiguous
+        device array) [K][4][Ny][Nx] of ``dtype`` float32 | float64."""
+        from . import device as D
+        pos = D.frame_positions(times, self.Nt)
+        out, ptr, dcode = D.maps_target(out, dtype, pos.size, self.Ny, self.Nx)
+        self._check(self._L.foto_bb_maps_dev(self._ctx, dptr(pos), int(pos.size), int(inv_iters), ctypes.c_void_p(ptr),
+                                             dcode, ctypes.c_void_p(D.stream_handle(stream, out))))
+        return out
+
+    def interpolate(self, frame0, frame1, times, inv_iters=_lib.FOTO_INV_ITERS_DEFAULT, dtype=None, out=None,
+                    stream=None, channels_last=True, divisor=None):
+        """Motion-compensated in-betweens of the caller's own frames (foto_bb_interp_dev): per
+        channel (1 - w) S(frame0; a) + w S(frame1; b), w = s / (Nt-1), along maps()'s a and b.
+        ``frame0`` / ``frame1``: two numpy arrays (Ny, Nx) or (Ny, Nx, C) -- uploaded, the result
+        downloaded -- or two device arrays ((C, Ny, Nx) with ``channels_last=False``), the result
+        left on the device: (K, Ny, Nx[, C]) of ``dtype`` uint8 | float32 | float64 (None: the
+        frames' own; numpy frames of another dtype go through float64).  Values are pixel /
+        ``divisor`` (255 for uint8 frames, 1 otherwise); uint8 output is 255 clip(x, 0, 1) rounded
+        to nearest.  Times 0 and Nt-1 give the two frames back bit for bit."""
+        from . import device as D
+        host = not (hasattr(frame0, "__cuda_array_interface__") or isinstance(frame0, dict))
+        if host:
+            def up(f):
+                a = np.asarray(f)
+                if a.dtype not in (np.uint8, np.float32, np.float64):
+                    a = a.astype(np.float64)
+                return D.DeviceArray.from_numpy(a)
+            frame0, frame1 = up(frame0), up(frame1)
+        a, b, C, sc0, sc1, has_c, own = D.interp_frames(frame0, frame1, channels_last, divisor)
+        if a.shape != (self.Ny, self.Nx):
+            raise ValueError(f"frames of shape {a.shape}; this solver was made for {(self.Ny, self.Nx)}")
+        pos = D.frame_positions(times, self.Nt)
+        out, ptr, dcode = D.interp_target(out, own if dtype is None else dtype, pos.size, self.Ny, self.Nx, C, has_c)
+        self._check(self._L.foto_bb_interp_dev(self._ctx, ctypes.byref(a), ctypes.byref(b), C, sc0, sc1, dptr(pos),
+                                               int(pos.size), int(inv_iters), ctypes.c_void_p(ptr), dcode,
+                                               ctypes.c_void_p(D.stream_handle(stream, out, frame0, frame1))))
+        return out.to_numpy() if host else out
+
     # -------------------------------------------------------------- transport report
     def report(self):
         """The TransportReport (foto.report) of the last completed outer iteration: per time
@@ -420,8 +473,10 @@ def clear_context_cache():
 
 
 def solve(rho0, rhoT, Nt, Nx, Ny, r=1, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, log=print,
-          stats=None, **opts):
-    """benamou_brenier.solve on the GPU.  Returns (u, v, m)."""
+          stats=None, then=None, **opts):
+    """benamou_brenier.solve on the GPU.  Returns (u, v, m).  ``then(solver)``: called on the
+    solved context after the flow extraction, while it still holds this pair's transport (the
+    exports of the path: frames, maps, in-betweens); its result is dropped."""
     if max_it <= 0:
         # reference: the loop body never runs and `phi` is unbound at benamou_brenier.py:271
         raise UnboundLocalError("cannot access local variable 'phi' where it is not associated with a value")
@@ -433,7 +488,7 @@ def solve(rho0, rhoT, Nt, Nx, Ny, r=1, convergence_tol=0.3, reg_epsilon=1e-3, ma
 
     return on_context(opts, lambda: cached_solver(rho0, rhoT, Nt, Nx, Ny, r, reg_epsilon, **opts),
                       lambda: BBSolver(rho0, rhoT, Nt, Nx, Ny, r=r, reg_epsilon=reg_epsilon, **opts),
-                      lambda s: _run(s, max_it, convergence_tol, cb, stats))
+                      lambda s: _run(s, max_it, convergence_tol, cb, stats, then))
 
 
 def solve_ex(rho0, rhoT, Nt, Nx, Ny, r=1, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, cap=None,
@@ -480,9 +535,11 @@ def solve_ex(rho0, rhoT, Nt, Nx, Ny, r=1, convergence_tol=0.3, reg_epsilon=1e-3,
     return u, v, m, rep
 
 
-def _run(s, max_it, convergence_tol, cb, stats):
+def _run(s, max_it, convergence_tol, cb, stats, then=None):
     s.iterate(max_it, convergence_tol=convergence_tol, stop_rules=True, callback=cb)
     out = s.flow()
+    if then is not None:
+        then(s)
     if stats is not None:
         stats.update(crit=np.array(s.crit), cg_its=np.array(s.cg_its), cg_info=np.array(s.cg_info),
                      phi=s.phi(), **s.stats())

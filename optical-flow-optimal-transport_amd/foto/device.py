@@ -413,6 +413,31 @@ def track_target(out, dtype, R, M):
     return _shaped_target(out, dtype, _OUT_DTYPES, (int(R), int(M), 2), "track records")
 
 
+def maps_target(out, dtype, count, h, w):
+    """(out, pointer, dtype code) of a maps export: [count][4][h][w] of float32 | float64."""
+    return _shaped_target(out, dtype, _OUT_DTYPES, (int(count), 4, h, w), "maps")
+
+
+def interp_frames(frame0, frame1, channels_last=True, divisor=None):
+    """The two frames of an in-between as (image 0, image 1, channels, stride_c0, stride_c1,
+    has_channel_axis, dtype name): device arrays (h, w), (h, w, C) or (C, h, w) of the same shape
+    (foto.render.source_arg's rules; dtypes and strides may differ).  ValueError before the library
+    is touched."""
+    from .render import source_arg
+    a, C, sc0, has_c = source_arg(frame0, channels_last, divisor)
+    b, C1, sc1, has_c1 = source_arg(frame1, channels_last, divisor)
+    if a.shape != b.shape or C != C1 or has_c != has_c1:
+        raise ValueError(f"frames differ in shape: {a.shape} x {C} and {b.shape} x {C1} (h x w x channels)")
+    name = {v[0]: np.dtype(v[1]).name for v in _DTYPES.values()}[a.dtype]
+    return a, b, C, sc0, sc1, has_c, name
+
+
+def interp_target(out, dtype, count, h, w, C, has_c):
+    """(out, pointer, dtype code) of an in-between export: [count][h][w][C] (no channel axis for
+    2-D frames) of uint8 | float32 | float64."""
+    return _shaped_target(out, dtype, _FRAME_DTYPES, (int(count), h, w) + ((C,) if has_c else ()), "in-betweens")
+
+
 def report_target(out, Nt):
     """(out, pointer) of a transport-report export: a new DeviceArray or the caller's ``out``,
     C-contiguous float64 of shape (Nt, 8).  ValueError before the library is touched."""
@@ -478,6 +503,23 @@ def bb_track(f0, f1, Nt, points, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, m
     return _bb_solved(f0, f1, Nt, r, convergence_tol, reg_epsilon, max_it, normalize, stream, opts,
                       lambda s, st: s.track_device(points, out=out, dtype=dtype, all_steps=all_steps, stream=st),
                       points)
+
+
+def bb_interpolate(f0, f1, Nt, times, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, normalize=False,
+                   inv_iters=_lib.FOTO_INV_ITERS_DEFAULT, dtype=None, out=None, stream=None, channels_last=True,
+                   colour0=None, colour1=None, **opts):
+    """bb_flow's solve on the cached context, then motion-compensated in-betweens of the caller's own
+    frames at plane positions ``times`` (an int K: np.linspace(0, Nt-1, K), or a sequence in
+    [0, Nt-1]), left on the device: BBSolver.interpolate.  The solve runs on the grey-scale pair
+    ``f0``, ``f1``; ``colour0`` / ``colour1`` (device (h, w, C) or (C, h, w) arrays, e.g. the RGB
+    frames the grey pair came from) are what is interpolated instead, when given.  Returns
+    [K][h][w] or [K][h][w][C] (``dtype`` None: the frames' own); times 0 and Nt-1 give the two
+    frames back bit for bit."""
+    g0 = f0 if colour0 is None else colour0
+    g1 = f1 if colour1 is None else colour1
+    return _bb_solved(f0, f1, Nt, r, convergence_tol, reg_epsilon, max_it, normalize, stream, opts,
+                      lambda s, st: s.interpolate(g0, g1, times, inv_iters=inv_iters, dtype=dtype, out=out, stream=st,
+                                                  channels_last=channels_last), g0, g1)
 
 
 def bb_report(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, normalize=False, stream=None,

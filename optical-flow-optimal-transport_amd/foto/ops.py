@@ -7,7 +7,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import check, dptr, f64, lib
+from ._lib import FOTO_INV_ITERS_DEFAULT, check, dptr, f64, lib
 
 
 def grad_st(phi, Nt, Nx, Ny):
@@ -122,6 +122,35 @@ def track_from_phi(phi, Nt, Nx, Ny, points, all_steps=True):
     M = pts.shape[0]
     out = np.empty((max(Nt - 1, 0) if all_steps else 1, M, 2))
     check(lib().foto_track_from_phi(dptr(x), Nt, Nx, Ny, dptr(pts), M, 1 if all_steps else 0, dptr(out)))
+    return out
+
+
+def maps_from_phi(phi, Nt, Nx, Ny, times, inv_iters=FOTO_INV_ITERS_DEFAULT):
+    """float64 (K, 4, Ny, Nx): the maps of BBSolver.maps from a caller's phi, without a context --
+    per time the planes (a_x - x, a_y - y, b_x - x, b_y - y) of include/foto.h, "maps and
+    in-betweens".  ``times``: an int K (np.linspace(0, Nt-1, K)) or a sequence of plane positions."""
+    from .device import frame_positions
+    x = f64(phi, Nt * Nx * Ny, "phi")
+    pos = frame_positions(times, Nt)
+    out = np.empty((pos.size, 4, Ny, Nx))
+    check(lib().foto_maps_from_phi(dptr(x), Nt, Nx, Ny, dptr(pos), int(pos.size), int(inv_iters), dptr(out)))
+    return out
+
+
+def interp_from_phi(phi, Nt, Nx, Ny, frame0, frame1, times, inv_iters=FOTO_INV_ITERS_DEFAULT):
+    """float64 (K, Ny, Nx[, C]): the in-betweens of BBSolver.interpolate from a caller's phi and
+    two host frames (Ny, Nx) or (Ny, Nx, C), taken as float64 values (divisor 1)."""
+    from .device import frame_positions
+    x = f64(phi, Nt * Nx * Ny, "phi")
+    a, b = np.asarray(frame0, dtype=np.float64), np.asarray(frame1, dtype=np.float64)
+    if a.shape != b.shape or a.ndim not in (2, 3) or a.shape[:2] != (Ny, Nx):
+        raise ValueError(f"frames of shape {a.shape} and {b.shape}: both ({Ny}, {Nx}) or ({Ny}, {Nx}, C)")
+    C = a.shape[2] if a.ndim == 3 else 1
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    pos = frame_positions(times, Nt)
+    out = np.empty((pos.size,) + a.shape)
+    check(lib().foto_interp_from_phi(dptr(x), Nt, Nx, Ny, dptr(a), dptr(b), C, dptr(pos), int(pos.size),
+                                     int(inv_iters), dptr(out)))
     return out
 
 

@@ -44,11 +44,27 @@ def build_parser():
     p.add_argument("--cg-mode", type=int, default=None, help="0 stencil, 1 spectral, 2 spectral s-step, 3 Gauss-compressed spectral CG (default)")
     p.add_argument("--gn-levels", type=int, default=1, help="GN: pyramid levels (1: the reference's single solve)")
     p.add_argument("--gn-warps", type=int, default=1, help="GN: warped increment solves per pyramid level")
+    p.add_argument("--inbetweens", type=int, default=0,
+                   help="FOTO: motion-compensated in-betweens of the two input frames at this many evenly spaced "
+                        "interior times (0: none)")
+    p.add_argument("--save-inbetweens", default=None,
+                   help="FOTO: prefix of the in-between PNGs, written as PREFIX001.png, PREFIX002.png, ...")
     return p
 
 
 def _save_gray(img, w, h, path):
     Image.fromarray(img.reshape([h, w]), "L").save(path)
+
+
+def _open_u8(path):
+    """An input frame as the caller has it: uint8 (h, w) for a grey-scale file, (h, w, 3) RGB otherwise."""
+    im = Image.open(path)
+    return np.asarray(im if im.mode == "L" else im.convert("RGB"), dtype=np.uint8)
+
+
+def inbetween_times(K, Nt):
+    """K evenly spaced interior plane positions of [0, Nt - 1]: neither input frame is among them."""
+    return np.linspace(0.0, float(Nt - 1), int(K) + 2)[1:-1]
 
 
 def main(argv=None, writer=None):
@@ -90,6 +106,10 @@ def main(argv=None, writer=None):
         opts = {"device": args.device}
         if args.cg_mode is not None:
             opts["cg_mode"] = args.cg_mode
+        inbetweens = []
+        if args.inbetweens > 0 and args.save_inbetweens:   # (on the solved context, after the flow extraction)
+            c0, c1 = _open_u8(args.f0), _open_u8(args.f1)
+            opts["then"] = lambda s: inbetweens.append(s.interpolate(c0, c1, inbetween_times(args.inbetweens, args.Nt)))
         u, v, m = benamou_brenier.solve(rho1, rho2, args.Nt, w, h, r=args.r, convergence_tol=args.convergence_tol,
                                         reg_epsilon=args.reg_epsilon, max_it=args.max_it, **opts)
     elif args.algo == "GN":
@@ -146,6 +166,11 @@ def main(argv=None, writer=None):
     if args.save_lum:
         print("saving luminosity...")
         emit(_save_gray, np.uint8(255 * np.clip((m + 1) / 2, 0, 1)), w, h, args.save_lum)
+
+    if args.algo == "foto" and inbetweens:
+        print("saving in-betweens...")
+        for k, img in enumerate(inbetweens[0]):
+            emit(lambda a, path: Image.fromarray(a).save(path), img, f"{args.save_inbetweens}{k + 1:03d}.png")
 
     print("***********************************")
     return u, v, m
