@@ -714,6 +714,86 @@ int foto_render_lum_dev(const foto_flow* fl, int w, int h, void* out, void* stre
 int foto_render_color_dev(const foto_flow* fl, int w, int h, double maxmotion, void* out, double* maxrad_or_null,
                           void* stream);
 
+/* ------------------------------------------------------------------ scoring
+ * The evaluation stage on the buffers the entries above leave in HBM: utils.EE / AE / IE
+ * (utils.py:294-354) for every record of a flow buffer at once, with the robustness measures R(t),
+ * the accuracy percentiles A(p) and the normalised interpolation error NE of the Middlebury
+ * evaluation (Baker et al. 2011).  Additive: foto_flow_errors / foto_intensity_error are unchanged.
+ * The *_dev entries obey the stream contract of the device-buffer section and never synchronise
+ * with the host (but for a library scratch that has to grow); every device pointer is checked for
+ * the CURRENT device before anything is enqueued; an argument error leaves the outputs untouched.
+ *
+ * Definitions.  Values widen to double exactly; per pixel, in foto_flow_errors' operations,
+ *   EE = sqrt((u - uGT)^2 + (v - vGT)^2),
+ *   AE = acos((1 + u uGT + v vGT) / (sqrt(1 + u^2 + v^2) sqrt(1 + uGT^2 + vGT^2)))   (radians).
+ * A pixel is VALID if the mask (when given) is non-zero there and the ground truth is known:
+ * |uGT| <= 1e9, |vGT| <= 1e9 and neither is NaN (foto_render_color_dev's rule).  EE is KEPT where
+ * the pixel is valid and EE <= ee_cap (the reference's 50: a NaN EE drops out); AE is kept where
+ * the pixel is valid and AE is not NaN.  Deviation: on unknown-flow pixels the reference's AE keeps
+ * a finite, meaningless value; here they are not valid.  With no unknown pixel and no mask the
+ * means and standard deviations are the reference's.
+ *   R(t) = the fraction of the kept errors strictly above t.
+ *   A(p) = the k-th smallest kept error, k = max(1, ceil(p n / 100)) evaluated in float64 on the
+ *          device (n is known only there): an order statistic, an actual sample, found exactly by
+ *          a radix select on the bit pattern of the non-negative double.
+ * Table row of a record, FOTO_SCORE_COLS doubles:
+ *    0 n_valid   1 n_EE   2 EE mean   3 EE standard deviation (population)   4 EE max
+ *    5-8 R(ee_thr[i])   9-12 A(pct[j]) of EE
+ *   13 n_AE   14 AE mean   15 AE standard deviation   16 AE max
+ *   17-20 R(ae_thr[i])   21-24 A(pct[j]) of AE   25-31 zero.
+ * Unused R and A slots are NaN; with n = 0 every statistic of that quantity is NaN.  Sums are
+ * fixed-order reductions, counts and order statistics integer work: the same call gives the same
+ * bits.                                                                                        */
+#define FOTO_SCORE_COLS 32
+#define FOTO_SCORE_MAX_RECORDS 65535
+typedef struct {
+    double ee_cap;        /* EE above it is not kept; > 0 or +inf; default 50                  */
+    int n_ee_thr;         /* 0..4 thresholds of R for EE; default 3: 0.5, 1, 2                 */
+    int n_ae_thr;         /* 0..4 thresholds of R for AE, radians; default 3: 2.5, 5, 10 degrees */
+    int n_pct;            /* 0..4 percentiles of A, for EE and AE alike; default 3: 50, 75, 95  */
+    int reserved;         /* 0                                                                 */
+    double ee_thr[4];     /* finite, >= 0                                                      */
+    double ae_thr[4];     /* finite, >= 0                                                      */
+    double pct[4];        /* in (0, 100]                                                       */
+} foto_score_opts;
+int foto_score_opts_default(foto_score_opts* o);
+/* Host-only validation (no HIP call) of everything foto_score_flow / _dev take by descriptor:
+ * FOTO_ERR_ARG for a null fl or gt, anything foto_flow_check rejects for either, fl records above
+ * FOTO_SCORE_MAX_RECORDS, gt records that are neither 1 nor fl's, anything foto_image_check rejects
+ * for the mask, a count outside 0..4, a threshold that is negative or not finite, a percentile
+ * outside (0, 100], an ee_cap that is not > 0 (+inf is allowed, NaN is not).                    */
+int foto_score_check(const foto_flow* fl, const foto_flow* gt, const foto_image* mask_or_null, int w, int h,
+                     const foto_score_opts* opts_or_null);
+/* Scores every record of `fl` against `gt`: 1 record, broadcast, or as many as fl (a .flo payload
+ * as utils.openFlo reads it is {FOTO_F32, layout 1, 1 record}).  mask: a strided image, non-zero =
+ * evaluate.  table: DEVICE double [records][FOTO_SCORE_COLS].  maps_or_null: DEVICE
+ * [records][2][h][w] of maps_dtype FOTO_F32 | FOTO_F64 = EE, AE per pixel, NaN where the pixel is
+ * not valid.  FOTO_ERR_ARG also for a null table, a misaligned table / maps, a maps_dtype outside
+ * {F32, F64}, a pointer that is not device memory of the current device, and an output that
+ * overlaps an input or the other output.  Launches: the moments (one read of flow, ground truth and
+ * mask: counts, sums, maxima, threshold counts, maps, and the kept errors into a library scratch of
+ * 16 bytes per pixel and record), the squared deviations around the device-resident means, and one
+ * histogram + one scan launch per digit of the select, all records on a grid axis.               */
+int foto_score_flow_dev(const foto_flow* fl, const foto_flow* gt, const foto_image* mask_or_null, int w, int h,
+                        const foto_score_opts* opts_or_null, double* table, void* maps_or_null, int maps_dtype,
+                        void* stream);
+/* The same on HOST arrays behind the same descriptors (table and maps host arrays too): uploaded
+ * into the library's scratch, scored by the same launches, downloaded; waits once, at the end.   */
+int foto_score_flow(const foto_flow* fl, const foto_flow* gt, const foto_image* mask_or_null, int w, int h,
+                    const foto_score_opts* opts_or_null, double* table, void* maps_or_null, int maps_dtype);
+/* Scores `count` grey frames against one ground-truth frame: `frames` describes record 0, record k
+ * starts k * stride_rec ELEMENTS further on (the output of foto_bb_interp_dev, foto_bb_frames_dev
+ * or foto_render_warp_dev); value = (double)pixel / divisor for frames and truth alike.  table4:
+ * DEVICE double [count][4] = {n, IE, NE, max |255 I - 255 T|} over the n pixels the mask keeps
+ * (all, without one): IE = sqrt(mean(d^2)) (utils.IE), NE = sqrt(mean(d^2 / (gx^2 + gy^2 +
+ * ne_eps))), d = 255 I - 255 T, (gx, gy) the gradient of 255 T, central in the interior and
+ * one-sided at the border (np.gradient's default; 0 along an axis of length 1).  n = 0: NaN.
+ * FOTO_ERR_ARG: a null pointer, count outside 1..FOTO_SCORE_MAX_RECORDS, stride_rec <= 0, anything
+ * foto_image_check rejects, an ne_eps that is negative or not finite, a pointer that is not device
+ * memory of the current device, a table that overlaps an input.                                 */
+int foto_score_frames_dev(const foto_image* frames, int count, int64_t stride_rec, const foto_image* truth,
+                          const foto_image* mask_or_null, int w, int h, double ne_eps, double* table4, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,13 @@ __device__ __forceinline__ void inv_step(const double* __restrict__ P, int Nx, i
     }
 }
 
+// Middlebury's unknown-flow marker (UNKNOWN_FLOW_THRESH of its flowIO): such a pixel is black in
+// the colour code (foto_render.hip) and not evaluated by the scorer (foto_score.hip)
+constexpr double UNKNOWN_FLOW_THRESH = 1e9;
+__device__ __forceinline__ bool flow_unknown(double u, double v) {
+    return fabs(u) > UNKNOWN_FLOW_THRESH || fabs(v) > UNKNOWN_FLOW_THRESH || u != u || v != v;
+}
+
 // ----------------------------------------------------------------------------- backward warp
 // One output pixel (row i, column j) of utils.apply_opticalflow (utils.py:186-248) in a w x h
 // frame, displacement (u, v): the four bilinear weights and the clamped taps, rows a, a1 and

@@ -392,6 +392,10 @@ hipError_t launch_interp(const double* const* table, int Nt, int Nx, int Ny, con
 int maps_arg_check(const double* s, const void* out, int count, int inv_iters, int Nt, const char* who);
 int interp_frame_check(const foto_image* f, int channels, int64_t stride_c, int w, int h, const char* who);
 size_t interp_frame_bytes(const foto_image* f, int channels, int64_t stride_c, int w, int h);   // all channels
+// a flow descriptor for w x h records (foto_render.hip; foto_flow_check's rules, host-only) and
+// the bytes it covers
+int flow_check(const foto_flow* fl, int w, int h, const char* who);
+size_t flow_bytes(const foto_flow* fl, int w, int h);
 inline bool overlaps(const void* a, size_t na, const void* b, size_t nb) {   // byte ranges
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a0 < b0 + nb && b0 < a0 + na;

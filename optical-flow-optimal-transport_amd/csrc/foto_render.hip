@@ -208,11 +208,6 @@ constexpr Wheel make_wheel() {
 }
 __constant__ Wheel WHEEL = make_wheel();
 
-constexpr double UNKNOWN_FLOW_THRESH = 1e9;
-__device__ __forceinline__ bool flow_unknown(double u, double v) {
-    return fabs(u) > UNKNOWN_FLOW_THRESH || fabs(v) > UNKNOWN_FLOW_THRESH || u != u || v != v;
-}
-
 // mr[k] = max over the known pixels of record k = blockIdx.y of sqrt(u u + v v), mr zeroed before
 // the launch.  The maximum does not depend on the order, and a non-negative double orders like
 // its bit pattern: a block tree, then one 64-bit unsigned atomic max per block.
@@ -285,6 +280,9 @@ __global__ __launch_bounds__(NT) void k_render_color(const Tf* __restrict__ flow
 
 // ----------------------------------------------------------------------------- host side
 
+}  // namespace
+
+// (foto_internal.h: the scorer, foto_score.hip, reads the same descriptors)
 int flow_check(const foto_flow* fl, int w, int h, const char* who) {
     if (!fl) { set_error("%s: null flow descriptor", who); return FOTO_ERR_ARG; }
     if (w < 1 || h < 1) { set_error("%s: w = %d, h = %d: both must be >= 1", who, w, h); return FOTO_ERR_ARG; }
@@ -308,6 +306,8 @@ int flow_check(const foto_flow* fl, int w, int h, const char* who) {
 size_t flow_bytes(const foto_flow* fl, int w, int h) {
     return (size_t)fl->records * (fl->layout == 0 ? 3 : 2) * (size_t)w * (size_t)h * dtype_bytes(fl->dtype);
 }
+
+namespace {
 
 // One stream, link and maxrad scratch per device, kept for the process like the EvSlots of
 // foto_eval.hip.  The calls only enqueue: the stream is never handed back to the pool, so nothing

@@ -147,6 +147,23 @@ class Flow(ctypes.Structure):
     ]
 
 
+FOTO_SCORE_COLS, FOTO_SCORE_MAX_RECORDS = 32, 65535   # (include/foto.h, scoring)
+
+
+class ScoreOpts(ctypes.Structure):
+    """foto_score_opts (include/foto.h): the cap, thresholds and percentiles of a flow score."""
+    _fields_ = [
+        ("ee_cap", ctypes.c_double),
+        ("n_ee_thr", ctypes.c_int),
+        ("n_ae_thr", ctypes.c_int),
+        ("n_pct", ctypes.c_int),
+        ("reserved", ctypes.c_int),
+        ("ee_thr", ctypes.c_double * 4),
+        ("ae_thr", ctypes.c_double * 4),
+        ("pct", ctypes.c_double * 4),
+    ]
+
+
 ITER_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int)
 
 _D = ctypes.POINTER(ctypes.c_double)
@@ -258,6 +275,16 @@ SIGNATURES = {
                                   _P]),
     "foto_render_lum_dev": (_I, [ctypes.POINTER(Flow), _I, _I, _P, _P]),
     "foto_render_color_dev": (_I, [ctypes.POINTER(Flow), _I, _I, _Dbl, _P, _P, _P]),
+    # scoring: flow and frame buffers -> statistics tables on the device
+    "foto_score_opts_default": (_I, [ctypes.POINTER(ScoreOpts)]),
+    "foto_score_check": (_I, [ctypes.POINTER(Flow), ctypes.POINTER(Flow), ctypes.POINTER(Image), _I, _I,
+                              ctypes.POINTER(ScoreOpts)]),
+    "foto_score_flow_dev": (_I, [ctypes.POINTER(Flow), ctypes.POINTER(Flow), ctypes.POINTER(Image), _I, _I,
+                                 ctypes.POINTER(ScoreOpts), _P, _P, _I, _P]),
+    "foto_score_flow": (_I, [ctypes.POINTER(Flow), ctypes.POINTER(Flow), ctypes.POINTER(Image), _I, _I,
+                             ctypes.POINTER(ScoreOpts), _P, _P, _I]),
+    "foto_score_frames_dev": (_I, [ctypes.POINTER(Image), _I, ctypes.c_int64, ctypes.POINTER(Image),
+                                   ctypes.POINTER(Image), _I, _I, _Dbl, _P, _P]),
 }
 
 _lib = None

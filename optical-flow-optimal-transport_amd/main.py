@@ -49,7 +49,26 @@ def build_parser():
                         "interior times (0: none)")
     p.add_argument("--save-inbetweens", default=None,
                    help="FOTO: prefix of the in-between PNGs, written as PREFIX001.png, PREFIX002.png, ...")
+    p.add_argument("--stats", action="store_true",
+                   help="with --ground-truth: also the robustness R0.5 / R1.0 / R2.0 and the accuracy percentiles "
+                        "A50 / A75 / A95 of EE, and the AE twins (R2.5 / R5.0 / R10.0, degrees), after the "
+                        "reference's lines")
     return p
+
+
+def stats_lines(w, h, u, v, uGT, vGT):
+    """The extra benchmark lines of --stats, as (name, value) pairs: foto.evaluate.score_flow on the
+    solved flow and the .flo payload, AE in degrees."""
+    from foto import evaluate
+    flow = np.stack([np.asarray(x, dtype=np.float64).reshape(h, w) for x in (u, v, np.zeros(w * h))])
+    gt = np.ascontiguousarray(np.stack([uGT, vGT], axis=-1).reshape(h, w, 2))
+    s = evaluate.score_flow(flow, gt)
+    deg = s.ae_degrees()
+    lines = [(f"EE-R{t}", r) for t, r in zip(s.ee_thresholds, s.ee_R)]
+    lines += [(f"EE-A{p:g}", a) for p, a in zip(s.percentiles, s.ee_A)]
+    lines += [(f"AE-R{d}", r) for d, r in zip((2.5, 5.0, 10.0), s.ae_R)]
+    lines += [(f"AE-A{p:g}", a) for p, a in zip(s.percentiles, deg["A"])]
+    return [(k, float(x)) for k, x in lines]
 
 
 def _save_gray(img, w, h, path):
@@ -144,6 +163,9 @@ def main(argv=None, writer=None):
         print(" - EE-stddev: " + str(SDEE))
         print(" - AE-mean: " + str(AAE))
         print(" - AE-stddev: " + str(SDAE))
+        extra = stats_lines(w, h, u, v, uGT, vGT) if args.stats else []
+        for name, x in extra:
+            print(" - " + name + ": " + str(x))
 
     if args.save_benchmark:
         with open(args.save_benchmark, "w") as f:
@@ -154,6 +176,9 @@ def main(argv=None, writer=None):
                 f.write("AE-stddev: " + str(SDAE) + "\n")
             f.write("IE: " + str(IE) + "\n")
             f.write("time: " + str(timer) + "s")
+            if args.ground_truth and args.stats:   # (after the reference's lines, whose last has no newline)
+                for name, x in extra:
+                    f.write("\n" + name + ": " + str(x))
 
     if args.out:
         print("saving flo file...")
