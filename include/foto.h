@@ -794,6 +794,73 @@ int foto_score_flow(const foto_flow* fl, const foto_flow* gt, const foto_image* 
 int foto_score_frames_dev(const foto_image* frames, int count, int64_t stride_rec, const foto_image* truth,
                           const foto_image* mask_or_null, int w, int h, double ne_eps, double* table4, void* stream);
 
+/* ------------------------------------------------------------------ flow algebra
+ * For a caller with K + 1 frames and K pair flows: the composed flow frame 0 -> frame k, the
+ * backward flow of a forward flow, and the forward-backward cross-check whose mask is the one
+ * foto_score_flow_dev takes (non-zero = evaluate).  Per-pixel gathers on the foto_flow buffers the
+ * entries above leave in HBM; nothing in the solvers is involved.  Additive.  The *_dev entries obey
+ * the stream contract of the device-buffer section and never synchronise with the host (but for a
+ * library scratch that has to grow); every device pointer is checked for the CURRENT device before
+ * anything is enqueued; an argument error leaves the outputs untouched.
+ *
+ * Definitions.  Flow values widen to double exactly and all arithmetic is float64.  Pixel p =
+ * (i, j) (column, row) has position (x, y) = (i, j).  S(f; x, y) is the clamped bilinear sample
+ * of a w x h field, w, h >= 2: the coordinate is clamped into the frame, a NaN coordinate gives
+ * NaN (read from in-frame taps), value = (1 - ay) ((1 - ax) f00 + ax f01) + ay ((1 - ax) f10 +
+ * ax f11) on the cell that holds the clamped coordinate (the sample of the coarse-to-fine GN and
+ * of the in-betweens).  The cell and the fractions are computed once per position and serve u, v
+ * and m.  Flow outputs are FOTO_F32 ((float)x, to nearest even) or FOTO_F64, layout 0 or 1, all
+ * index arithmetic int64_t.  The operations are + - * sqrt, comparisons, floor and min / max, so
+ * a restatement in the same order gives the same bits.
+ *
+ * FOTO_ERR_ARG before any device call: anything foto_flow_check rejects for a flow, w or h < 2,
+ * backward records that are neither 1 nor the forward flow's, iters outside [1,
+ * FOTO_INV_ITERS_MAX], an alpha that is negative or not finite, a dtype outside {F32, F64}, a
+ * layout outside {0, 1}, last_only outside {0, 1}, a null or misaligned output (valid and table
+ * are required, err is optional).  FOTO_ERR_ARG after the pointer queries: a pointer that is not
+ * device memory of the current device, an output that overlaps an input or another output (all
+ * three kernels gather: overlap would corrupt the result).                                      */
+/* Host-only validation (no HIP call): foto_flow_check of `a` (and of `b`, when given) for w x h
+ * records, w, h >= 2, and b's records 1 or a's.                                                  */
+int foto_chain_check(const foto_flow* a, const foto_flow* b_or_null, int w, int h);
+/* Record k of `fl` is the flow frame k -> frame k + 1, K = fl->records.  The composed flows
+ *   C_0(p) = F_0(p),   C_k(p) = C_{k-1}(p) + S(F_k; p + C_{k-1}(p))   (u, then v),
+ * one thread per pixel walking the records in order, one launch.  last_only = 0: out holds K
+ * records C_0 .. C_{K-1}; 1: one record, C_{K-1}.  The m plane of a layout-0 output: with layout-0
+ * input the brightness gains multiply along the path,
+ *   M_0 = m_0,   M_k(p) = (1 + M_{k-1}(p)) * (1 + S(m_k; p + C_{k-1}(p))) - 1,
+ * which is a definition of this library, not of the reference (which has no sequences): its
+ * reconstruction scales a frame by (1 + m) (utils.apply_opticalflow), so gains along a path
+ * multiply.  With layout-1 input the m plane is +0.0.  K = 1 copies the input: bit for bit from
+ * F64 to F64, NaN payloads included.  A NaN in a record makes NaN exactly the composed values
+ * whose path samples it.                                                                         */
+int foto_flow_compose_dev(const foto_flow* fl, int w, int h, int last_only, void* out, int out_dtype, int out_layout,
+                          void* stream);
+/* The backward flow B of every record F of `fl`, F(p + B(p)) + B(p) = 0: B <- 0, then
+ * B <- -S(F; p + B) exactly `iters` times (FOTO_INV_ITERS_DEFAULT is the usual choice).  A fixed
+ * count and no convergence test, the rule of the inverse step of foto_bb_maps: the result is a
+ * function of the inputs alone; it converges where F is a contraction (Jacobian norm L < 1: the
+ * residual falls like L^iters), and elsewhere it is still inside every bound above.  One thread
+ * per (pixel, record).  The m plane of a layout-0 output is +0.0.                              */
+int foto_flow_invert_dev(const foto_flow* fl, int w, int h, int iters, void* out, int out_dtype, int out_layout,
+                         void* stream);
+/* The forward-backward cross-check of forward records F and backward records B (as many as F, or
+ * one for every record).  Per pixel: q = p + F(p), Bq = S(B; q), e = (F_u + Bq_u)^2 + (F_v +
+ * Bq_v)^2, and the class is the first that applies of
+ *   3  not finite: one of F_u, F_v, Bq_u, Bq_v is NaN or +-inf;
+ *   2  leaves the frame: q_x < 0, q_x > w - 1, q_y < 0 or q_y > h - 1;
+ *   1  inconsistent: e > alpha1 ((F_u^2 + F_v^2) + (Bq_u^2 + Bq_v^2)) + alpha2;
+ *   0  consistent.
+ * alpha1 = 0.01, alpha2 = 0.5 are the values of Sundaram, Brox, Keutzer (ECCV 2010).
+ * valid_u8: DEVICE uint8 [records][h][w], 1 for class 0 and 0 otherwise.  err_or_null: DEVICE
+ * [records][h][w] of err_dtype FOTO_F32 | FOTO_F64 = sqrt(e), NaN for class 3.  table: DEVICE
+ * double [records][4], the number of pixels of class 0, 1, 2, 3: integer counts summed in a fixed
+ * order, the same bits from call to call.                                                       */
+#define FOTO_CONSISTENCY_ALPHA1 0.01
+#define FOTO_CONSISTENCY_ALPHA2 0.5
+int foto_flow_consistency_dev(const foto_flow* fwd, const foto_flow* bwd, int w, int h, double alpha1, double alpha2,
+                              void* valid_u8, void* err_or_null, int err_dtype, double* table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,7 @@ class Flow(ctypes.Structure):
 
 
 FOTO_SCORE_COLS, FOTO_SCORE_MAX_RECORDS = 32, 65535   # (include/foto.h, scoring)
+FOTO_CONSISTENCY_ALPHA1, FOTO_CONSISTENCY_ALPHA2 = 0.01, 0.5   # (include/foto.h, flow algebra)
 
 
 class ScoreOpts(ctypes.Structure):
@@ -285,6 +286,12 @@ SIGNATURES = {
                              ctypes.POINTER(ScoreOpts), _P, _P, _I]),
     "foto_score_frames_dev": (_I, [ctypes.POINTER(Image), _I, ctypes.c_int64, ctypes.POINTER(Image),
                                    ctypes.POINTER(Image), _I, _I, _Dbl, _P, _P]),
+    # flow algebra: compose, invert and cross-check flow buffers on the device
+    "foto_chain_check": (_I, [ctypes.POINTER(Flow), ctypes.POINTER(Flow), _I, _I]),
+    "foto_flow_compose_dev": (_I, [ctypes.POINTER(Flow), _I, _I, _I, _P, _I, _I, _P]),
+    "foto_flow_invert_dev": (_I, [ctypes.POINTER(Flow), _I, _I, _I, _P, _I, _I, _P]),
+    "foto_flow_consistency_dev": (_I, [ctypes.POINTER(Flow), ctypes.POINTER(Flow), _I, _I, _Dbl, _Dbl, _P, _P, _I, _P,
+                                       _P]),
 }
 
 _lib = None

@@ -476,6 +476,25 @@ def bb_flow(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100
                       lambda s, st: s.flow_device(out=out, dtype=dtype, layout=layout, stream=st))
 
 
+def bb_sequence(frames, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, normalize=False,
+                dtype="float32", layout="planar", out=None, stream=None, **opts):
+    """bb_flow for every consecutive pair of ``frames`` -- a sequence of K + 1 device frames (or one
+    (K + 1, h, w) device array) -- into one flow buffer of K records, [K][3][h][w] planar or
+    [K][h][w][2] interleaved: record k is bb_flow(frames[k], frames[k + 1]), exported into its view
+    of the buffer by the one cached context, reset per pair.  Returns the DeviceArray (or ``out``):
+    what ``foto.chain.compose`` takes as it is."""
+    n = int(frames.shape[0]) if hasattr(frames, "shape") else len(frames)
+    if n < 2:
+        raise ValueError(f"bb_sequence: {n} frames; a sequence has at least 2")
+    frs = [frames[k] for k in range(n)]
+    h, w = as_image(frs[0]).shape
+    out, _, _, _ = path_target(out, dtype, layout, n, h, w)   # (K = n - 1 records)
+    for k in range(n - 1):
+        bb_flow(frs[k], frs[k + 1], Nt, r, convergence_tol, reg_epsilon, max_it, normalize=normalize, dtype=dtype,
+                layout=layout, out=out[k], stream=stream, **opts)
+    return out
+
+
 def bb_path(f0, f1, Nt, r=1.0, convergence_tol=0.3, reg_epsilon=1e-3, max_it=100, *, frames=None, normalize=False,
             frame_dtype="float32", dtype="float32", layout="planar", frames_out=None, out=None, stream=None,
             **opts):

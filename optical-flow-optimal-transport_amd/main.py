@@ -53,6 +53,10 @@ def build_parser():
                    help="with --ground-truth: also the robustness R0.5 / R1.0 / R2.0 and the accuracy percentiles "
                         "A50 / A75 / A95 of EE, and the AE twins (R2.5 / R5.0 / R10.0, degrees), after the "
                         "reference's lines")
+    p.add_argument("--save-consistency", default=None,
+                   help="file output of the forward-backward consistency mask (255 = consistent); the backward flow "
+                        "is the solved transport read backwards (FOTO) or a second solve with the frames swapped "
+                        "(GN); also prints the four class counts")
     return p
 
 
@@ -69,6 +73,17 @@ def stats_lines(w, h, u, v, uGT, vGT):
     lines += [(f"AE-R{d}", r) for d, r in zip((2.5, 5.0, 10.0), s.ae_R)]
     lines += [(f"AE-A{p:g}", a) for p, a in zip(s.percentiles, deg["A"])]
     return [(k, float(x)) for k, x in lines]
+
+
+def consistency_mask(w, h, u, v, bu, bv):
+    """(255 * valid as uint8 (h, w), the four class counts) of the forward flow (u, v) against the
+    backward flow (bu, bv): foto.chain.consistency with its default thresholds."""
+    from foto import chain
+    z = np.zeros((h, w))
+    fwd = np.stack([np.asarray(x, dtype=np.float64).reshape(h, w) for x in (u, v)] + [z])
+    bwd = np.stack([np.asarray(x, dtype=np.float64).reshape(h, w) for x in (bu, bv)] + [z])
+    valid, table = chain.consistency(fwd, bwd)
+    return np.uint8(255) * valid, [int(c) for c in table]
 
 
 def _save_gray(img, w, h, path):
@@ -125,10 +140,19 @@ def main(argv=None, writer=None):
         opts = {"device": args.device}
         if args.cg_mode is not None:
             opts["cg_mode"] = args.cg_mode
-        inbetweens = []
+        inbetweens, backward = [], []
         if args.inbetweens > 0 and args.save_inbetweens:   # (on the solved context, after the flow extraction)
             c0, c1 = _open_u8(args.f0), _open_u8(args.f1)
             opts["then"] = lambda s: inbetweens.append(s.interpolate(c0, c1, inbetween_times(args.inbetweens, args.Nt)))
+        if args.save_consistency:   # (the a-planes of the maps at the last plane: frame 1 -> frame 0, a - p)
+            first = opts.get("then")
+
+            def then(s):
+                if first is not None:
+                    first(s)
+                backward.append(s.maps([args.Nt - 1])[0, :2])
+
+            opts["then"] = then
         u, v, m = benamou_brenier.solve(rho1, rho2, args.Nt, w, h, r=args.r, convergence_tol=args.convergence_tol,
                                         reg_epsilon=args.reg_epsilon, max_it=args.max_it, **opts)
     elif args.algo == "GN":
@@ -191,6 +215,16 @@ def main(argv=None, writer=None):
     if args.save_lum:
         print("saving luminosity...")
         emit(_save_gray, np.uint8(255 * np.clip((m + 1) / 2, 0, 1)), w, h, args.save_lum)
+
+    if args.save_consistency:
+        print("saving consistency mask...")
+        if args.algo == "GN":   # (after the timer: the second solve is not part of the benchmark)
+            bu, bv, _ = gn.assemble(rho2, rho1).process()
+        else:
+            bu, bv = backward[0]
+        mask, counts = consistency_mask(w, h, u, v, bu, bv)
+        print(" - consistent / inconsistent / leaves the frame / not finite: " + " / ".join(str(c) for c in counts))
+        emit(_save_gray, mask, w, h, args.save_consistency)
 
     if args.algo == "foto" and inbetweens:
         print("saving in-betweens...")
