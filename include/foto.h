@@ -861,6 +861,94 @@ int foto_flow_invert_dev(const foto_flow* fl, int w, int h, int iters, void* out
 int foto_flow_consistency_dev(const foto_flow* fwd, const foto_flow* bwd, int w, int h, double alpha1, double alpha2,
                               void* valid_u8, void* err_or_null, int err_dtype, double* table, void* stream);
 
+/* ------------------------------------------------------------------ flow filtering
+ * The last stage of a classical flow pipeline on the foto_flow buffers the entries above leave in
+ * HBM: the edge-aware weighted median of Sun, Roth and Black ("Secrets of optical flow estimation",
+ * CVPR 2010), guided by an image, and the same operator with unusable pixels given weight zero,
+ * which fills holes -- the pixels the mask of foto_flow_consistency_dev rejects -- from their usable
+ * neighbours.  Additive; nothing in the solvers is involved and the reference has no such stage.
+ * foto_flow_median_dev obeys the stream contract of the device-buffer section and never
+ * synchronises with the host (but for a library scratch that has to grow); every device pointer is
+ * checked for the CURRENT device before anything is enqueued; an argument error leaves the outputs
+ * untouched.
+ *
+ * Inputs.  A foto_flow (F32 / F64, layout 0 / 1, K records) of w x h pixels, w, h >= 1.  An optional
+ * guide: a foto_image that describes channel 0, `channels` >= 1 and stride_c as in
+ * foto_render_warp_dev; a guide value is (double)pixel / divisor.  An optional mask, a foto_image,
+ * non-zero = usable (foto_score_flow_dev's rule: the valid_u8 of foto_flow_consistency_dev goes in
+ * as it is).  Guide and mask serve every record.
+ *
+ * Per record, rounds t = 1 .. rounds.  F_0 is the input widened exactly to double.  A pixel q is
+ * USABLE in V_0 iff u_q and v_q are both finite and the mask, when given, is non-zero at q.
+ *   window   for pixel p = (i, j) the q = (i + dx, j + dy), |dx|, |dy| <= R, that lie inside the
+ *            frame: windows are truncated at the border, nothing is padded or mirrored.
+ *   weight   a uint32: w(p, q) = spatial[dy + R][dx + R] * G(p, q) if q is usable in V_{t-1}, else
+ *            0.  Without a guide G = 1.  With one, d = max over the channels of |I_c(q) - I_c(p)|
+ *            (NaN if any of them is NaN), idx = min(n_range - 1, (int64)floor(d * range_scale +
+ *            0.5)), a NaN d gives n_range - 1, and G = range[idx].  `spatial` and `range` are the
+ *            caller's uint16 tables: the device never evaluates exp.
+ *   median   T = the sum of w(p, q) over the window, an exact integer (at most 225 * 65535^2 <
+ *            2^40).  For u and v separately the candidates are ordered by the monotone 64-bit key
+ *            of the double, key = bits ^ (sign ? ~0 : 1 << 63), so -0.0 < +0.0 and no tie is
+ *            ambiguous; the result is the value of the smallest key k among the usable candidates
+ *            with 2 * (the sum of w(p, q) over key_q <= k) >= T: the LOWER weighted median, one of
+ *            the samples, whatever the order of summation or the selection algorithm.
+ *   T = 0    p is UNFILLED: F_t(p) = F_{t-1}(p) and p is not in V_t.
+ *   T > 0    p is in V_t and F_t(p) is the median; with fill_only = 1 a p already in V_{t-1} keeps
+ *            F_{t-1}(p) bit for bit and only unusable pixels are replaced.
+ * foto_filter_check enforces spatial[R][R] > 0 and range[0] > 0, so a usable pixel always has T > 0
+ * and V only grows.  The round count is fixed: no convergence test and no host synchronisation
+ * (foto_flow_invert_dev's rule).  Between the rounds the flow lives as float64 with its mask in a
+ * grow-only scratch of the library (17 bytes per pixel and record, twice); the conversion to
+ * out_dtype happens after the last round only.
+ *
+ * Outputs.  out: K records of out_dtype FOTO_F32 ((float)x) or FOTO_F64, layout 0 or 1, = F_rounds.
+ * The m plane of a layout-0 output is the input's m passed through (F64 to F64 bit for bit; the
+ * filter acts on the motion only); of a layout-1 input, +0.0.  valid_out_or_null: DEVICE uint8
+ * [K][h][w] = V_rounds.  table_or_null: DEVICE double [K][4] = {usable in V_0, filled (not in V_0,
+ * in V_rounds), unfilled (not in V_rounds), 0}: integer counts summed in a fixed order, the same
+ * bits from call to call.
+ *
+ * FOTO_ERR_ARG before any device call: anything foto_flow_check rejects, anything
+ * foto_image_check rejects for the mask or a guide channel, channels < 1 or stride_c <= 0 with a
+ * guide, a null opts, radius outside [1, FOTO_MEDIAN_MAX_RADIUS], rounds outside [1,
+ * FOTO_MEDIAN_MAX_ROUNDS], fill_only outside {0, 1}, n_range outside [1, FOTO_MEDIAN_MAX_RANGE], a
+ * range_scale that is not finite and > 0, spatial[R][R] = 0 or range[0] = 0, an out_dtype outside
+ * {F32, F64}, an out_layout outside {0, 1}, a null or misaligned out, a misaligned table.
+ * FOTO_ERR_ARG after the pointer queries: a pointer that is not device memory of the current
+ * device, an output that overlaps an input or another output (the kernel gathers).  All index
+ * arithmetic is int64_t.
+ *
+ * The kernel works on FOTO_MEDIAN_TILE_W x FOTO_MEDIAN_TILE_H pixel tiles, each staged on chip
+ * with its R-wide halo (csrc/foto_filter.hip); the constants are here for the tests,
+ * whose frame sizes derive from them, and are no part of the contract.                          */
+#define FOTO_MEDIAN_MAX_RADIUS 7
+#define FOTO_MEDIAN_MAX_ROUNDS 64
+#define FOTO_MEDIAN_MAX_RANGE 256
+#define FOTO_MEDIAN_TILE_W 32
+#define FOTO_MEDIAN_TILE_H 8
+typedef struct {
+    int radius;          /* 1..7                                                      default 2 */
+    int rounds;          /* 1..64                                                     default 1 */
+    int fill_only;       /* 0 | 1                                                     default 0 */
+    int n_range;         /* 1..256 entries of range[] in use                          default 1 */
+    double range_scale;  /* finite, > 0: guide difference -> index of range[]       default 255 */
+    uint16_t spatial[15 * 15];   /* row-major [2R+1][2R+1], the first (2R+1)^2 entries: default 1 */
+    uint16_t range[256];         /*                                                   default 1 */
+} foto_median_opts;
+/* R = 2, 1 round, fill_only = 0, n_range = 1, range_scale = 255, every weight 1.                */
+int foto_median_opts_default(foto_median_opts* o);
+/* Host-only validation (no HIP call) of everything foto_flow_median_dev takes by descriptor: the
+ * first list above up to range[0].                                                             */
+int foto_filter_check(const foto_flow* fl, const foto_image* guide_or_null, int channels, int64_t stride_c,
+                      const foto_image* mask_or_null, int w, int h, const foto_median_opts* opts);
+/* The filter defined above, all records and one round per launch.  The options travel to the
+ * kernel by value as a kernel argument: no upload, no wait.                                    */
+int foto_flow_median_dev(const foto_flow* fl, const foto_image* guide_or_null, int channels, int64_t stride_c,
+                         const foto_image* mask_or_null, int w, int h, const foto_median_opts* opts,
+                         void* out, int out_dtype, int out_layout, void* valid_out_or_null, double* table_or_null,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,25 @@ class ScoreOpts(ctypes.Structure):
     ]
 
 
+# (include/foto.h, flow filtering)
+FOTO_MEDIAN_MAX_RADIUS, FOTO_MEDIAN_MAX_ROUNDS, FOTO_MEDIAN_MAX_RANGE = 7, 64, 256
+FOTO_MEDIAN_TILE_W, FOTO_MEDIAN_TILE_H = 32, 8   # the kernel's tile: the tests' frame sizes derive from it
+
+
+class MedianOpts(ctypes.Structure):
+    """foto_median_opts (include/foto.h): radius, rounds and the two integer weight tables of the
+    weighted median."""
+    _fields_ = [
+        ("radius", ctypes.c_int),
+        ("rounds", ctypes.c_int),
+        ("fill_only", ctypes.c_int),
+        ("n_range", ctypes.c_int),
+        ("range_scale", ctypes.c_double),
+        ("spatial", ctypes.c_uint16 * (15 * 15)),
+        ("range", ctypes.c_uint16 * 256),
+    ]
+
+
 ITER_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int)
 
 _D = ctypes.POINTER(ctypes.c_double)
@@ -292,6 +311,12 @@ SIGNATURES = {
     "foto_flow_invert_dev": (_I, [ctypes.POINTER(Flow), _I, _I, _I, _P, _I, _I, _P]),
     "foto_flow_consistency_dev": (_I, [ctypes.POINTER(Flow), ctypes.POINTER(Flow), _I, _I, _Dbl, _Dbl, _P, _P, _I, _P,
                                        _P]),
+    # flow filtering: the guided weighted median and hole filling of flow buffers
+    "foto_median_opts_default": (_I, [ctypes.POINTER(MedianOpts)]),
+    "foto_filter_check": (_I, [ctypes.POINTER(Flow), ctypes.POINTER(Image), _I, ctypes.c_int64, ctypes.POINTER(Image),
+                               _I, _I, ctypes.POINTER(MedianOpts)]),
+    "foto_flow_median_dev": (_I, [ctypes.POINTER(Flow), ctypes.POINTER(Image), _I, ctypes.c_int64,
+                                  ctypes.POINTER(Image), _I, _I, ctypes.POINTER(MedianOpts), _P, _I, _I, _P, _P, _P]),
 }
 
 _lib = None

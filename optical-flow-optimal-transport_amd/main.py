@@ -57,6 +57,15 @@ def build_parser():
                    help="file output of the forward-backward consistency mask (255 = consistent); the backward flow "
                         "is the solved transport read backwards (FOTO) or a second solve with the frames swapped "
                         "(GN); also prints the four class counts")
+    p.add_argument("--median", type=int, default=0, choices=range(0, 8), metavar="R",
+                   help="radius R (1..7) of a weighted median of the solved flow, guided by frame 0, applied before "
+                        "the flow is written and evaluated (0: none)")
+    p.add_argument("--median-rounds", type=int, default=1, choices=range(1, 65), metavar="N",
+                   help="rounds of --median (1..64)")
+    p.add_argument("--fill-occluded", action="store_true",
+                   help="mask the flow by the forward-backward check of --save-consistency (the --median, if any, then "
+                        "ignores the rejected pixels) and fill the rejected pixels from their neighbours; prints the "
+                        "filled and unfilled counts")
     return p
 
 
@@ -84,6 +93,37 @@ def consistency_mask(w, h, u, v, bu, bv):
     bwd = np.stack([np.asarray(x, dtype=np.float64).reshape(h, w) for x in (bu, bv)] + [z])
     valid, table = chain.consistency(fwd, bwd)
     return np.uint8(255) * valid, [int(c) for c in table]
+
+
+MEDIAN_SIGMA_R = 0.08     # the range term of --median / --fill-occluded, of the [0, 1] grey scale
+FILL_RADIUS = 2           # --fill-occluded without --median
+
+
+def median_tables(radius):
+    """The weight tables of --median R: a Gaussian of sigma R in space, of MEDIAN_SIGMA_R in grey value."""
+    from foto import filter as flt
+    return flt.tables(radius, sigma_s=float(radius), sigma_r=MEDIAN_SIGMA_R)
+
+
+def postprocess_flow(w, h, u, v, f0, radius=0, rounds=1, valid=None):
+    """(u, v, counts) after --median / --fill-occluded: foto.filter.median of the solved flow guided
+    by frame 0 (``radius`` > 0), masked by ``valid`` when given, then foto.filter.fill of what
+    ``valid`` rejects; counts = (filled, unfilled) with a mask, else None."""
+    from foto import filter as flt
+    flow = np.stack([np.asarray(x, dtype=np.float64).reshape(h, w) for x in (u, v, np.zeros(w * h))])
+    guide = np.asarray(f0, dtype=np.float64).reshape(h, w)
+    usable = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+    if radius > 0:
+        sp, rg = median_tables(radius)
+        flow, usable, _ = flt.median(flow, guide=guide, mask=usable, radius=radius, rounds=rounds, spatial=sp, range=rg)
+    counts = None
+    if valid is not None:
+        r = radius if radius > 0 else FILL_RADIUS
+        sp, rg = median_tables(r)
+        flow, usable, _ = flt.fill(flow, usable, guide=guide, radius=r, spatial=sp, range=rg)
+        rejected = np.asarray(valid) == 0
+        counts = (int(np.count_nonzero(rejected & (usable != 0))), int(np.count_nonzero(usable == 0)))
+    return flow[0].reshape(-1), flow[1].reshape(-1), counts
 
 
 def _save_gray(img, w, h, path):
@@ -144,7 +184,7 @@ def main(argv=None, writer=None):
         if args.inbetweens > 0 and args.save_inbetweens:   # (on the solved context, after the flow extraction)
             c0, c1 = _open_u8(args.f0), _open_u8(args.f1)
             opts["then"] = lambda s: inbetweens.append(s.interpolate(c0, c1, inbetween_times(args.inbetweens, args.Nt)))
-        if args.save_consistency:   # (the a-planes of the maps at the last plane: frame 1 -> frame 0, a - p)
+        if args.save_consistency or args.fill_occluded:   # (the a-planes of the maps at the last plane: frame 1 -> frame 0, a - p)
             first = opts.get("then")
 
             def then(s):
@@ -170,6 +210,27 @@ def main(argv=None, writer=None):
         # reference: `assert("not implemented")` (always true), then NameError on `u` below
         raise NotImplementedError(f"algorithm {args.algo!r} is not implemented (use --algo=foto or --algo=GN)")
     timer = time.time() - start_time
+
+    checked = []
+
+    def cross_check(fu, fv):
+        """(mask, counts) of the solved flow against its backward flow, computed once."""
+        if not checked:
+            if args.algo == "GN":   # (after the timer: the second solve is not part of the benchmark)
+                bu, bv, _ = gn.assemble(rho2, rho1).process()
+            else:
+                bu, bv = backward[0]
+            checked.append(consistency_mask(w, h, fu, fv, bu, bv))
+        return checked[0]
+
+    solved = (u, v)
+    if args.median > 0 or args.fill_occluded:   # (the flow written and evaluated below is the filtered one)
+        valid = (cross_check(*solved)[0] != 0) if args.fill_occluded else None
+        u, v, counts = postprocess_flow(w, h, u, v, f1, args.median, args.median_rounds, valid)
+        if args.median > 0:
+            print(f" - median filter: radius {args.median}, {args.median_rounds} round(s), guided by f0")
+        if counts is not None:
+            print(" - occluded pixels filled / unfilled: " + " / ".join(str(c) for c in counts))
 
     print("Benchmark:")
     rec = utils.apply_opticalflow(f1, u, v, w, h, m)
@@ -218,11 +279,7 @@ def main(argv=None, writer=None):
 
     if args.save_consistency:
         print("saving consistency mask...")
-        if args.algo == "GN":   # (after the timer: the second solve is not part of the benchmark)
-            bu, bv, _ = gn.assemble(rho2, rho1).process()
-        else:
-            bu, bv = backward[0]
-        mask, counts = consistency_mask(w, h, u, v, bu, bv)
+        mask, counts = cross_check(*solved)   # (of the solved flow, before any --median)
         print(" - consistent / inconsistent / leaves the frame / not finite: " + " / ".join(str(c) for c in counts))
         emit(_save_gray, mask, w, h, args.save_consistency)
 
