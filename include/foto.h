@@ -630,6 +630,91 @@ int foto_gn_solve_prior(const double* f1, const double* g, int w, int h, double 
                         int maxiter, const double* u0, const double* v0, const double* m0, double* u, double* v,
                         double* m, int* iterations);
 
+/* ------------------------------------------------------------------------- TV-L1 flow
+ * Duality-based TV-L1 optical flow (Zach, Pock & Bischof 2007) with the illumination channel of
+ * Chambolle & Pock 2011: the classical baseline that keeps motion boundaries sharp, where GN's
+ * quadratic prior smears them.  Pointwise arithmetic plus a 3-point stencil, no linear solve, and
+ * every count fixed: the result is a function of the frames and the options alone.  Float64.
+ * The flow convention is the pyramid's, f1(x) ~ (1 - m) f2(x + u).  Unknowns per pixel
+ * U = (u, v, w); the reported luminosity is m = gamma w.
+ *   pyramid     the sizes of foto_gn_pyr_sizes, the restriction, S and the prolongation above;
+ *               coarsest level first, from U = 0; every other level from the prolonged (u, v, w),
+ *               u and v scaled by the size ratio, w unscaled; the dual variables P (two per
+ *               channel) start at zero on every level and are kept across the warps of a level;
+ *   per warp    at the current U0: g = S(f2; x + u0, y + v0), a1 = S(Gx f2; .), a2 = S(Gy f2; .)
+ *               at the same positions, a3 = -gamma g, n2 = (a1^2 + a2^2) + a3^2,
+ *               rc = ((g - f1) - a1 u0) - a2 v0; Gx f [j][i] = 0.5 (f[j][i+1] - f[j][i-1]), zero
+ *               in the first and last column, Gy likewise in y;
+ *   per inner   rho = ((rc + a1 u) + a2 v) + a3 w, from all three channels before any changes;
+ *   iteration   k = lambda theta where rho < -lambda theta n2, -lambda theta where
+ *               rho > lambda theta n2, elsewhere -rho / n2 if n2 > 1e-12, else 0; then for each
+ *               channel d: U_d <- (U_d + k a_d) + theta div(P_d); (dx, dy) = fwd(U_d);
+ *               P_d <- (P_d + (tau / theta) (dx, dy)) / (1 + (tau / theta) sqrt(dx^2 + dy^2));
+ *   fwd, div    fwd: the forward difference, zero in the last column / row; div = minus its
+ *               adjoint: px[0] in the first column, px[i] - px[i-1] inside, -px[w-2] in the last
+ *               one, the same in y, x part + y part.
+ * lambda is for frames in [0, 1] (the paper's 0.15 is for [0, 255]).  gamma = 0 switches the
+ * illumination channel off and leaves w, and so m, exactly zero.                              */
+typedef struct {
+    double lambda;   /* data weight                                                   default 38 */
+    double theta;    /* coupling of the flow and its auxiliary                       default 0.3 */
+    double tau;      /* dual step                                                   default 0.25 */
+    double gamma;    /* illumination coupling; 0: the channel is off                 default 0.1 */
+    int levels;      /* levels asked for (the sizes rule may build fewer)              default 4 */
+    int warps;       /* linearisations per level                                       default 5 */
+    int iters;       /* inner iterations per warp                                     default 30 */
+    int min_size;    /* as foto_gn_pyr_opts                                           default 16 */
+    int per_launch;  /* inner iterations per kernel launch, 1 .. FOTO_TVL1_MAX_PER_LAUNCH: 1 is
+                        one launch per iteration on global memory, more is that many iterations on
+                        LDS tiles with a halo of as many pixels; the result has the same bits for
+                        every value (DESIGN.md has the measurements)                   default 5 */
+} foto_tvl1_opts;
+#define FOTO_TVL1_MAX_PER_LAUNCH 8
+int foto_tvl1_opts_default(foto_tvl1_opts* o);
+
+/* Report of one solve.  The caller sizes wl / hl / launches / ms_level (cap entries each, any may
+ * be NULL; index = level, finest first).                                                       */
+typedef struct {
+    int cap;                  /* in: entries of the four arrays                                */
+    int* wl;                  /* level sizes                                                   */
+    int* hl;
+    int* launches;            /* kernels launched on the level: its prolongation, `warps`
+                                 coefficient launches, warps * ceil(iters / per_launch)
+                                 iteration launches                                            */
+    double* ms_level;         /* device time per level (the coarsest level's includes the ingest
+                                 and the restrictions)                                         */
+    int levels;               /* levels built                                                  */
+    int launches_total;       /* the sum of `launches` over all levels                          */
+    double ms_total;          /* host wall time of the call                                    */
+} foto_tvl1_stats;
+
+/* The level frames, two copies of U and P and the coefficients, one stream, made once.
+ * FOTO_ERR_ARG (nothing made, nothing enqueued): a null pointer, w or h < 2, theta or tau not
+ * positive and finite, lambda or gamma negative or not finite, levels, warps or iters < 1,
+ * min_size < 2, per_launch outside 1 .. FOTO_TVL1_MAX_PER_LAUNCH.  opts NULL: the defaults.    */
+typedef struct foto_tvl1 foto_tvl1;
+int foto_tvl1_create(int w, int h, const foto_tvl1_opts* opts, foto_tvl1** out);
+void foto_tvl1_destroy(foto_tvl1* p);
+int foto_tvl1_device(const foto_tvl1* p);
+/* Host float64 frames in, u, v, m out (w * h each).  Returns 0, < 0 on error.  stats may be NULL. */
+int foto_tvl1_solve(foto_tvl1* p, const double* f1, const double* f2, double* u, double* v, double* m,
+                    foto_tvl1_stats* stats);
+/* The same on device frames, exported like foto_gn_pyr_solve_dev (same checks, same stream
+ * contract): `out` is a buffer foto_flow describes; its float64 values are foto_tvl1_solve's bit
+ * for bit.  With stats the call waits for the last level's event to read the times.            */
+int foto_tvl1_solve_dev(foto_tvl1* p, const foto_image* f1, const foto_image* f2, void* out, int dtype, int layout,
+                        void* stream, foto_tvl1_stats* stats);
+
+/* The solver's two kernels on host arrays (tests; w, h >= 2).  foto_tvl1_coeffs: one warp's
+ * out5 = [5][w h] = a1, a2, a3, n2, rc from the frames and U0 = (u, v).  foto_tvl1_iterate:
+ * n >= 1 inner iterations on coef5 = [5][w h] as above, U3 = [3][w h] = u, v, w and
+ * P6 = [6][w h] = (px, py) of u, of v, of w, both updated in place, at most per_launch
+ * (1 .. FOTO_TVL1_MAX_PER_LAUNCH) of them in one kernel launch.                               */
+int foto_tvl1_coeffs(const double* f1, const double* f2, const double* u, const double* v, int w, int h,
+                     double gamma, double* out5);
+int foto_tvl1_iterate(const double* coef5, double* U3, double* P6, int w, int h, double lambda, double theta,
+                      double tau, int n, int per_launch);
+
 /* foto_warp / foto_flow_errors / foto_intensity_error (utils.py:186-248, 294-354) on contiguous
  * float64 DEVICE arrays of w * h elements: the same kernels and reduction order without the
  * uploads.  `out` of the warp is a device array (not aliasing an input); the metrics return

@@ -62,6 +62,12 @@ hipError_t launch_gn_rhs_prior(int w, int h, double alpha, double lam, const dou
 // x[i] += x0[i], i < n (foto_gn_pyr.hip)
 hipError_t launch_gn_add(int64_t n, double* x, const double* x0, hipStream_t s);
 
+// The pyramid's grid transfers (foto_gn_pyr.hip), shared with the TV-L1 solver (foto_tvl1.hip):
+// both frames of a w x h level restricted to ceil(w/2) x ceil(h/2); [3][wc hc] = u, v, m prolonged
+// to [3][w h] with the displacement scales (m unscaled)
+hipError_t launch_pyr_down(int w, int h, const double* f1, const double* f2, double* c1, double* c2, hipStream_t s);
+hipError_t launch_pyr_up(int wc, int hc, int w, int h, const double* c, double* o, hipStream_t s);
+
 // foto_gn_plan_create's plan on `shared` (null: a stream of its own): the pyramid's plans run on
 // the pyramid's one stream, which the plan then neither synchronises for others nor releases
 int gn_plan_make(int w, int h, double alpha, double lam, double rtol, int maxiter, hipStream_t shared,

@@ -93,14 +93,13 @@ hipError_t launch_gn_add(int64_t n, double* x, const double* x0, hipStream_t s) 
     return hipGetLastError();
 }
 
-static hipError_t launch_pyr_down(int w, int h, const double* f1, const double* f2, double* c1, double* c2,
-                                  hipStream_t s) {
+hipError_t launch_pyr_down(int w, int h, const double* f1, const double* f2, double* c1, double* c2, hipStream_t s) {
     const int wc = (w + 1) / 2, hc = (h + 1) / 2;
     k_pyr_down<<<flat_blocks((int64_t)wc * hc), NT, 0, s>>>(w, h, wc, hc, f1, f2, c1, c2);
     return hipGetLastError();
 }
 
-static hipError_t launch_pyr_up(int wc, int hc, int w, int h, const double* c, double* o, hipStream_t s) {
+hipError_t launch_pyr_up(int wc, int hc, int w, int h, const double* c, double* o, hipStream_t s) {
     k_pyr_up<<<flat_blocks((int64_t)w * h), NT, 0, s>>>(wc, hc, w, h, c, o);
     return hipGetLastError();
 }

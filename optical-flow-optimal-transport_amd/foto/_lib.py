@@ -122,6 +122,38 @@ class GNPyrStats(ctypes.Structure):
     ]
 
 
+class TVL1Opts(ctypes.Structure):
+    """foto_tvl1_opts (include/foto.h)."""
+    _fields_ = [
+        ("lam", ctypes.c_double),   # (`lambda` in C)
+        ("theta", ctypes.c_double),
+        ("tau", ctypes.c_double),
+        ("gamma", ctypes.c_double),
+        ("levels", ctypes.c_int),
+        ("warps", ctypes.c_int),
+        ("iters", ctypes.c_int),
+        ("min_size", ctypes.c_int),
+        ("per_launch", ctypes.c_int),
+    ]
+
+
+FOTO_TVL1_MAX_PER_LAUNCH = 8
+
+
+class TVL1Stats(ctypes.Structure):
+    """foto_tvl1_stats (include/foto.h): the caller sizes the four arrays by cap."""
+    _fields_ = [
+        ("cap", ctypes.c_int),
+        ("wl", ctypes.POINTER(ctypes.c_int)),
+        ("hl", ctypes.POINTER(ctypes.c_int)),
+        ("launches", ctypes.POINTER(ctypes.c_int)),
+        ("ms_level", ctypes.POINTER(ctypes.c_double)),
+        ("levels", ctypes.c_int),
+        ("launches_total", ctypes.c_int),
+        ("ms_total", ctypes.c_double),
+    ]
+
+
 FOTO_U8, FOTO_F32, FOTO_F64 = 0, 1, 2
 FOTO_INV_ITERS_MAX, FOTO_INV_ITERS_DEFAULT = 64, 6   # (include/foto.h, maps and in-betweens)
 
@@ -283,6 +315,16 @@ SIGNATURES = {
     "foto_pyr_up": (_I, [_D, _D, _D, _I, _I, _I, _I, _D, _D, _D]),
     "foto_gn_warp_prior": (_I, [_D, _D, _D, _D, _I, _I, _D]),
     "foto_gn_solve_prior": (_I, [_D, _D, _I, _I, _Dbl, _Dbl, _Dbl, _I, _D, _D, _D, _D, _D, _D, ctypes.POINTER(_I)]),
+    # TV-L1 flow with an illumination channel
+    "foto_tvl1_opts_default": (_I, [ctypes.POINTER(TVL1Opts)]),
+    "foto_tvl1_create": (_I, [_I, _I, ctypes.POINTER(TVL1Opts), ctypes.POINTER(_P)]),
+    "foto_tvl1_destroy": (None, [_P]),
+    "foto_tvl1_device": (_I, [_P]),
+    "foto_tvl1_solve": (_I, [_P, _D, _D, _D, _D, _D, ctypes.POINTER(TVL1Stats)]),
+    "foto_tvl1_solve_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _P, _I, _I, _P,
+                                 ctypes.POINTER(TVL1Stats)]),
+    "foto_tvl1_coeffs": (_I, [_D, _D, _D, _D, _I, _I, _Dbl, _D]),
+    "foto_tvl1_iterate": (_I, [_D, _D, _D, _I, _I, _Dbl, _Dbl, _Dbl, _I, _I]),
     "foto_warp_dev": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "foto_flow_errors_dev": (_I, [_P, _P, _P, _P, _I, _I, _D, _P]),
     "foto_intensity_error_dev": (_I, [_P, _P, _I, _I, _D, _P]),

@@ -561,3 +561,15 @@ def gn_flow(f0, f1, alpha, lam, *, dtype="float32", layout="planar", out=None, s
         return p.solve_device(a, b, out=out, dtype=dtype, layout=layout, stream=stream_handle(stream, f0, f1))[0]
     p = gn.cached_plan(w, h, alpha, lam)
     return p.solve_device(a, b, out=out, dtype=dtype, layout=layout, stream=stream_handle(stream, f0, f1))[0]
+
+
+def tvl1_flow(f0, f1, *, dtype="float32", layout="planar", out=None, stream=None, **opts):
+    """Duality-based TV-L1 flow with an illumination channel on device frames (the solver from
+    foto.tvl1's cache; ``opts`` are foto.tvl1.DEFAULTS' keys); returns the DeviceArray (or ``out``)
+    holding u, v, m: a flow buffer foto.chain, foto.filter, foto.render and foto.evaluate take as
+    it is."""
+    from . import tvl1
+    a, b = _pair(f0, f1)
+    h, w = a.shape
+    p = tvl1.cached_tvl1(w, h, **opts)
+    return p.solve_device(a, b, out=out, dtype=dtype, layout=layout, stream=stream_handle(stream, f0, f1))[0]

@@ -44,6 +44,13 @@ def build_parser():
     p.add_argument("--cg-mode", type=int, default=None, help="0 stencil, 1 spectral, 2 spectral s-step, 3 Gauss-compressed spectral CG (default)")
     p.add_argument("--gn-levels", type=int, default=1, help="GN: pyramid levels (1: the reference's single solve)")
     p.add_argument("--gn-warps", type=int, default=1, help="GN: warped increment solves per pyramid level")
+    p.add_argument("--tv-lambda", type=float, default=38.0, help="TVL1: data weight, for frames in [0, 1]")
+    p.add_argument("--tv-theta", type=float, default=0.3, help="TVL1: coupling of the flow and its auxiliary")
+    p.add_argument("--tv-tau", type=float, default=0.25, help="TVL1: dual step")
+    p.add_argument("--tv-gamma", type=float, default=0.1, help="TVL1: illumination coupling (0: the channel is off)")
+    p.add_argument("--tv-levels", type=int, default=4, help="TVL1: pyramid levels")
+    p.add_argument("--tv-warps", type=int, default=5, help="TVL1: linearisations per pyramid level")
+    p.add_argument("--tv-iters", type=int, default=30, help="TVL1: inner iterations per warp")
     p.add_argument("--inbetweens", type=int, default=0,
                    help="FOTO: motion-compensated in-betweens of the two input frames at this many evenly spaced "
                         "interior times (0: none)")
@@ -206,9 +213,19 @@ def main(argv=None, writer=None):
             print(f"\t - pyramid: {args.gn_levels} levels x {args.gn_warps} warps")
             gn.setPyramid(args.gn_levels, args.gn_warps)
         [u, v, m] = gn.assemble(rho1, rho2).process()
+    elif args.algo == "TVL1":
+        from foto import tvl1
+        tv = dict(lam=args.tv_lambda, theta=args.tv_theta, tau=args.tv_tau, gamma=args.tv_gamma, levels=args.tv_levels,
+                  warps=args.tv_warps, iters=args.tv_iters)
+        print(" - algorithm: TVL1")
+        for name in ("lambda", "theta", "tau", "gamma", "levels", "warps", "iters"):
+            print(f"\t - {name}={tv['lam' if name == 'lambda' else name]}")
+        solver = tvl1.cached_tvl1(w, h, **tv)
+        u, v, m, _ = solver.solve(rho1, rho2)
     else:
         # reference: `assert("not implemented")` (always true), then NameError on `u` below
-        raise NotImplementedError(f"algorithm {args.algo!r} is not implemented (use --algo=foto or --algo=GN)")
+        raise NotImplementedError(f"algorithm {args.algo!r} is not implemented (use --algo=foto, --algo=GN or "
+                                  "--algo=TVL1)")
     timer = time.time() - start_time
 
     checked = []
@@ -218,6 +235,8 @@ def main(argv=None, writer=None):
         if not checked:
             if args.algo == "GN":   # (after the timer: the second solve is not part of the benchmark)
                 bu, bv, _ = gn.assemble(rho2, rho1).process()
+            elif args.algo == "TVL1":
+                bu, bv, _, _ = solver.solve(rho2, rho1)
             else:
                 bu, bv = backward[0]
             checked.append(consistency_mask(w, h, fu, fv, bu, bv))
