@@ -412,7 +412,10 @@ static int ctx_init(foto_bb_ctx* c, const RhoSrc& src) {
     }
     const int nlocal = c->rccl ? 1 : W;
     {
-        c->fuse = c->tn.fuse_pr;   // FOTO_FUSE_PR=0: separate k_prox / k_rhs (A/B runs)
+        Geo plane{};
+        plane.Nx = c->Nx;
+        // FOTO_FUSE_PR=0: separate k_prox / k_rhs (A/B runs; rows beyond the fused kernel's offsets)
+        c->fuse = c->tn.fuse_pr && prox_rhs_fits(plane);
         // FOTO_PIPE=0: one outer iteration in flight (A/B runs)
         c->pipe = W == 1 && c->fuse && c->o.cg_mode == 3 && c->tn.pipe;
         // the crit readback as two stores of k_prox_rhs's last block into the slot (a copy launch

@@ -278,6 +278,9 @@ hipError_t launch_prox(const Geo& g, const double* phi, double* mut, double* mux
 // halo plane, F of that edge plane is left to launch_rhs_edge after w_t's halo exchange
 // (wt_out: a halo-padded field, planes 0, 1, nloc - 2, nloc - 1 written; edge: 2 x 4 planes).
 int prox_rhs_blocks(const Geo& g, int tch);
+// the fused kernel addresses a tile's phi region (12 rows) by 32-bit byte offsets: rows of up to
+// ~2^25 voxels.  Wider grids take the separate k_prox + k_rhs (the same bits per voxel).
+bool prox_rhs_fits(const Geo& g);
 hipError_t launch_prox_rhs(const Geo& g, const double* phi, const double* mut, const double* mux, const double* muy,
                            double* nut, double* nux, double* nuy, const double* rho0, const double* rhoT, double r,
                            double* F, RedBuf rb, double* gath_crit, double* gath_rr, int tch, hipStream_t s,

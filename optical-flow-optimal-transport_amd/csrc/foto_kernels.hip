@@ -16,6 +16,8 @@
 //              and re-reading q), r.r partials.
 // Both finish with a last-block reduction (grid_reduce_last, foto_reduce.h: write-through
 // partials + agent-scope ticket): no extra launch per dot product.
+#include <type_traits>
+
 #include "foto_devutil.h"
 #include "foto_internal.h"
 #include "foto_reduce.h"
@@ -766,15 +768,45 @@ hipError_t launch_q_from_phi(const Geo& g, const double* phi, const double* mut,
 // stepB on plane p (phi planes p - 1 .. p + 1 from the ring) -> w = mu' - r q of plane p into
 // a double-buffered LDS image (x, y parts; the own voxel's t part stays in registers), then
 // F(p - 1) from w of planes p - 2 .. p; one barrier per iteration.  Threads 0..147 (waves
-// 0-2) also take the 148 ring voxels.  Chunks of FOTO_PR_TCH planes (default 16) give the
-// grid more blocks than resident slots (a full-length march leaves a one-sixth-full second
-// round at 640 x 480).
+// 0-2) also take the 148 ring voxels -- on the chunk's own planes only: of the planes l0 - 1 and
+// l1, F reads the own voxels' w_t alone, which stays in registers, so those two iterations load
+// no ring mu, run no ring stepB and write no w image.  Chunks of FOTO_PR_TCH planes (default 16)
+// give the grid more blocks than resident slots (a full-length march leaves a one-sixth-full
+// second round at 640 x 480).
+// The wait for a plane's loads must not wait for the stores issued behind them (vmcnt retires in
+// order: the loads of plane p + 1 go out before the mu' and F stores of plane p).  The compiler
+// counts those stores only where every wave executes them, so the iterations in which every
+// plane condition holds -- the STEADY planes, 24 of the two chunks' 35 iterations at Nt = 32 --
+// run a copy of the iteration without the conditions, and mu(p + 1) alternates between two
+// register sets instead of being copied at the back edge (prox_rhs_body has the bounds and the
+// argument that every wave runs the same barriers).  Not on a deferred-edge shard (EDGE).
+// Addresses: plane base + tile origin in scalar registers, one 32-bit byte offset per voxel and
+// thread for all eight arrays (byte_at, in_loop) instead of a 64-bit address pair per array.
 // Cache policy of the streams.  mu' is read again only by the next outer iteration's prox,
 // ~1.5 GB of other traffic later: stored non-temporal it does not displace the lines the next
 // kernels read (F, phi; F itself is stored plainly, the x-DCT reads it next).  The old mu is dead
 // after this kernel: its loads, the own and the ring voxels', are non-temporal, so F stays cached
 // for the x-DCT.  phi is loaded plainly: its halo is re-read.  (A/B figures: DESIGN.md 3.5.)
 constexpr int PR_X = 64, PR_Y = 8;
+
+// base + a 32-bit byte offset: with a block-uniform base the access takes the base from scalar
+// registers and one VGPR of offset
+template <class T>
+__device__ __forceinline__ T* byte_at(T* base, uint32_t off) {
+    return (T*)((const char*)base + off);
+}
+// ... and stays one: an offset the compiler has to take as new at each use, so that it does not
+// hoist a 64-bit base + offset per array and thread out of the march's loops
+__device__ __forceinline__ uint32_t in_loop(uint32_t off) {
+    asm volatile("" : "+v"(off));
+    return off;
+}
+// a block-uniform element offset, held in scalar registers also where it is used under a lane mask
+__device__ __forceinline__ int64_t uniform64(int64_t v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
 constexpr int PR_VPT = 1;                                   // own voxels per thread (the march is written over v < PR_VPT)
 constexpr int PR_NT = PR_X * PR_Y / PR_VPT;                 // 512 threads (64 x 8)
 constexpr int PR_YV = PR_Y / PR_VPT;                        // rows between a thread's own voxels
@@ -805,17 +837,23 @@ __device__ __forceinline__ void prox_rhs_body(
     const int64_t nxy = g.nxy;
     const int l0 = ch * tch, l1 = min(g.nloc, l0 + tch);   // own planes of this chunk (local)
     const int tid = threadIdx.x;
+    // Global addresses: a plane's base plus the origin of the tile's phi region is block-uniform
+    // (scalar registers); a thread adds the 32-bit byte offset of its voxel inside the region, one
+    // register for every array (prox_rhs_fits holds the region to 2^32 bytes)
+    const int64_t org = (int64_t)(y0 - 2) * Nx + (x0 - 2);
     // own voxels: stepB region positions (1 + tid % 64, 1 + tid / 64 + v PR_YV)
     const int opx = 1 + (tid & (PR_X - 1));
     const int ox = x0 - 1 + opx;
     int opy[PR_VPT], oy[PR_VPT], ooff[PR_VPT];
+    uint32_t oob[PR_VPT];
     bool own[PR_VPT];
 #pragma unroll
     for (int v = 0; v < PR_VPT; ++v) {
         opy[v] = 1 + tid / PR_X + v * PR_YV;
         oy[v] = y0 - 1 + opy[v];
         own[v] = INTERIOR || (ox < Nx && oy[v] < Ny);
-        ooff[v] = own[v] ? oy[v] * Nx + ox : 0;   // in-plane offsets fit 32 bits
+        ooff[v] = own[v] ? oy[v] * Nx + ox : 0;   // in-plane offsets fit 32 bits (the deferred edges')
+        oob[v] = own[v] ? 8u * (uint32_t)((opy[v] + 1) * Nx + opx + 1) : 0u;
     }
     // ring voxel of threads 0..PR_HALO-1
     int hpx = 0, hpy = 0;
@@ -825,9 +863,9 @@ __device__ __forceinline__ void prox_rhs_body(
     else { hpx = PR_PW - 1; hpy = 1 + tid - 2 * PR_PW - PR_Y; }
     const int hx = x0 - 1 + hpx, hy = y0 - 1 + hpy;
     const bool hal = tid < PR_HALO && (INTERIOR || (hx >= 0 && hx < Nx && hy >= 0 && hy < Ny));
-    const int hoff = hal ? hy * Nx + hx : 0;
+    const uint32_t hob = hal ? 8u * (uint32_t)((hpy + 1) * Nx + hpx + 1) : 0u;
     // phi region loads of this thread
-    int foff[PR_FR];
+    uint32_t fob[PR_FR];
     bool fin[PR_FR];
 #pragma unroll
     for (int j = 0; j < PR_FR; ++j) {
@@ -835,56 +873,78 @@ __device__ __forceinline__ void prox_rhs_body(
         const int fy = idx / PR_FW, fx = idx - fy * PR_FW;
         const int xx = x0 - 2 + fx, yy = y0 - 2 + fy;
         fin[j] = idx < PR_FN && (INTERIOR || (xx >= 0 && xx < Nx && yy >= 0 && yy < Ny));
-        foff[j] = fin[j] ? yy * Nx + xx : 0;
+        fob[j] = fin[j] ? 8u * (uint32_t)(fy * Nx + fx) : 0u;
     }
     // stepB planes (local): one beyond the chunk on each side, within the grid and, where an edge
     // is deferred, within the shard
     if (!EDGE) defer_lo = defer_hi = 0;
     const int pa = max(l0 - 1, defer_lo ? 0 : -t0), pz = min(l1, defer_hi ? g.nloc - 1 : Nt - 1 - t0);
     const int nl = g.nloc;
+    // the steady planes: every condition of a step folds (below); none on a deferred-edge shard
+    const int ps = max(l0 + 1, 2 - t0), pe = EDGE ? ps - 1 : min(pz - 2, Nt - 4 - t0);
     double fv[PR_FR];
-    auto load_phi_to = [&](int p, double (&v)[PR_FR]) {   // planes beyond pz + 1 are never read
-        const bool ok = t0 + p >= 0 && p <= pz + 1 && t0 + p < Nt;
+    // ST: a steady plane, in the grid by construction
+    auto load_phi_to = [&](auto st, int p, double (&v)[PR_FR]) {   // planes beyond pz + 1 are never read
+        constexpr bool ST = decltype(st)::value;
+        const bool ok = ST || (t0 + p >= 0 && p <= pz + 1 && t0 + p < Nt);
+        const int64_t pb = uniform64(p * nxy + org);
 #pragma unroll
         for (int j = 0; j < PR_FR; ++j)
-            v[j] = (ok && fin[j]) ? phi[p * nxy + foff[j]] : 0.0;
+            v[j] = (ok && fin[j]) ? *byte_at(phi + pb, in_loop(fob[j])) : 0.0;
     };
     auto store_phi_from = [&](int p, const double (&v)[PR_FR]) {
 #pragma unroll
         for (int j = 0; j < PR_FR; ++j)
             if (tid + j * PR_NT < PR_FN) fr[p & 3][tid + j * PR_NT] = v[j];
     };
-    auto load_phi = [&](int p) { load_phi_to(p, fv); };
     auto store_phi = [&](int p) { store_phi_from(p, fv); };
-    // mu of the own and the ring voxels, one plane ahead
-    double om[PR_VPT][3], hm[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int v = 0; v < PR_VPT; ++v) om[v][0] = om[v][1] = om[v][2] = 0.0;
-    auto load_mu = [&](int p) {
-        if (p > pz) return;
+    // mu of plane p, loaded one plane ahead: the ring voxels' (first: the own voxels' loads are the
+    // unconditional ones a wait can count from) only on the chunk's own planes -- F(n) exists for
+    // n in [l0, l1) and reads the ring's w of plane n alone -- then the own voxels'
+    auto load_mu = [&](auto st, int p, double (&mo)[PR_VPT][3], double (&mh)[3]) {
+        constexpr bool ST = decltype(st)::value;
+        if (!ST && p > pz) return;
+        const int64_t pb = uniform64(p * nxy + org);
+        if (hal && (ST || (p >= l0 && p < l1))) {
+            const uint32_t o = in_loop(hob);
+            mh[0] = __builtin_nontemporal_load(byte_at(mut + pb, o));
+            mh[1] = __builtin_nontemporal_load(byte_at(mux + pb, o));
+            mh[2] = __builtin_nontemporal_load(byte_at(muy + pb, o));
+        }
 #pragma unroll
         for (int v = 0; v < PR_VPT; ++v) {
             if (own[v]) {   // (the old mu is dead after this kernel)
-                om[v][0] = __builtin_nontemporal_load(&mut[p * nxy + ooff[v]]);
-                om[v][1] = __builtin_nontemporal_load(&mux[p * nxy + ooff[v]]);
-                om[v][2] = __builtin_nontemporal_load(&muy[p * nxy + ooff[v]]);
+                const uint32_t o = in_loop(oob[v]);
+                mo[v][0] = __builtin_nontemporal_load(byte_at(mut + pb, o));
+                mo[v][1] = __builtin_nontemporal_load(byte_at(mux + pb, o));
+                mo[v][2] = __builtin_nontemporal_load(byte_at(muy + pb, o));
             }
         }
-        if (hal) {
-            hm[0] = __builtin_nontemporal_load(&mut[p * nxy + hoff]);
-            hm[1] = __builtin_nontemporal_load(&mux[p * nxy + hoff]);
-            hm[2] = __builtin_nontemporal_load(&muy[p * nxy + hoff]);
+    };
+    // rho0 / rhoT under the own voxels for F(n) on a boundary plane n, issued ahead of the
+    // iteration's other loads (Nt >= 2: a plane is at most one of the two): the wait for it leaves
+    // those in flight where the compiler can count them, and falls behind the plane's stepB
+    auto load_rho = [&](int n, double (&rc)[PR_VPT]) {
+        const int tn = t0 + n;
+        if (n < l0) return;
+#pragma unroll
+        for (int v = 0; v < PR_VPT; ++v) {
+            if (own[v] && tn == 0) rc[v] = *byte_at(rho0 + org, in_loop(oob[v]));
+            if (own[v] && tn == Nt - 1) rc[v] = *byte_at(rhoT + org, in_loop(oob[v]));
         }
     };
     // stepB / stepC at stepB-region position (px, py) of local plane p (k_prox's body)
-    auto stepb = [&](int p, int px, int py, int xg, int yg, const double (&m)[3], double (&w)[3], double& n0o,
-                     double& ao, double& gto, double& gxo, double& gyo, double (&nu)[3]) {
+    // (a steady plane has both t neighbours: d1w's interior case)
+    auto stepb = [&](auto st, int p, int px, int py, int xg, int yg, const double (&m)[3], double (&w)[3],
+                     double& n0o, double& ao, double& gto, double& gxo, double& gyo, double (&nu)[3]) {
+        constexpr bool ST = decltype(st)::value;
         const int t = t0 + p;
         const int fi = (py + 1) * PR_FW + px + 1;
         const double* P = fr[p & 3];
         const double c = P[fi];
-        const double tm = t > 0 ? fr[(p - 1) & 3][fi] : 0.0, tp = t < Nt - 1 ? fr[(p + 1) & 3][fi] : 0.0;
-        const double gt = d1w(t, Nt, tm, c, tp);
+        const double tm = (ST || t > 0) ? fr[(p - 1) & 3][fi] : 0.0;
+        const double tp = (ST || t < Nt - 1) ? fr[(p + 1) & 3][fi] : 0.0;
+        const double gt = ST ? 0.5 * (tp - tm) : d1w(t, Nt, tm, c, tp);
         const double gx = d1w(xg, Nx, P[fi - 1], c, P[fi + 1]);
         const double gy = d1w(yg, Ny, P[fi - PR_FW], c, P[fi + PR_FW]);
         double a, b1, b2;
@@ -908,60 +968,55 @@ __device__ __forceinline__ void prox_rhs_body(
     double wtm[PR_VPT], wtc[PR_VPT], wtn[PR_VPT], bcm[PR_VPT], bcq[PR_VPT], bcm_n[PR_VPT], bcq_n[PR_VPT];
 #pragma unroll
     for (int v = 0; v < PR_VPT; ++v) wtm[v] = wtc[v] = wtn[v] = bcm[v] = bcq[v] = bcm_n[v] = bcq_n[v] = 0.0;
-    // plane p's stepB for the own and the ring voxels: mu' out (own planes only), w into
-    // wb[p & 1], crit terms (own planes only)
-    auto plane = [&](int p, const double (&mo)[PR_VPT][3], const double (&mh)[3]) {
-        const bool mine = p >= l0 && p < l1;
+    // plane p's stepB.  An own plane of the chunk: the own and the ring voxels, mu' out, w into
+    // wb[p & 1], crit terms.  The planes l0 - 1 and l1 give F only the own voxels' w_t (registers):
+    // no ring voxel, no LDS write
+    auto plane = [&](auto st, int p, const double (&mo)[PR_VPT][3], const double (&mh)[3]) {
+        constexpr bool ST = decltype(st)::value;
+        const bool mine = ST || (p >= l0 && p < l1);
 #pragma unroll
         for (int v = 0; v < PR_VPT; ++v) {
             if (own[v]) {
                 double w[3], nu[3], n0, a, gt, gx, gy;
-                stepb(p, opx, opy[v], ox, oy[v], mo[v], w, n0, a, gt, gx, gy, nu);
+                stepb(st, p, opx, opy[v], ox, oy[v], mo[v], w, n0, a, gt, gx, gy, nu);
                 if (mine) {
-                    const int64_t i = p * nxy + ooff[v];
-                    __builtin_nontemporal_store(nu[0], &nut[i]);
-                    __builtin_nontemporal_store(nu[1], &nux[i]);
-                    __builtin_nontemporal_store(nu[2], &nuy[i]);
+                    const uint32_t o = in_loop(oob[v]);
+                    const int64_t pb = uniform64(p * nxy + org);
+                    __builtin_nontemporal_store(nu[0], byte_at(nut + pb, o));
+                    __builtin_nontemporal_store(nu[1], byte_at(nux + pb, o));
+                    __builtin_nontemporal_store(nu[2], byte_at(nuy + pb, o));
                     const double gg = gx * gx + gy * gy;
                     num += n0 * fabs(gt + 0.5 * gg);
                     den += n0 * gg;
+                    wb[p & 1][0][opy[v] * PR_PW + opx] = w[1];
+                    wb[p & 1][1][opy[v] * PR_PW + opx] = w[2];
                 }
-                wb[p & 1][0][opy[v] * PR_PW + opx] = w[1];
-                wb[p & 1][1][opy[v] * PR_PW + opx] = w[2];
                 wtn[v] = w[0];
-                bcm_n[v] = n0;
-                bcq_n[v] = a;
+                if (!ST) {   // (F of a boundary plane: never next to a steady one)
+                    bcm_n[v] = n0;
+                    bcq_n[v] = a;
+                }
             }
         }
-        if (hal) {
+        if (hal && mine) {
             double w[3], nu[3], n0, a, gt, gx, gy;
-            stepb(p, hpx, hpy, hx, hy, mh, w, n0, a, gt, gx, gy, nu);
+            stepb(st, p, hpx, hpy, hx, hy, mh, w, n0, a, gt, gx, gy, nu);
             wb[p & 1][0][hpy * PR_PW + hpx] = w[1];
             wb[p & 1][1][hpy * PR_PW + hpx] = w[2];
         }
     };
-    // prologue: phi planes pa-1 .. pa+1 in the ring, phi(pa+2) and mu(pa) in flight
-    {   // every prologue load in flight before the first LDS store
-        double f0[PR_FR], f1[PR_FR], f2[PR_FR];
-        load_phi_to(pa - 1, f0);
-        load_phi_to(pa, f1);
-        load_phi_to(pa + 1, f2);
-        load_phi(pa + 2);
-        load_mu(pa);
-        store_phi_from(pa - 1, f0);   // (pa = 0: plane -1 is never read)
-        store_phi_from(pa, f1);
-        store_phi_from(pa + 1, f2);
-    }
-    __syncthreads();
-    for (int p = pa; p <= l1; ++p) {
-        store_phi(p + 2);   // slot (p+2) & 3 = (p-2) & 3: last read by iteration p-1
-        load_phi(p + 3);
-        double cm[PR_VPT][3];
+    // iteration p of the march: mu(p) in (mc, hc); mu(p + 1) into (mn, hn)
+    auto step = [&](auto st, int p, const double (&mc)[PR_VPT][3], const double (&hc)[3], double (&mn)[PR_VPT][3],
+                    double (&hn)[3]) {
+        constexpr bool ST = decltype(st)::value;
+        double rc[PR_VPT];
 #pragma unroll
-        for (int v = 0; v < PR_VPT; ++v) { cm[v][0] = om[v][0]; cm[v][1] = om[v][1]; cm[v][2] = om[v][2]; }
-        const double chm[3] = {hm[0], hm[1], hm[2]};   // mu(p)
-        load_mu(p + 1);
-        if (p <= pz) plane(p, cm, chm);
+        for (int v = 0; v < PR_VPT; ++v) rc[v] = 0.0;
+        if (!ST) load_rho(p - 1, rc);
+        store_phi(p + 2);   // slot (p+2) & 3 = (p-2) & 3: last read by iteration p-1
+        load_phi_to(st, p + 3, fv);
+        load_mu(st, p + 1, mn, hn);
+        if (ST || p <= pz) plane(st, p, mc, hc);
         else {
 #pragma unroll
             for (int v = 0; v < PR_VPT; ++v) wtn[v] = 0.0;   // t0 + p = Nt: F(Nt - 1) reads no w_t(Nt)
@@ -991,29 +1046,110 @@ __device__ __forceinline__ void prox_rhs_body(
                     }
                 }
             }
-            if (own[v] && n >= l0 && !deferred) {
+            if (own[v] && (ST || n >= l0) && !deferred) {
                 // F(n) (k_rhs's order: t, x, y terms, then the boundary-plane corrections)
                 const double* WX = wb[n & 1][0];
                 const double* WY = wb[n & 1][1];
                 const int ci = opy[v] * PR_PW + opx;
-                const int oo = ooff[v], yv = oy[v];
+                const int yv = oy[v];
                 double s = 0.0;
-                acc_d1w(s, tn, Nt, wtm[v], wtc[v], wtn[v]);
+                if (ST) {   // 0 < tn < Nt - 1: acc_d1w's interior case
+                    s += -0.5 * wtm[v];
+                    s += 0.5 * wtn[v];
+                } else {
+                    acc_d1w(s, tn, Nt, wtm[v], wtc[v], wtn[v]);
+                }
                 acc_d1w(s, ox, Nx, (INTERIOR || ox > 0) ? WX[ci - 1] : 0.0, WX[ci],
                         (INTERIOR || ox < Nx - 1) ? WX[ci + 1] : 0.0);
                 acc_d1w(s, yv, Ny, (INTERIOR || yv > 0) ? WY[ci - PR_PW] : 0.0, WY[ci],
                         (INTERIOR || yv < Ny - 1) ? WY[ci + PR_PW] : 0.0);
-                if (tn == 0) s -= (rho0[oo] - bcm[v]) + r * bcq[v];
-                if (tn == Nt - 1) s += (rhoT[oo] - bcm[v]) + r * bcq[v];
-                F[n * nxy + oo] = s;
+                if (!ST && tn == 0) s -= (rc[v] - bcm[v]) + r * bcq[v];        // rho0
+                if (!ST && tn == Nt - 1) s += (rc[v] - bcm[v]) + r * bcq[v];   // rhoT
+                *byte_at(F + uniform64(n * nxy + org), in_loop(oob[v])) = s;
                 ff += s * s;
             }
             wtm[v] = wtc[v];
             wtc[v] = wtn[v];
-            bcm[v] = bcm_n[v];
-            bcq[v] = bcq_n[v];
+            if (!ST) {
+                bcm[v] = bcm_n[v];
+                bcq[v] = bcq_n[v];
+            }
         }
         __syncthreads();
+    };
+    // mu one plane ahead: two register sets.  The steady planes alternate between them; the other
+    // planes keep theirs in (mA, hA) by copying
+    double mA[PR_VPT][3], hA[3] = {0.0, 0.0, 0.0}, mB[PR_VPT][3], hB[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int v = 0; v < PR_VPT; ++v) mA[v][0] = mA[v][1] = mA[v][2] = mB[v][0] = mB[v][1] = mB[v][2] = 0.0;
+    const std::false_type any_plane{};
+    const std::true_type steady{};
+    // prologue: phi planes pa-1 .. pa+1 in the ring, phi(pa+2) and mu(pa) in flight
+    {   // every prologue load in flight before the first LDS store
+        double f0[PR_FR], f1[PR_FR], f2[PR_FR];
+        load_phi_to(any_plane, pa - 1, f0);
+        load_phi_to(any_plane, pa, f1);
+        load_phi_to(any_plane, pa + 1, f2);
+        load_phi_to(any_plane, pa + 2, fv);
+        load_mu(any_plane, pa, mA, hA);
+        store_phi_from(pa - 1, f0);   // (pa = 0: plane -1 is never read)
+        store_phi_from(pa, f1);
+        store_phi_from(pa + 1, f2);
+    }
+    __syncthreads();
+    // Iterations pa .. l1 in order, each once: the planes before the steady ones, the steady ones,
+    // the planes after them (tests/test_gpu_prox_march.py restates the bounds and checks them).
+    // BARRIERS: one per iteration, at the end of step(), outside every branch of it; pa, ps, pe,
+    // l1 and `last` derive from the kernel arguments and the block's chunk alone, so the eight
+    // waves of a block run the same iterations and the same number of barriers, and nothing
+    // returns between the first barrier and the last.
+    // STEADY planes p in [ps, pe]: p and p - 1 are own planes of the chunk (mu' and F(p - 1) are
+    // stored: four stores per own voxel, inside no branch), p - 1 and p are no boundary planes (no
+    // rho, both t neighbours), p + 1 <= pz and p + 3 is in the grid (every load issued).  With
+    // nothing of the iteration under a wave-level branch but the ring voxels -- loaded before the
+    // own voxels for that reason -- the compiler counts the step's memory operations: the waits
+    // for the loads of the iteration before leave the stores behind them in flight (s_waitcnt
+    // vmcnt(7) before the phi ring store, vmcnt(9..7) before stepB on an interior tile, where the
+    // general iteration drains them with vmcnt(0) every plane; a bounded tile's stores sit under
+    // its lane masks and still drain), and the two register sets alternate without a copy of a
+    // loaded value.  The first steady plane stands before the loop of pairs, so that the loop is
+    // entered in the state its back edge leaves; a steady-able plane left over by the pairs runs
+    // the general iteration.
+    int p = pa;
+#pragma nounroll
+    for (int part = 0; part < 2; ++part) {
+        const int last = part == 0 ? min(ps - 1, l1) : l1;
+        for (; p <= last; ++p) {
+            double cm[PR_VPT][3];
+#pragma unroll
+            for (int v = 0; v < PR_VPT; ++v) {
+                cm[v][0] = mA[v][0];
+                cm[v][1] = mA[v][1];
+                cm[v][2] = mA[v][2];
+            }
+            const double chm[3] = {hA[0], hA[1], hA[2]};   // mu(p)
+            step(any_plane, p, cm, chm, mA, hA);
+        }
+        if constexpr (!EDGE) {
+            if (part == 0 && p <= pe) {
+                step(steady, p, mA, hA, mB, hB);
+                for (++p; p + 1 <= pe; p += 2) {
+                    step(steady, p, mB, hB, mA, hA);
+                    step(steady, p + 1, mA, hA, mB, hB);
+                }
+#pragma unroll
+                for (int v = 0; v < PR_VPT; ++v) {
+                    mA[v][0] = mB[v][0];
+                    mA[v][1] = mB[v][1];
+                    mA[v][2] = mB[v][2];
+                    // (no steady plane is a boundary plane or next to one: not carried across them)
+                    bcm[v] = bcq[v] = bcm_n[v] = bcq_n[v] = 0.0;
+                }
+                hA[0] = hB[0];
+                hA[1] = hB[1];
+                hA[2] = hB[2];
+            }
+        }
     }
     num_out = num;
     den_out = den;
@@ -1068,6 +1204,8 @@ int prox_rhs_blocks(const Geo& g, int tch) {
     return ((g.Nx + PR_X - 1) / PR_X) * ((g.Ny + PR_Y - 1) / PR_Y) * ((g.nloc + tch - 1) / tch);
 }
 
+bool prox_rhs_fits(const Geo& g) { return 8 * ((int64_t)PR_FH * g.Nx + PR_FW) <= (int64_t)UINT32_MAX; }
+
 hipError_t launch_prox_rhs(const Geo& g, const double* phi, const double* mut, const double* mux, const double* muy,
                            double* nut, double* nux, double* nuy, const double* rho0, const double* rhoT, double r,
                            double* F, RedBuf rb, double* gath_crit, double* gath_rr, int tch, hipStream_t s,
@@ -1075,6 +1213,7 @@ hipError_t launch_prox_rhs(const Geo& g, const double* phi, const double* mut, c
                            int wt_pre) {
     const int nb = prox_rhs_blocks(g, tch);
     if (rb.cap < 3 * nb) return hipErrorInvalidValue;
+    if (!prox_rhs_fits(g)) return hipErrorInvalidValue;
     if ((defer_lo || defer_hi) && (!wt_out || !edge)) return hipErrorInvalidValue;
     if (defer_lo || defer_hi)
         k_prox_rhs<true><<<nb, PR_NT, 0, s>>>(g, phi, mut, mux, muy, nut, nux, nuy, rho0, rhoT, r, 1.0 / r, F, rb,
