@@ -1034,6 +1034,135 @@ int foto_flow_median_dev(const foto_flow* fl, const foto_image* guide_or_null, i
                          void* out, int out_dtype, int out_layout, void* valid_out_or_null, double* table_or_null,
                          void* stream);
 
+/* ------------------------------------------------------------------ frame preparation
+ * The stages BEFORE a solve, on device frames: what the reference does to a frame before main.py
+ * sees it -- utils.openGrayscaleImage's convert('L') (utils.py:39-42), the halving of run.sh:18-30,
+ * bin/create_lum_dataset.py, bin/normalize_image.py, bin/data_diff.py -- and the way back: a flow
+ * solved at a reduced size resized to the size of the caller's frames.  A caller whose frames come
+ * out of a decoder as RGB in HBM prepares them without a round trip through the host.  Additive.
+ * Every *_dev entry obeys the stream contract of the device-buffer section, unchanged; every
+ * device pointer is checked (for the plan's device, or the CURRENT one for the entries without a
+ * plan) before anything is enqueued; all argument checks that need no device come before any HIP
+ * call; an argument error leaves the outputs untouched.  Frames are foto_image views (channel 0;
+ * channel c starts c * stride_c ELEMENTS further on, as in foto_render_warp_dev), flows are
+ * foto_flow buffers, outputs are C-contiguous and may not overlap an input.
+ *
+ * Output rule of the pointwise stages (illuminate, normalise, difference), value x in float64:
+ * FOTO_U8 is the reference's TRUNCATING np.uint8(255 * np.clip(x, 0, 1)), NaN -> 0 (the rule of
+ * foto_render_warp_dev); FOTO_F32 is (float)x and FOTO_F64 is x, neither clipped.  A frame value
+ * is (double)pixel / divisor.                                                                    */
+
+/* PIL's convert('L') (utils.py:39-42) of a frame of 3 or 4 channels (R, G, B[, A]; alpha is
+ * ignored).  out: [h][w] of the frame's dtype.  FOTO_U8: (19595 R + 38470 G + 7471 B + 0x8000) >> 16,
+ * PIL's bits.  FOTO_F32 / FOTO_F64: ((19595 / 65536) R + (38470 / 65536) G) + (7471 / 65536) B in
+ * float64 on the raw pixel values (the divisor is not applied), written in the frame's dtype.
+ * FOTO_ERR_ARG: a null pointer, channels not 3 or 4, stride_c <= 0, anything foto_image_check
+ * rejects for any channel, a misaligned out; then a non-device pointer, an out that overlaps.     */
+int foto_prep_gray_dev(const foto_image* src, int channels, int64_t stride_c, int w, int h, void* out, void* stream);
+
+/* Separable resize, bit for bit Pillow's Image.resize (Resample.c) for modes 'L' (FOTO_U8) and 'F'
+ * (FOTO_F32), and the same in float64.  Per axis, n_in -> n_out and a filter of support S:
+ *   scale = n_in / n_out, fs = max(1, scale), support = S fs, ksize = 2 ceil(support) + 1;
+ *   output xx: center = (xx + 0.5) scale, first = max(0, (int)(center - support + 0.5)),
+ *   count = min(n_in, (int)(center + support + 0.5)) - first,
+ *   k[t] = filter((t + first - center + 0.5) / fs) (as (..) * (1 / fs)), t < count, then divided by
+ *   their sum when it is not 0 (taps are clipped at the border and renormalised).
+ * Filters (Resample.c): box (-0.5 < x <= 0.5), bilinear, bicubic with a = -0.5, Lanczos
+ * sinc(x) sinc(x / 3) on [-3, 3) with the C library's sin.  (Hamming is left out: Pillow evaluates
+ * it with float literals, and a double restatement is 1 ulp off in mode 'F'.)
+ * The horizontal pass runs first, then the vertical one; a pass whose size does not change is
+ * skipped; equal sizes return the input's bits.
+ *   FOTO_U8        coefficients (int)(+-0.5 + k 2^22); an int32 accumulator from 2^21 plus pixel *
+ *                  coefficient in tap order; each pass writes clip(acc >> 22, 0, 255) as uint8.
+ *   FOTO_F32 / F64 a double accumulator from 0 plus (double)pixel * k in tap order; float32 writes
+ *                  (float)acc after each pass (mode 'F'), float64 writes acc.
+ * The divisor of the frame plays no part: pixels in, pixels out.
+ * foto_resize_coeffs: the tables of one axis on the host, no GPU: *ksize always; bounds
+ * [n_out][2] = (first, count), kk [n_out][ksize] (zero beyond count) and kk_int, the 22-bit
+ * table, when non-null; cap = the entries kk / kk_int hold (FOTO_ERR_ARG when < n_out * ksize).   */
+#define FOTO_FILTER_BOX 0        /* support 0.5 */
+#define FOTO_FILTER_BILINEAR 1   /* support 1   */
+#define FOTO_FILTER_BICUBIC 2    /* support 2   */
+#define FOTO_FILTER_LANCZOS 3    /* support 3   */
+int foto_resize_coeffs(int n_in, int n_out, int filter, int* ksize, int* bounds, double* kk, int32_t* kk_int, int cap);
+/* A plan for (w, h) -> (ow, oh) and a filter on the current device: both axes' tables, computed
+ * once on the host and uploaded once, a stream, and a grow-only scratch for the image between the
+ * passes; reused for every frame of a video.  FOTO_ERR_ARG (nothing made): a null pointer, a size
+ * < 1 or w h >= 2^31, a filter outside 0..3, an axis whose table n_out * ksize exceeds
+ * FOTO_RESIZE_MAX_TABLE entries (foto_resize_coeffs likewise: nothing that large is allocated).  foto_resize_plan_info: info8 = {w, h, ow, oh,
+ * filter, ksize of x, ksize of y, the widest input span of a horizontal tile}.
+ * The horizontal pass works on tiles of FOTO_PREP_TILE_X outputs and stages a tile's input span on
+ * chip; where the widest span exceeds the staging (512 elements: large reduction ratios, where an
+ * output takes hundreds of taps -- 551 for 640 -> 7) it reads its taps from memory instead.  Both
+ * routes do the same arithmetic and give the same bits.  route:
+ * FOTO_RESIZE_ROUTE_AUTO picks, _LDS and _DIRECT force one (tests, timing; _LDS with a span that
+ * does not fit is FOTO_ERR_ARG).  The tile width is here for the tests, whose sizes derive from it.*/
+#define FOTO_PREP_TILE_X 64
+#define FOTO_RESIZE_MAX_TABLE (1 << 22)
+#define FOTO_RESIZE_ROUTE_AUTO 0
+#define FOTO_RESIZE_ROUTE_LDS 1
+#define FOTO_RESIZE_ROUTE_DIRECT 2
+typedef struct foto_resize_plan foto_resize_plan;
+int foto_resize_plan_create(int w, int h, int ow, int oh, int filter, foto_resize_plan** out);
+void foto_resize_plan_destroy(foto_resize_plan* p);
+int foto_resize_plan_device(const foto_resize_plan* p);   /* -1 for NULL */
+int foto_resize_plan_info(const foto_resize_plan* p, int* info8);
+/* A frame of `channels` channels (w x h, the plan's) -> out of the frame's dtype, [oh][ow][channels]
+ * (out_planar = 0) or [channels][oh][ow] (out_planar = 1), every channel in the same launches.
+ * FOTO_ERR_ARG: a null pointer, channels < 1, stride_c <= 0, anything foto_image_check rejects for
+ * any channel, a misaligned out, an out_planar outside {0, 1}, a route
+ * outside 0..2 or an LDS route that does not fit; then a pointer that is not device memory of
+ * the plan's device, an out that overlaps the frame.                                             */
+int foto_resize_dev(foto_resize_plan* p, const foto_image* src, int channels, int64_t stride_c, void* out,
+                    int out_planar, int route, void* stream);
+/* Every record and plane of a flow buffer of w x h records through the float path of the same
+ * plan -> `out`, a buffer of the same dtype, layout and record count with ow x oh records.  In
+ * the last pass that runs, before the final rounding, the accumulator of u is multiplied by
+ * (double)ow / w and that of v by (double)oh / h; m is not scaled.  With it a solve at half
+ * resolution answers at the size of the caller's frames and ground truth.  FOTO_ERR_ARG: a null
+ * pointer, anything foto_flow_check rejects, a misaligned out, the route rules above; then a
+ * pointer that is not device memory of the plan's device, an out that overlaps the flow.         */
+int foto_flow_resize_dev(foto_resize_plan* p, const foto_flow* fl, void* out, int route, void* stream);
+
+/* bin/normalize_image.py:20-26 on a pair: per frame one fixed-order sum S of the float64 values
+ * (the order of normalize = 1 of foto_bb_create_dev: the same bits from call to call) and the
+ * maximum; scale = max(max0 / S0, max1 / S1); out_k = (v / S_k) / scale by the output rule above.
+ * out0, out1: [h][w] of out_dtype.  stats4 (HOST, required) = {S0, S1, max0, max1}: the call
+ * waits for it.  A NaN pixel never wins the maximum.  Temporaries (both frames as float64) live
+ * for the call.  FOTO_ERR_ARG: a null pointer, w or h < 1, anything foto_image_check rejects, an
+ * out_dtype outside 0..2, a misaligned output; then a non-device pointer, an output that overlaps
+ * a frame or the other output.                                                                   */
+int foto_prep_normalize_pair_dev(const foto_image* f0, const foto_image* f1, int w, int h, void* out0, void* out1,
+                                 int out_dtype, double* stats4, void* stream);
+
+/* bin/create_lum_dataset.py:8-21: up to FOTO_PREP_MAX_SHAPES rectangles and discs added to the
+ * frame's float64 values per pixel (i, j) = (column, row), in list order:
+ *   FOTO_LUM_RECT    p = {L_x, L_y, r_x, r_y}: += v where (int)(r_x - L_x / 2) <= i < (int)(r_x +
+ *                    L_x / 2) and likewise j (the reference's range(); here clipped to the frame,
+ *                    where the reference's flat index would wrap into a neighbouring row or raise);
+ *   FOTO_LUM_CIRCLE  p = {R, c_x, c_y, unused}: += v where (i - c_x)^2 + (j - c_y)^2 < R^2.
+ * out: [h][w] of out_dtype by the output rule above.  FOTO_ERR_ARG: a null pointer, count outside
+ * 0..FOTO_PREP_MAX_SHAPES, a kind outside {0, 1}, a parameter or value that is not finite (a
+ * rectangle bound beyond 1e9), the image and output rules above.                                 */
+#define FOTO_PREP_MAX_SHAPES 8
+#define FOTO_LUM_RECT 0
+#define FOTO_LUM_CIRCLE 1
+typedef struct {
+    int kind;        /* FOTO_LUM_RECT | FOTO_LUM_CIRCLE                                          */
+    int reserved;    /* 0                                                                        */
+    double p[4];     /* see above                                                                */
+    double v;        /* the value added                                                          */
+} foto_lum_shape;
+int foto_prep_illuminate_dev(const foto_image* src, int w, int h, const foto_lum_shape* shapes, int count, void* out,
+                             int out_dtype, void* stream);
+
+/* bin/data_diff.py:35-39: d = v1 - v0 in float64, its minimum and maximum (order-independent; a
+ * NaN never wins), out = (d - min) / (max - min) by the output rule above: [h][w] of out_dtype.  A
+ * constant difference gives 0 / 0: 0 as uint8, NaN as float.  minmax2_or_null (HOST) = {min, max}.
+ * Temporaries live for the call, which waits for them.  Argument rules: those of the pair above. */
+int foto_prep_diff_dev(const foto_image* f0, const foto_image* f1, int w, int h, void* out, int out_dtype,
+                       double* minmax2_or_null, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

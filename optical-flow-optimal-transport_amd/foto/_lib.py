@@ -216,6 +216,23 @@ class MedianOpts(ctypes.Structure):
     ]
 
 
+# (include/foto.h, frame preparation)
+FOTO_FILTER_BOX, FOTO_FILTER_BILINEAR, FOTO_FILTER_BICUBIC, FOTO_FILTER_LANCZOS = range(4)
+FOTO_PREP_TILE_X, FOTO_PREP_MAX_SHAPES, FOTO_RESIZE_MAX_TABLE = 64, 8, 1 << 22
+FOTO_RESIZE_ROUTE_AUTO, FOTO_RESIZE_ROUTE_LDS, FOTO_RESIZE_ROUTE_DIRECT = range(3)
+FOTO_LUM_RECT, FOTO_LUM_CIRCLE = 0, 1
+
+
+class LumShape(ctypes.Structure):
+    """foto_lum_shape (include/foto.h): one rectangle or disc of added illumination."""
+    _fields_ = [
+        ("kind", ctypes.c_int),
+        ("reserved", ctypes.c_int),
+        ("p", ctypes.c_double * 4),
+        ("v", ctypes.c_double),
+    ]
+
+
 ITER_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int)
 
 _D = ctypes.POINTER(ctypes.c_double)
@@ -359,6 +376,19 @@ SIGNATURES = {
                                _I, _I, ctypes.POINTER(MedianOpts)]),
     "foto_flow_median_dev": (_I, [ctypes.POINTER(Flow), ctypes.POINTER(Image), _I, ctypes.c_int64,
                                   ctypes.POINTER(Image), _I, _I, ctypes.POINTER(MedianOpts), _P, _I, _I, _P, _P, _P]),
+    # frame preparation: grey, PIL-exact resize, pair normalisation, illumination, difference
+    "foto_prep_gray_dev": (_I, [ctypes.POINTER(Image), _I, ctypes.c_int64, _I, _I, _P, _P]),
+    "foto_resize_coeffs": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _D, ctypes.POINTER(ctypes.c_int32),
+                                _I]),
+    "foto_resize_plan_create": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
+    "foto_resize_plan_destroy": (None, [_P]),
+    "foto_resize_plan_device": (_I, [_P]),
+    "foto_resize_plan_info": (_I, [_P, ctypes.POINTER(_I)]),
+    "foto_resize_dev": (_I, [_P, ctypes.POINTER(Image), _I, ctypes.c_int64, _P, _I, _I, _P]),
+    "foto_flow_resize_dev": (_I, [_P, ctypes.POINTER(Flow), _P, _I, _P]),
+    "foto_prep_normalize_pair_dev": (_I, [ctypes.POINTER(Image), ctypes.POINTER(Image), _I, _I, _P, _P, _I, _D, _P]),
+    "foto_prep_illuminate_dev": (_I, [ctypes.POINTER(Image), _I, _I, ctypes.POINTER(LumShape), _I, _P, _I, _P]),
+    "foto_prep_diff_dev": (_I, [ctypes.POINTER(Image), ctypes.POINTER(Image), _I, _I, _P, _I, _D, _P]),
 }
 
 _lib = None

@@ -6,6 +6,7 @@
 ``as_image``      anything exposing ``__cuda_array_interface__`` (a torch ROCm tensor, a
                   DeviceArray, a strided view of either) -> the C ABI's foto_image.
 ``bb_flow`` / ``gn_flow``  the two solvers on device frames, through the context / plan caches.
+``prepare_pair``  grey, resize and pair normalisation of two device frames ahead of a solve.
 
 This module never imports torch.  One HIP runtime per process: torch bundles its own
 libamdhip64, and device pointers of one runtime mean nothing to another -- import torch before
@@ -447,6 +448,29 @@ def report_target(out, Nt):
 
 
 # -------------------------------------------------------------------- convenience
+
+def prepare_pair(c0, c1, size=None, filter="lanczos", normalize=True, *, channels_last=True, stream=None):
+    """Two grey or colour device frames made ready for bb_flow / gn_flow / tvl1_flow / bb_sequence
+    without leaving the device (foto.prep): colour frames ((h, w, 3 | 4), or (3 | 4, h, w) with
+    ``channels_last=False``) go through PIL's convert('L'); ``size`` ((ow, oh), "WxH" or a scale
+    factor; None: as they are) through PIL's Image.resize with ``filter``; ``normalize`` through
+    bin/normalize_image.py's mass equalisation, written as uint8 like the tool's PNGs.  The stages
+    run.sh:18-70 applies before main.py.  Returns the two device images."""
+    from . import prep
+    frames = []
+    for f in (c0, c1):
+        if len(_interface(f)[2]) == 3:
+            f = prep.gray(f, channels_last=channels_last, stream=stream)
+        if size is not None:
+            f = prep.resize(f, size, filter, stream=stream)
+        frames.append(f)
+    a, b = frames
+    if as_image(a).shape != as_image(b).shape:
+        raise ValueError(f"frames differ in shape: {as_image(a).shape} and {as_image(b).shape}")
+    if normalize:
+        a, b, _ = prep.normalize_pair(a, b, dtype="uint8", stream=stream)
+    return a, b
+
 
 def _bb_solved(f0, f1, Nt, r, convergence_tol, reg_epsilon, max_it, normalize, stream, opts, run, *more):
     """The frame of bb_flow, bb_path and bb_track: the pair solved with the reference's stop rules

@@ -73,7 +73,47 @@ def build_parser():
                    help="mask the flow by the forward-backward check of --save-consistency (the --median, if any, then "
                         "ignores the rejected pixels) and fill the rejected pixels from their neighbours; prints the "
                         "filled and unfilled counts")
+    p.add_argument("--resize", default=None, metavar="S|WxH",
+                   help="prepare the frames on the device before the solve: resized by the factor S, or to W x H, "
+                        "with PIL's Image.resize arithmetic (run.sh:18-30 halves them: --resize 0.5)")
+    p.add_argument("--resize-filter", default="lanczos", choices=("box", "bilinear", "bicubic", "lanczos"),
+                   help="filter of --resize")
+    p.add_argument("--normalize-pair", action="store_true",
+                   help="prepare the frames on the device before the solve: the mass equalisation of "
+                        "bin/normalize_image.py (run.sh:50-70), quantised to 8 bits like its PNGs")
+    p.add_argument("--flow-full-size", action="store_true",
+                   help="with --resize: resize the solved flow back to the size of the input frames (bilinear, u and "
+                        "v scaled with it) before --out, --stats and the --save-* outputs")
     return p
+
+
+def prepared_frames(args, size):
+    """(f, w, h) x 2 of --resize / --normalize-pair: the input files as the decoder gives them (grey or
+    RGB uint8), prepared on the device by foto.device.prepare_pair, back as utils.openGrayscaleImage
+    returns a frame.  ``size`` None: not resized."""
+    from foto import device as D
+    up = [D.DeviceArray.from_numpy(_open_u8(p)) for p in (args.f0, args.f1)]
+    out = []
+    for d in D.prepare_pair(up[0], up[1], size=size, filter=args.resize_filter, normalize=args.normalize_pair):
+        a = d.to_numpy()
+        out.append((a.flatten() / 255, a.shape[1], a.shape[0]))
+    return out
+
+
+def resized_u8(a, size, filt):
+    """A uint8 frame, grey or colour, through foto.prep.resize on the device."""
+    from foto import device as D
+    from foto import prep
+    return prep.resize(D.DeviceArray.from_numpy(a), size, filt).to_numpy()
+
+
+def flow_to_size(u, v, m, w, h, W, H):
+    """The solved (u, v, m) of a w x h solve at W x H: foto.prep.resize_flow, bilinear."""
+    from foto import device as D
+    from foto import prep
+    flow = np.stack([np.asarray(x, dtype=np.float64).reshape(h, w) for x in (u, v, m)])
+    big = prep.resize_flow(D.DeviceArray.from_numpy(flow), (W, H), "bilinear").to_numpy()
+    return big[0].reshape(-1), big[1].reshape(-1), big[2].reshape(-1)
 
 
 def stats_lines(w, h, u, v, uGT, vGT):
@@ -161,8 +201,17 @@ def main(argv=None, writer=None):
             writer.submit(fn, *a)
 
     np.random.seed(0)
-    f1, w, h = utils.openGrayscaleImage(args.f0)
-    f2, w, h = utils.openGrayscaleImage(args.f1)
+    if args.flow_full_size and not args.resize:
+        raise SystemExit("--flow-full-size needs --resize: there is no other size to come back from")
+    full = None
+    if args.resize or args.normalize_pair:   # (off by default: every other run reads its frames as before)
+        (f1, w, h), (f2, w, h) = prepared_frames(args, args.resize)
+        if args.flow_full_size:
+            full = prepared_frames(args, None)
+    else:
+        f1, w, h = utils.openGrayscaleImage(args.f0)
+        f2, w, h = utils.openGrayscaleImage(args.f1)
+    sw, sh = w, h   # (the size of the solve: w, h become the full size under --flow-full-size)
 
     print("***********************************")
     print("Input images: ")
@@ -190,6 +239,8 @@ def main(argv=None, writer=None):
         inbetweens, backward = [], []
         if args.inbetweens > 0 and args.save_inbetweens:   # (on the solved context, after the flow extraction)
             c0, c1 = _open_u8(args.f0), _open_u8(args.f1)
+            if args.resize:   # (the in-betweens are drawn at the size of the solve)
+                c0, c1 = (resized_u8(c, args.resize, args.resize_filter) for c in (c0, c1))
             opts["then"] = lambda s: inbetweens.append(s.interpolate(c0, c1, inbetween_times(args.inbetweens, args.Nt)))
         if args.save_consistency or args.fill_occluded:   # (the a-planes of the maps at the last plane: frame 1 -> frame 0, a - p)
             first = opts.get("then")
@@ -239,7 +290,7 @@ def main(argv=None, writer=None):
                 bu, bv, _, _ = solver.solve(rho2, rho1)
             else:
                 bu, bv = backward[0]
-            checked.append(consistency_mask(w, h, fu, fv, bu, bv))
+            checked.append(consistency_mask(sw, sh, fu, fv, bu, bv))
         return checked[0]
 
     solved = (u, v)
@@ -250,6 +301,12 @@ def main(argv=None, writer=None):
             print(f" - median filter: radius {args.median}, {args.median_rounds} round(s), guided by f0")
         if counts is not None:
             print(" - occluded pixels filled / unfilled: " + " / ".join(str(c) for c in counts))
+
+    if full is not None:   # (the consistency mask stays at the size of the solve, sw x sh)
+        (F1, W, H), (F2, _, _) = full
+        print(f" - flow resized from {w}x{h} to {W}x{H}")
+        u, v, m = flow_to_size(u, v, m, w, h, W, H)
+        f1, f2, w, h = F1, F2, W, H
 
     print("Benchmark:")
     rec = utils.apply_opticalflow(f1, u, v, w, h, m)
@@ -300,7 +357,7 @@ def main(argv=None, writer=None):
         print("saving consistency mask...")
         mask, counts = cross_check(*solved)   # (of the solved flow, before any --median)
         print(" - consistent / inconsistent / leaves the frame / not finite: " + " / ".join(str(c) for c in counts))
-        emit(_save_gray, mask, w, h, args.save_consistency)
+        emit(_save_gray, mask, sw, sh, args.save_consistency)
 
     if args.algo == "foto" and inbetweens:
         print("saving in-betweens...")

@@ -28,7 +28,8 @@ Differences from run.sh, all deliberate:
     eval-gray-twoframes.zip (run.sh:9-10) first; this needs network access.  The 50 %
     resize uses PIL's Lanczos filter, not ImageMagick (run.sh:26), so resized pixels
     can differ from magick's.  The lum seeds are bash's $RANDOM after RANDOM=12345
-    (run.sh:33), restated in bash_random(), in the same glob order.
+    (run.sh:33), restated in bash_random(), in the same glob order.  ``prepare --device``
+    does the three stages on the GPU through foto.prep and writes the same files.
   * ``--dataset NAME=FRAMES_DIR[:GT_DIR]`` adds a dataset such as Middlebury-2
     other-data-gray with other-gt-flow.  When GT_DIR/<seq>/flow10.flo exists it is passed
     as --ground-truth, so the benchmark txt gains EE/AE.  ``results/summary.json``
@@ -154,10 +155,58 @@ def normalize_dataset(ds):
         save_gray(f2, w, h, ds.frame(seq, 1))
 
 
+def _open_dev(path):
+    """A frame file on the device: uint8 (h, w) for a mode 'L' file (the eval-data-gray sets), else
+    (h, w, 3) after a conversion to RGB -- the host path resizes a file in its own mode, so for 'LA',
+    'P', 'RGBA' or 16-bit files the two paths do not write the same files."""
+    from PIL import Image
+    from foto.device import DeviceArray
+    im = Image.open(path)
+    return DeviceArray.from_numpy(np.asarray(im if im.mode == "L" else im.convert("RGB"), dtype=np.uint8))
+
+
+def _save_dev(d, path):
+    from PIL import Image
+    Image.fromarray(d.to_numpy()).save(path)
+
+
+def prepare_device(m1, lum, seed=12345):
+    """prepare's three stages through foto.prep, on the device, writing the same files for mode 'L'
+    frames (other modes go through RGB, see _open_dev): the Lanczos
+    halving is PIL's bit for bit and so is the illumination; the pair normalisation sums in the
+    device's fixed order, not np.sum's, so a pixel whose 255 x lands within an ulp of an integer can
+    come out one grey level apart."""
+    from foto import prep
+    print("Resizing datasets")
+    for seq in sequences(m1.frames):
+        for k in (0, 1):
+            _save_dev(prep.resize(_open_dev(m1.frame(seq, k)), 0.5, "lanczos"), m1.frame(seq, k))
+    print("Adding random artifical illumination")
+    seqs = sequences(m1.frames)
+    os.makedirs(lum.frames, exist_ok=True)
+    for seq, sd in zip(seqs, bash_random(seed, len(seqs))):
+        os.makedirs(os.path.join(lum.frames, seq), exist_ok=True)
+        shutil.copyfile(m1.frame(seq, 0), lum.frame(seq, 0))
+        d = _open_dev(m1.frame(seq, 1))
+        d = prep.gray(d) if d.ndim == 3 else d
+        h, w = d.shape
+        _save_dev(prep.illuminate(d, prep.lum_shapes(w, h, sd)), lum.frame(seq, 1))
+    print("Normalizing datasets")
+    for ds in (m1, lum):
+        for seq in sequences(ds.frames):
+            pair = [_open_dev(ds.frame(seq, k)) for k in (0, 1)]
+            pair = [prep.gray(d) if d.ndim == 3 else d for d in pair]
+            o0, o1, _ = prep.normalize_pair(pair[0], pair[1])
+            _save_dev(o0, ds.frame(seq, 0))
+            _save_dev(o1, ds.frame(seq, 1))
+
+
 def prepare(args):
     m1, lum = datasets(args)[:2]
     if not sequences(m1.frames):
         raise SystemExit(f"no sequences under {m1.frames}: unpack eval-gray-twoframes.zip there first (or `run.py download`)")
+    if getattr(args, "device", False):
+        return prepare_device(m1, lum)
     resize_dataset(m1)
     create_lum_dataset(m1, lum)
     print("Normalizing datasets")
@@ -432,6 +481,8 @@ def build_parser():
     p.add_argument("--devices", default=None,
                    help="comma list of device ordinals, worker i on entry i mod len (default: worker i on "
                         "device i; env FOTO_RUN_DEVICES); e.g. --gpus 2 --devices 0,0: two workers share GPU 0")
+    p.add_argument("--device", action="store_true",
+                   help="prepare: run the three preparation stages on the GPU (foto.prep) instead of numpy / PIL")
     p.add_argument("--data", default="data")
     p.add_argument("--results", default="results")
     p.add_argument("--dataset", action="append", help="extra dataset NAME=FRAMES_DIR[:GT_DIR]")
