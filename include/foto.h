@@ -1163,6 +1163,116 @@ int foto_prep_illuminate_dev(const foto_image* src, int w, int h, const foto_lum
 int foto_prep_diff_dev(const foto_image* f0, const foto_image* f1, int w, int h, void* out, int out_dtype,
                        double* minmax2_or_null, void* stream);
 
+/* ------------------------------------------------------------------ sparse tracking
+ * Feature points and a classical sparse tracker on device frames: Shi-Tomasi corners (Shi & Tomasi
+ * 1994), pyramidal Lucas-Kanade with fixed counts (Lucas & Kanade 1981; Bouguet 2001), and a dense
+ * flow sampled at points.  No reference counterpart (the reference tracks pixel centres through
+ * the transport only, utils.py:44-99); tests/sparse_ref.py restates the arithmetic below in numpy
+ * and the device equals it bit for bit.  Additive.  Everything is float64 on the device; frames
+ * are foto_image views, widened as (double)pixel / divisor like every *_dev entry; points are
+ * [M][2] = (x, y) in foto_bb_track's coordinates (x along w).  Every entry obeys the stream
+ * contract of the device-buffer section; argument checks that need no device come before any HIP
+ * call, every device pointer is checked before anything is enqueued, and an argument error leaves
+ * the outputs untouched.  None of them waits for the device, but foto_corners_dev with a host
+ * count.  Gx, Gy below are central differences, zero in the first and last column / row (the
+ * gradients of the TV-L1 solver); S(f; x, y) is the clamped bilinear sample of the pyramid.
+ *
+ * Corners.  Box sums a, b, cc of Gx Gx, Gx Gy, Gy Gy over (2 c + 1)^2 pixels, a plane counting as
+ * +0.0 outside the frame: first H[j][i] = sum over dx = -c..c of P[j][i + dx], in increasing dx
+ * from the first term, then the sum over dy = -c..c of H[j + dy][i], in increasing dy.
+ *   R = 0.5 ((a + cc) - sqrt((a - cc) (a - cc) + 4.0 (b b)))
+ * Rmax = the largest finite positive R of the frame (0 when there is none).  A pixel is a
+ * candidate when R is finite and > 0, R >= quality Rmax, the pixel is at least `margin` pixels
+ * from every border, and R is the maximum of its (2 s + 1)^2 neighbourhood truncated at the frame,
+ * ties going to the earlier pixel in raster order (R > every earlier neighbour, R >= every later
+ * one; a NaN neighbour fails both).  Of the candidates the max_count strongest are kept (R
+ * descending, then index ascending) and written in raster order; rows from the count on are NaN.
+ * The count goes to count_dev (a device int32) and, when count_host_or_null is given, to the host:
+ * only then does the call wait.  response_or_null: a device double[h][w] that receives R.        */
+#define FOTO_CORNER_MAX_WINDOW 7
+#define FOTO_CORNER_MAX_NMS 15
+typedef struct {
+    double quality;   /* in [0, 1]                                                              */
+    int window;       /* c: the box radius, 1 .. FOTO_CORNER_MAX_WINDOW                          */
+    int nms;          /* s: the suppression radius, 1 .. FOTO_CORNER_MAX_NMS                     */
+    int margin;       /* >= 0                                                                    */
+    int reserved;     /* 0                                                                       */
+} foto_corner_opts;
+/* quality 0.01, window 3, nms 5, margin 8 */
+int foto_corner_opts_default(foto_corner_opts* o);
+/* opts NULL: the defaults.  pts: [max_count][2] of pts_dtype FOTO_F32 | FOTO_F64 (an index is
+ * exact in either).  FOTO_ERR_ARG: a null pointer, w or h < 2 or w h >= 2^31, anything
+ * foto_image_check rejects, an option outside its range, max_count < 1, a dtype outside {F32,
+ * F64}, a misaligned pointer; then a pointer that is not device memory of the current device.    */
+int foto_corners_dev(const foto_image* frame, int w, int h, const foto_corner_opts* opts, int max_count, void* pts,
+                     int pts_dtype, int32_t* count_dev, int* count_host_or_null, double* response_or_null,
+                     void* stream);
+
+/* Pyramidal Lucas-Kanade.  The plan owns both frames' pyramids: the levels of foto_gn_pyr_sizes(w,
+ * h, levels, min_size), built by foto_lk_set_frames_dev with the GN pyramid's restriction
+ * (foto_pyr_down); any number of track calls may follow.  A point (x, y) of level 0 is carried to
+ * level l by repeating x <- (x + 0.5) ((double)w_{l+1} / (double)w_l) - 0.5 (y with h); d starts
+ * at 0 on the coarsest level and is scaled by (double)w_l / (double)w_{l+1} (h for d_y) on
+ * entering level l.  At a level, over the window offsets (ax, ay) in [-R, R]^2, element e = (ay +
+ * R) (2 R + 1) + (ax + R), n = (2 R + 1)^2:
+ *   T_e = S(f; x + ax, y + ay), Gx_e = S(Gx f; .), Gy_e = S(Gy f; .)       (f: the template frame)
+ *   gxx = sum Gx_e^2, gxy = sum Gx_e Gy_e, gyy = sum Gy_e^2, det = gxx gyy - gxy gxy,
+ *   mineig = 0.5 ((gxx + gyy) - sqrt((gxx - gyy) (gxx - gyy) + 4.0 (gxy gxy))) / n;
+ *   unless mineig > min_eig the level is skipped (d unchanged; at level 0 status gets FLAT);
+ *   otherwise exactly `iters` times, with no stop test:
+ *     r_e = T_e - S(g; (x + d_x) + ax, (y + d_y) + ay)                     (g: the search frame)
+ *     bx = sum r_e Gx_e, by = sum r_e Gy_e,
+ *     d_x += (gyy bx - gxy by) / det, d_y += (gxx by - gxy bx) / det.
+ * Every sum over e has one order: lane p of 64 adds its slots e = p, p + 64, p + 128, p + 192 (0.0
+ * for a slot >= n) as ((s0 + s1) + s2) + s3; the 64 partials go through the tree a[p] += a[p + o],
+ * p < o, for o = 32, 16, .., 1.  After level 0: err = sum |r_e| / n at the final d (one more
+ * residual pass).  Status bits: FLAT; OUT: the start point or the end point is not inside [0, w-1]
+ * x [0, h-1]; NONFINITE: a NaN or Inf coordinate or result -- for that point alone d and err are
+ * NaN (and OUT is set); it is neither an error nor an out-of-range read.
+ * direction 0: template f0, search f1; 1: the roles swapped.  prior_or_null: a device [M][2] of
+ * `dtype`; with it the start point is pts + prior, fb = sqrt(sx sx + sy sy) with s = prior + d goes
+ * to fb_or_null, and the status buffer is not overwritten: INCONSISTENT is OR-ed into it unless fb
+ * <= fb_tol.  The backward call (direction 1, prior = the forward call's `out`, the forward
+ * call's status) after a forward call is therefore the whole forward-backward check, with
+ * nothing downloaded.  out: [M][2] = d (x_end - x_start, foto_bb_track's convention) of dtype
+ * FOTO_F32 | FOTO_F64; status: uint8[M]; err_or_null, fb_or_null: double[M].
+ * FOTO_ERR_ARG: a null pointer, the size rules of foto_gn_pyr_sizes, radius outside 1 ..
+ * FOTO_LK_MAX_RADIUS, iters < 1, min_eig negative or not finite, M < 1 or > 2^31 - 1, a dtype
+ * outside {F32, F64}, a pair array not aligned to a pair, a direction outside {0, 1}, fb without
+ * a prior, a NaN fb_tol with a prior; then a pointer that is not device memory of the plan's
+ * device, an `out` that overlaps pts or prior.  FOTO_ERR_STATE: a track before any frames.       */
+#define FOTO_LK_MAX_RADIUS 7
+#define FOTO_LK_FLAT 1
+#define FOTO_LK_OUT 2
+#define FOTO_LK_NONFINITE 4
+#define FOTO_LK_INCONSISTENT 8
+typedef struct {
+    int radius;       /* R: 1 .. FOTO_LK_MAX_RADIUS                                              */
+    int levels;       /* >= 1 (foto_gn_pyr_sizes)                                                */
+    int min_size;     /* >= 2 (foto_gn_pyr_sizes)                                                */
+    int iters;        /* >= 1                                                                    */
+    double min_eig;   /* finite, >= 0                                                            */
+} foto_lk_opts;
+/* radius 7, levels 4, min_size 16, iters 10, min_eig 1e-7 */
+int foto_lk_opts_default(foto_lk_opts* o);
+typedef struct foto_lk foto_lk;
+int foto_lk_create(int w, int h, const foto_lk_opts* opts, foto_lk** out);
+void foto_lk_destroy(foto_lk* p);
+int foto_lk_device(const foto_lk* p);   /* -1 for NULL */
+int foto_lk_set_frames_dev(foto_lk* p, const foto_image* f0, const foto_image* f1, void* stream);
+int foto_lk_track_dev(foto_lk* p, const void* pts, int pts_dtype, int64_t M, int direction, const void* prior_or_null,
+                      double fb_tol, void* out, int dtype, unsigned char* status, double* err_or_null,
+                      double* fb_or_null, void* stream);
+
+/* A dense flow read at points: out[r][p] = (S(u_r; x_p, y_p), S(v_r; x_p, y_p)) for every record r
+ * of a flow buffer of w x h records (values widened exactly) -- a dense solver's flow, a ground
+ * truth and the LK tracks on the same points.  out: [records][M][2] of dtype FOTO_F32 | FOTO_F64.
+ * A NaN coordinate gives NaN, read from in-frame taps.  FOTO_ERR_ARG: anything foto_flow_check
+ * rejects, w or h < 2, the point rules above; then a pointer that is not device memory of the
+ * current device, an out that overlaps an input.                                                 */
+int foto_flow_sample_dev(const foto_flow* fl, int w, int h, const void* pts, int pts_dtype, int64_t M, void* out,
+                         int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

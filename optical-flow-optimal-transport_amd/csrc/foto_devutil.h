@@ -207,4 +207,18 @@ __device__ __forceinline__ double pyr_sample(const double* __restrict__ f, int w
     return sample_sum(T, r0[0], r0[1], r1[0], r1[1]);
 }
 
+// ----------------------------------------------------------------------------- central differences
+// Gx f and Gy f at (i, j): central differences, zero in the first and last column / row (bc N).
+// Both taps are loaded from clamped indices and the edge zero is selected afterwards.  Shared by
+// the TV-L1 coefficients (foto_tvl1.hip) and by the corner detector and the Lucas-Kanade windows
+// (foto_sparse.hip): a gradient has the same bits wherever it is formed.
+__device__ __forceinline__ double cdiff_x(const double* __restrict__ f, int w, int i, int64_t row) {
+    const double a = f[row + max(i - 1, 0)], b = f[row + min(i + 1, w - 1)];
+    return (i == 0 || i == w - 1) ? 0.0 : 0.5 * (b - a);
+}
+__device__ __forceinline__ double cdiff_y(const double* __restrict__ f, int w, int h, int i, int j) {
+    const double a = f[(int64_t)max(j - 1, 0) * w + i], b = f[(int64_t)min(j + 1, h - 1) * w + i];
+    return (j == 0 || j == h - 1) ? 0.0 : 0.5 * (b - a);
+}
+
 }  // namespace foto

@@ -32,20 +32,10 @@ namespace foto {
 
 // ----------------------------------------------------------------------------- kernels
 
-// Gx f and Gy f at (i, j): central differences, zero in the first and last column / row (bc N).
-// Both taps are loaded from clamped indices and the edge zero is selected afterwards.
-__device__ __forceinline__ double tv_gx(const double* __restrict__ f, int w, int i, int64_t row) {
-    const double a = f[row + max(i - 1, 0)], b = f[row + min(i + 1, w - 1)];
-    return (i == 0 || i == w - 1) ? 0.0 : 0.5 * (b - a);
-}
-__device__ __forceinline__ double tv_gy(const double* __restrict__ f, int w, int h, int i, int j) {
-    const double a = f[(int64_t)max(j - 1, 0) * w + i], b = f[(int64_t)min(j + 1, h - 1) * w + i];
-    return (j == 0 || j == h - 1) ? 0.0 : 0.5 * (b - a);
-}
-
 // One warp's coefficients at U0 = (u, v): g = S(f2; x + u, y + v), a1 = S(Gx f2; .), a2 =
-// S(Gy f2; .), a3 = -gamma g, n2 = |a|^2, rc = g - f1 - a1 u - a2 v; co = [5][w h].  Three gathers
-// through one sample_taps; every tap index is inside the frame whatever the displacement.
+// S(Gy f2; .), a3 = -gamma g, n2 = |a|^2, rc = g - f1 - a1 u - a2 v; co = [5][w h].  Gx, Gy are
+// cdiff_x / cdiff_y of foto_devutil.h.  Three gathers through one sample_taps; every tap index is
+// inside the frame whatever the displacement.
 __global__ __launch_bounds__(NT) void k_tvl1_coeffs(int w, int h, double gamma, const double* __restrict__ f1,
                                                     const double* __restrict__ f2, const double* __restrict__ U,
                                                     double* __restrict__ co) {
@@ -58,10 +48,10 @@ __global__ __launch_bounds__(NT) void k_tvl1_coeffs(int w, int h, double gamma, 
     const int i0 = T.i0, j0 = T.j0;
     const int64_t r0 = (int64_t)j0 * w, r1 = r0 + w;
     const double g = sample_sum(T, f2[r0 + i0], f2[r0 + i0 + 1], f2[r1 + i0], f2[r1 + i0 + 1]);
-    const double a1 = sample_sum(T, tv_gx(f2, w, i0, r0), tv_gx(f2, w, i0 + 1, r0), tv_gx(f2, w, i0, r1),
-                                 tv_gx(f2, w, i0 + 1, r1));
-    const double a2 = sample_sum(T, tv_gy(f2, w, h, i0, j0), tv_gy(f2, w, h, i0 + 1, j0), tv_gy(f2, w, h, i0, j0 + 1),
-                                 tv_gy(f2, w, h, i0 + 1, j0 + 1));
+    const double a1 = sample_sum(T, cdiff_x(f2, w, i0, r0), cdiff_x(f2, w, i0 + 1, r0), cdiff_x(f2, w, i0, r1),
+                                 cdiff_x(f2, w, i0 + 1, r1));
+    const double a2 = sample_sum(T, cdiff_y(f2, w, h, i0, j0), cdiff_y(f2, w, h, i0 + 1, j0), cdiff_y(f2, w, h, i0, j0 + 1),
+                                 cdiff_y(f2, w, h, i0 + 1, j0 + 1));
     const double a3 = -gamma * g;
     co[i] = a1;
     co[n + i] = a2;

@@ -233,6 +233,34 @@ class LumShape(ctypes.Structure):
     ]
 
 
+# (include/foto.h, sparse tracking)
+FOTO_CORNER_MAX_WINDOW, FOTO_CORNER_MAX_NMS, FOTO_LK_MAX_RADIUS = 7, 15, 7
+FOTO_LK_FLAT, FOTO_LK_OUT, FOTO_LK_NONFINITE, FOTO_LK_INCONSISTENT = 1, 2, 4, 8
+
+
+class CornerOpts(ctypes.Structure):
+    """foto_corner_opts (include/foto.h): the Shi-Tomasi detector's quality, box radius, suppression
+    radius and margin."""
+    _fields_ = [
+        ("quality", ctypes.c_double),
+        ("window", ctypes.c_int),
+        ("nms", ctypes.c_int),
+        ("margin", ctypes.c_int),
+        ("reserved", ctypes.c_int),
+    ]
+
+
+class LKOpts(ctypes.Structure):
+    """foto_lk_opts (include/foto.h): the Lucas-Kanade window radius, pyramid and fixed counts."""
+    _fields_ = [
+        ("radius", ctypes.c_int),
+        ("levels", ctypes.c_int),
+        ("min_size", ctypes.c_int),
+        ("iters", ctypes.c_int),
+        ("min_eig", ctypes.c_double),
+    ]
+
+
 ITER_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int)
 
 _D = ctypes.POINTER(ctypes.c_double)
@@ -389,6 +417,17 @@ SIGNATURES = {
     "foto_prep_normalize_pair_dev": (_I, [ctypes.POINTER(Image), ctypes.POINTER(Image), _I, _I, _P, _P, _I, _D, _P]),
     "foto_prep_illuminate_dev": (_I, [ctypes.POINTER(Image), _I, _I, ctypes.POINTER(LumShape), _I, _P, _I, _P]),
     "foto_prep_diff_dev": (_I, [ctypes.POINTER(Image), ctypes.POINTER(Image), _I, _I, _P, _I, _D, _P]),
+    # sparse tracking: Shi-Tomasi corners, pyramidal Lucas-Kanade, a dense flow sampled at points
+    "foto_corner_opts_default": (_I, [ctypes.POINTER(CornerOpts)]),
+    "foto_corners_dev": (_I, [ctypes.POINTER(Image), _I, _I, ctypes.POINTER(CornerOpts), _I, _P, _I, _P,
+                              ctypes.POINTER(_I), _P, _P]),
+    "foto_lk_opts_default": (_I, [ctypes.POINTER(LKOpts)]),
+    "foto_lk_create": (_I, [_I, _I, ctypes.POINTER(LKOpts), ctypes.POINTER(_P)]),
+    "foto_lk_destroy": (None, [_P]),
+    "foto_lk_device": (_I, [_P]),
+    "foto_lk_set_frames_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _P]),
+    "foto_lk_track_dev": (_I, [_P, _P, _I, ctypes.c_int64, _I, _P, _Dbl, _P, _I, _P, _P, _P, _P]),
+    "foto_flow_sample_dev": (_I, [ctypes.POINTER(Flow), _I, _I, _P, _I, ctypes.c_int64, _P, _I, _P]),
 }
 
 _lib = None

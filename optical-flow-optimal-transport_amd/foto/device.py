@@ -597,3 +597,25 @@ def tvl1_flow(f0, f1, *, dtype="float32", layout="planar", out=None, stream=None
     h, w = a.shape
     p = tvl1.cached_tvl1(w, h, **opts)
     return p.solve_device(a, b, out=out, dtype=dtype, layout=layout, stream=stream_handle(stream, f0, f1))[0]
+
+
+def lk_track(f0, f1, points_or_count, *, check=False, fb_tol=0.5, dtype="float32", stream=None, corner_opts=None,
+             **opts):
+    """Pyramidal Lucas-Kanade on device frames (the tracker from foto.sparse's cache; ``opts`` are
+    foto.sparse.LK_DEFAULTS' keys): the classical sparse baseline of bb_track, on the same points.
+    ``points_or_count``: device start points ((M, 2) float32 | float64), or an int K -- then the K
+    strongest Shi-Tomasi corners of ``f0`` (``corner_opts``: foto.sparse.CORNER_DEFAULTS' keys), M
+    = their count.  Returns (points (M, 2), disp (M, 2), status (M,), err (M,)) and, with
+    ``check``, fb (M,) after them: foto.sparse.LK.track's results, everything left on the device."""
+    from . import sparse
+    a, b = _pair(f0, f1)
+    h, w = a.shape
+    st = stream_handle(stream, f0, f1)
+    pts = points_or_count
+    if isinstance(pts, (int, np.integer)) and not isinstance(pts, (bool, np.bool_)):
+        pts, count = sparse.corners(a, int(pts), dtype=dtype, stream=st, **(corner_opts or {}))
+        if count < 1:
+            raise FotoError("lk_track: the frame has no corner to track")
+        pts = pts[:count]
+    p = sparse.cached_lk(w, h, **opts).set_frames(a, b, stream=st)
+    return (pts,) + tuple(p.track(pts, check=check, fb_tol=fb_tol, dtype=dtype, stream=st))

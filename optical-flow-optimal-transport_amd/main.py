@@ -84,7 +84,53 @@ def build_parser():
     p.add_argument("--flow-full-size", action="store_true",
                    help="with --resize: resize the solved flow back to the size of the input frames (bilinear, u and "
                         "v scaled with it) before --out, --stats and the --save-* outputs")
+    p.add_argument("--lk", type=int, default=0, metavar="K",
+                   help="also track the K strongest Shi-Tomasi corners of frame 0 with pyramidal Lucas-Kanade (0: "
+                        "none); with --ground-truth prints the mean EE of the tracks and of the solved flow at the "
+                        "same corners")
+    p.add_argument("--lk-radius", type=int, default=7, choices=range(1, 8), metavar="R", help="LK: window radius (1..7)")
+    p.add_argument("--lk-levels", type=int, default=4, help="LK: pyramid levels")
+    p.add_argument("--lk-iters", type=int, default=10, help="LK: iterations per level")
+    p.add_argument("--lk-check", action="store_true",
+                   help="LK: the forward-backward check (status bit 8: the round trip misses the corner by more than "
+                        "half a pixel)")
+    p.add_argument("--save-tracks", default=None, metavar="FILE",
+                   help="with --lk: one text row per corner, `x y dx dy status err`")
     return p
+
+
+def lk_tracks(f0, f1, w, h, K, radius=7, levels=4, iters=10, check=False):
+    """(points, disp, status, err) of --lk K as numpy arrays: foto.device.lk_track on the two frames
+    (float64 in [0, 1], as utils.openGrayscaleImage returns them)."""
+    from foto import device as D
+    a, b = (D.DeviceArray.from_numpy(np.asarray(f, dtype=np.float64).reshape(h, w)) for f in (f0, f1))
+    res = D.lk_track(a, b, int(K), check=check, dtype="float64", radius=radius, levels=levels, iters=iters)
+    return tuple(x.to_numpy() for x in res[:4])
+
+
+def flows_at(points, w, h, *flows):
+    """Each (u, v) of ``flows`` read at the corners: foto.sparse.sample on one buffer, (R, M, 2)."""
+    from foto import device as D
+    from foto import sparse
+    z = np.zeros((h, w))
+    buf = np.stack([np.stack([np.asarray(u, dtype=np.float64).reshape(h, w),
+                              np.asarray(v, dtype=np.float64).reshape(h, w), z]) for u, v in flows])
+    pts = D.DeviceArray.from_numpy(np.ascontiguousarray(points, dtype=np.float64))
+    return sparse.sample(D.DeviceArray.from_numpy(buf), pts).to_numpy()
+
+
+UNKNOWN_FLOW_THRESH = 1e9   # Middlebury's marker (flowIO)
+
+
+def track_rows(points, disp, status, err):
+    """The rows of --save-tracks: `x y dx dy status err`, floats by repr."""
+    return [" ".join([repr(float(p[0])), repr(float(p[1])), repr(float(d[0])), repr(float(d[1])), str(int(s)),
+                      repr(float(e))]) for p, d, s, e in zip(points, disp, status, err)]
+
+
+def _write_lines(lines, path):
+    with open(path, "w") as f:
+        f.write("".join(line + "\n" for line in lines))
 
 
 def prepared_frames(args, size):
@@ -327,6 +373,24 @@ def main(argv=None, writer=None):
         extra = stats_lines(w, h, u, v, uGT, vGT) if args.stats else []
         for name, x in extra:
             print(" - " + name + ": " + str(x))
+
+    if args.lk > 0:
+        pts, disp, status, err = lk_tracks(f1, f2, w, h, args.lk, args.lk_radius, args.lk_levels, args.lk_iters,
+                                           args.lk_check)
+        print(f" - LK: {len(pts)} corners tracked (radius {args.lk_radius}, {args.lk_levels} levels, "
+              f"{args.lk_iters} iterations)")
+        if args.lk_check:
+            print(" - LK forward-backward inconsistent: " + str(int(np.count_nonzero(status & 8))))
+        if args.ground_truth:
+            gt, dense = flows_at(pts, w, h, (uGT, vGT), (u, v))
+            known = ~((np.abs(gt) > UNKNOWN_FLOW_THRESH).any(axis=1) | np.isnan(gt).any(axis=1))
+            print(" - LK corners with known truth: " + str(int(known.sum())))
+            if known.any():
+                print(" - LK EE-mean at the corners: " + str(float(np.hypot(*(disp - gt)[known].T).mean())))
+                print(f" - {args.algo} EE-mean at the corners: " + str(float(np.hypot(*(dense - gt)[known].T).mean())))
+        if args.save_tracks:
+            print("saving tracks...")
+            emit(_write_lines, track_rows(pts, disp, status, err), args.save_tracks)
 
     if args.save_benchmark:
         with open(args.save_benchmark, "w") as f:
