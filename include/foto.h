@@ -1273,6 +1273,120 @@ int foto_lk_track_dev(foto_lk* p, const void* pts, int pts_dtype, int64_t M, int
 int foto_flow_sample_dev(const foto_flow* fl, int w, int h, const void* pts, int pts_dtype, int64_t M, void* out,
                          int dtype, void* stream);
 
+/* ------------------------------------------------------------------ global motion
+ * The one parametric motion that dominates a set of tracks or a dense flow: a RANSAC fit (Fischler
+ * & Bolles 1981) of a translation, similarity, affine map or homography in frame-normalised
+ * coordinates (Hartley & Zisserman 2004, 4.4), refined by least squares over its inliers; the
+ * model's flow field, and a flow with that field removed.  No reference counterpart;
+ * tests/motion_ref.py restates the arithmetic below in numpy and the device equals it bit for bit.
+ * Additive.  Everything is float64 on the device, inputs widened exactly.  Every entry obeys the
+ * stream contract of the device-buffer section; argument checks that need no device come before
+ * any HIP call, every device pointer is checked (for the CURRENT device) before anything is
+ * enqueued, and an argument error leaves the outputs untouched.  No entry waits for the device:
+ * the best hypothesis is chosen there and every result stays in device memory.  (A sample table
+ * that differs from the one of the previous call is uploaded first, which may wait for that
+ * previous call's work; a scratch that has to grow waits likewise.)
+ *
+ * Models.  A model maps a start point to an end point and is a row-major 3 x 3 matrix m[9] with
+ * m[8] = 1, in pixel coordinates for the caller ((x, y), x along w) and in normalised coordinates
+ * inside the fit.  k = the minimal sample, P = the parameters p:
+ *   TRANSLATION k 1, P 2   m = (1, 0, p0;  0, 1, p1;  0, 0, 1)
+ *   SIMILARITY  k 2, P 4   m = (p0, -p1, p2;  p1, p0, p3;  0, 0, 1)
+ *   AFFINE      k 3, P 6   m = (p0, p1, p2;  p3, p4, p5;  0, 0, 1)
+ *   HOMOGRAPHY  k 4, P 8   m = (p0, p1, p2;  p3, p4, p5;  p6, p7, 1)
+ * A correspondence (x, y) -> (X, Y) gives two rows r1, r2 of length P with right-hand sides b1, b2:
+ *   TRANSLATION  r1 = (1, 0), b1 = X - x;  r2 = (0, 1), b2 = Y - y
+ *   SIMILARITY   r1 = (x, -y, 1, 0), b1 = X;  r2 = (y, x, 0, 1), b2 = Y
+ *   AFFINE       r1 = (x, y, 1, 0, 0, 0), b1 = X;  r2 = (0, 0, 0, x, y, 1), b2 = Y
+ *   HOMOGRAPHY   r1 = (x, y, 1, 0, 0, 0, -(X x), -(X y)), b1 = X;  r2 = (0, 0, 0, x, y, 1, -(Y x), -(Y y)), b2 = Y
+ * (the homography in its inhomogeneous form, X (p6 x + p7 y + 1) = p0 x + p1 y + p2).
+ *
+ * Elimination.  An n x n system A p = b: for c = 0 .. n - 1 the pivot row is the row r >= c with the
+ * largest |A[r][c]|, the lowest such row on a tie; unless |A[r][c]| > 1e-12 the system is
+ * DEGENERATE; rows c and r are exchanged; then for r = c + 1 .. n - 1: f = A[r][c] / A[c][c], A[r][j]
+ * = A[r][j] - f A[c][j] for j = c + 1 .. n - 1, b[r] = b[r] - f b[c].  Back: for r = n - 1 .. 0, s =
+ * b[r], s = s - A[r][j] p[j] for j = r + 1 .. n - 1 in increasing j, p[r] = s / A[r][r].
+ *
+ * The fit.  1. s = 0.5 max(w, h), cx = 0.5 (w - 1), cy = 0.5 (h - 1).  Correspondence i with start
+ * (px, py) and displacement (dx, dy) is VALID when the four numbers are finite and its status byte
+ * (when there is a status array) is 0; x = (px - cx) / s, y = (py - cy) / s, X = ((px + dx) - cx) /
+ * s, Y = ((py + dy) - cy) / s.  2. The valid correspondences, in index order, form the list q = 0 ..
+ * n_valid - 1.  3. Hypothesis j < H takes the list entries ((uint64)samples[j][i] n_valid) >> 32, i <
+ * k, stacks their rows (entry i: rows 2 i, 2 i + 1) and solves; with n_valid < k, or a degenerate
+ * system, the hypothesis is degenerate and scores -1.  4. With wv = (m6 x + m7 y) + 1, ex = ((m0 x +
+ * m1 y) + m2) - X wv, ey = ((m3 x + m4 y) + m5) - Y wv and t = threshold / s, a list entry is an
+ * INLIER of m when wv > 0 and ex ex + ey ey <= (t t) (wv wv).  The score of a hypothesis is its
+ * inlier count; the winner has the highest score, the lowest j on a tie.  When the winner's score
+ * is below max(k, min_inliers): FOTO_MOTION_NONE -- the model is the identity, the mask 0, inliers
+ * 0, the winner -1, rms NaN: a result, not an error.  5. Otherwise exactly `rounds` times: with
+ * fewer than k inliers of the current model m, or a degenerate system, m stays and status gains
+ * FOTO_MOTION_KEPT; else m becomes the solution of N p = g, N[a][b] = sum (r1[a] r1[b] + r2[a]
+ * r2[b]) (a <= b, mirrored), g[a] = sum (r1[a] b1 + r2[a] b2) over the inliers of m.  6. The mask is
+ * 1 at the inliers of the final m; rms = s sqrt(S / inliers), S = sum (rx rx + ry ry), rx = ((m0 x +
+ * m1 y) + m2) / wv - X, ry likewise.  The pixel matrix: with A[i][0] = m[i][0] / s, A[i][1] = m[i][1]
+ * / s, A[i][2] = (m[i][2] - (m[i][0] cx) / s) - (m[i][1] cy) / s, B[0][j] = s A[0][j] + cx A[2][j],
+ * B[1][j] = s A[1][j] + cy A[2][j], B[2][j] = A[2][j]: out[i][j] = B[i][j] / B[2][2], out[2][2] = 1.
+ * Every floating-point sum of 5 and 6 has one order, fixed by M alone: the list, followed by +0.0
+ * terms (an entry that is no inlier is a +0.0 term too), in ceil(M / FOTO_MOTION_TILE) tiles of
+ * FOTO_MOTION_TILE = 1024 entries; in a tile thread p of 256 adds its entries p, p + 256, p + 512,
+ * p + 768 as ((s0 + s1) + s2) + s3, the 64 partials of each of the four waves go through the tree
+ * a[p] += a[p + o], p < o, o = 32, 16, .., 1, the four wave sums add as ((w0 + w1) + w2) + w3, and
+ * the tile sums are added to 0.0 in tile order.  Counts are integers.
+ *
+ * samples: a HOST uint32[H][4] (foto.motion.samples draws it with numpy; the device draws no random
+ * number); the index rule above is in range for every n_valid, so the table depends on neither M
+ * nor a count that only the device knows.
+ * Outputs (device): model double[9]; inliers uint8[M] (0 for an invalid correspondence); info
+ * int64[4] = (inliers, n_valid, winner, status bits); rms double[1].
+ * FOTO_ERR_ARG: a null pointer (status excepted), M < 1 or > 2^31 - 1, H < 1, a model outside the
+ * four, a threshold that is not finite and > 0, rounds < 0, min_inliers < 0, w or h < 2, a dtype
+ * outside {F32, F64}, a pair array not aligned to a pair, a misaligned output; then a pointer that
+ * is not device memory of the current device, an output that overlaps an input or another output. */
+#define FOTO_MOTION_TRANSLATION 0
+#define FOTO_MOTION_SIMILARITY 1
+#define FOTO_MOTION_AFFINE 2
+#define FOTO_MOTION_HOMOGRAPHY 3
+#define FOTO_MOTION_NONE 1   /* status bit: no hypothesis reached max(k, min_inliers) inliers      */
+#define FOTO_MOTION_KEPT 2   /* status bit: a refinement round kept the model it started from     */
+#define FOTO_MOTION_TILE 1024
+typedef struct {
+    int model;          /* FOTO_MOTION_TRANSLATION .. FOTO_MOTION_HOMOGRAPHY; the default leaves -1 */
+    int rounds;         /* refinement rounds, >= 0                                                 */
+    int min_inliers;    /* >= 0                                                                    */
+    int reserved;       /* 0                                                                       */
+    double threshold;   /* the inlier distance in pixels, finite and > 0                           */
+} foto_motion_opts;
+/* model -1 (the caller chooses), rounds 3, min_inliers 0, threshold 1.0 */
+int foto_motion_opts_default(foto_motion_opts* o);
+/* pts, disp: [M][2] of FOTO_F32 | FOTO_F64, what foto_corners_dev and foto_lk_track_dev /
+ * foto_flow_sample_dev write; status_or_null: uint8[M], non-zero = unusable (LK's status byte). */
+int foto_motion_fit_dev(const void* pts, int pts_dtype, const void* disp, int disp_dtype,
+                        const unsigned char* status_or_null, int64_t M, int w, int h, const foto_motion_opts* opts,
+                        const uint32_t* samples, int H, double* model, unsigned char* inliers, int64_t* info,
+                        double* rms, void* stream);
+/* The same fit on record `record` of a flow buffer of w x h records: the correspondences are the
+ * lattice pixels (i stride, j stride), i < lw = (w - 1) / stride + 1, j < lh = (h - 1) / stride + 1,
+ * number j lw + i, M = lw lh, with the flow there as displacement; valid when u and v are finite and
+ * mask_or_null (uint8[h][w], foto_flow_consistency_dev's `valid`: non-zero = usable) allows the
+ * pixel.  inliers: uint8[lh][lw].  FOTO_ERR_ARG: the rules above, anything foto_flow_check
+ * rejects, a record outside the buffer, stride < 1.                                              */
+int foto_motion_fit_flow_dev(const foto_flow* fl, int record, int w, int h, int stride,
+                             const unsigned char* mask_or_null, const foto_motion_opts* opts, const uint32_t* samples,
+                             int H, double* model, unsigned char* inliers, int64_t* info, double* rms, void* stream);
+/* The flow field of `count` pixel models (device double[count][9]): record r of `out`, a flow buffer
+ * of `dtype`, `layout` and count records, is at pixel (x, y): wv = (m6 x + m7 y) + m8, u = ((m0 x +
+ * m1 y) + m2) / wv - x, v = ((m3 x + m4 y) + m5) / wv - y, both NaN unless wv > 0; m = 0 (planar).
+ * What foto_render_warp_dev, foto_flow_compose_dev and foto_score_flow_dev take as it is.
+ * FOTO_ERR_ARG: a null pointer, count < 1, w or h < 1 or w h >= 2^31, a dtype outside {F32, F64}, a
+ * layout outside {0, 1}, a misaligned pointer; then non-device memory, an overlap.               */
+int foto_motion_field_dev(const double* models, int count, int w, int h, void* out, int dtype, int layout,
+                          void* stream);
+/* flow - field per record, the motion left once the global one is removed: `out` has the flow's
+ * dtype, layout and record count; u_out = u - field u, v_out = v - field v in float64 (NaN where
+ * the field is), m copied.  count: 1 (one model for every record) or fl->records.                */
+int foto_motion_residual_dev(const foto_flow* fl, const double* models, int count, int w, int h, void* out,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

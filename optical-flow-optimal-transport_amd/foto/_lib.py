@@ -261,6 +261,23 @@ class LKOpts(ctypes.Structure):
     ]
 
 
+# (include/foto.h, global motion)
+FOTO_MOTION_TRANSLATION, FOTO_MOTION_SIMILARITY, FOTO_MOTION_AFFINE, FOTO_MOTION_HOMOGRAPHY = range(4)
+FOTO_MOTION_NONE, FOTO_MOTION_KEPT, FOTO_MOTION_TILE = 1, 2, 1024
+
+
+class MotionOpts(ctypes.Structure):
+    """foto_motion_opts (include/foto.h): the model, the refinement rounds, the inlier bar and the
+    inlier distance of a global-motion fit."""
+    _fields_ = [
+        ("model", ctypes.c_int),
+        ("rounds", ctypes.c_int),
+        ("min_inliers", ctypes.c_int),
+        ("reserved", ctypes.c_int),
+        ("threshold", ctypes.c_double),
+    ]
+
+
 ITER_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int)
 
 _D = ctypes.POINTER(ctypes.c_double)
@@ -428,6 +445,14 @@ SIGNATURES = {
     "foto_lk_set_frames_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _P]),
     "foto_lk_track_dev": (_I, [_P, _P, _I, ctypes.c_int64, _I, _P, _Dbl, _P, _I, _P, _P, _P, _P]),
     "foto_flow_sample_dev": (_I, [ctypes.POINTER(Flow), _I, _I, _P, _I, ctypes.c_int64, _P, _I, _P]),
+    # global motion: RANSAC fit of a parametric model, its flow field, the residual flow
+    "foto_motion_opts_default": (_I, [ctypes.POINTER(MotionOpts)]),
+    "foto_motion_fit_dev": (_I, [_P, _I, _P, _I, _P, ctypes.c_int64, _I, _I, ctypes.POINTER(MotionOpts), _P, _I, _P, _P,
+                                 _P, _P, _P]),
+    "foto_motion_fit_flow_dev": (_I, [ctypes.POINTER(Flow), _I, _I, _I, _I, _P, ctypes.POINTER(MotionOpts), _P, _I, _P,
+                                      _P, _P, _P, _P]),
+    "foto_motion_field_dev": (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
+    "foto_motion_residual_dev": (_I, [ctypes.POINTER(Flow), _P, _I, _I, _I, _P, _P]),
 }
 
 _lib = None

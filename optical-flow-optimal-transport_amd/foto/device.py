@@ -619,3 +619,24 @@ def lk_track(f0, f1, points_or_count, *, check=False, fb_tol=0.5, dtype="float32
         pts = pts[:count]
     p = sparse.cached_lk(w, h, **opts).set_frames(a, b, stream=st)
     return (pts,) + tuple(p.track(pts, check=check, fb_tol=fb_tol, dtype=dtype, stream=st))
+
+
+def global_motion(f0, f1, model="affine", max_corners=1024, *, threshold=1.0, rounds=3, samples=None, min_inliers=0,
+                  fb_tol=0.5, dtype="float32", stream=None, corner_opts=None, **opts):
+    """The global motion between two device frames: the ``max_corners`` strongest Shi-Tomasi
+    corners of ``f0`` (``corner_opts``: foto.sparse.CORNER_DEFAULTS' keys), tracked forward and
+    backward by the cached Lucas-Kanade tracker (``opts``: foto.sparse.LK_DEFAULTS' keys), and
+    ``foto.motion.fit`` with LK's status bytes, all on one stream and with nothing downloaded (the
+    corner count stays on the device: rows beyond it are NaN, which the tracker marks and the fit
+    leaves out).  Returns (fit, points, disp, status): a foto.motion.Fit and the device arrays it
+    was fitted to.  ``foto.render.reconstruct(f1, foto.motion.field(fit, w, h))`` stabilises."""
+    from . import motion, sparse
+    a, b = _pair(f0, f1)
+    h, w = a.shape
+    st = stream_handle(stream, f0, f1)
+    pts, _ = sparse.corners(a, int(max_corners), dtype=dtype, stream=st, wait=False, **(corner_opts or {}))
+    p = sparse.cached_lk(w, h, **opts).set_frames(a, b, stream=st)
+    disp, status, _, _ = p.track(pts, check=True, fb_tol=fb_tol, dtype=dtype, stream=st)
+    fit = motion.fit(pts, disp, w, h, model, status=status, threshold=threshold, rounds=rounds, samples=samples,
+                     min_inliers=min_inliers, stream=st)
+    return fit, pts, disp, status

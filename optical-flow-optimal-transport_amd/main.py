@@ -96,7 +96,27 @@ def build_parser():
                         "half a pixel)")
     p.add_argument("--save-tracks", default=None, metavar="FILE",
                    help="with --lk: one text row per corner, `x y dx dy status err`")
+    p.add_argument("--global-motion", default=None, choices=("translation", "similarity", "affine", "homography"),
+                   metavar="MODEL", help="fit the solved flow with one parametric motion (translation, similarity, "
+                   "affine, homography; foto.motion.fit_flow on every fourth pixel, --save-consistency's mask when "
+                   "that is computed) and print its matrix and inlier share")
+    p.add_argument("--save-residual-flow", default=None, metavar="FILE",
+                   help="with --global-motion: the flow minus the model's field, as .flo")
     return p
+
+
+def global_motion(w, h, u, v, model, mask=None):
+    """The solved flow fitted by ``model`` on the device: (matrix (3, 3), inliers, usable lattice
+    pixels, residual u, residual v).  ``mask``: uint8 (h * w), non-zero = usable."""
+    from foto import device as D
+    from foto import motion
+    flow = D.DeviceArray.from_numpy(np.stack([np.reshape(u, (h, w)), np.reshape(v, (h, w)),
+                                              np.zeros((h, w))]).astype(np.float64))
+    dm = None if mask is None else D.DeviceArray.from_numpy(np.reshape(mask, (h, w)).astype(np.uint8))
+    fit = motion.fit_flow(flow, w, h, mask=dm, model=model)
+    res = motion.residual(flow, fit).to_numpy()
+    inliers, usable, _, _ = fit.counts()
+    return fit.matrix(), inliers, usable, res[0].reshape(-1), res[1].reshape(-1)
 
 
 def lk_tracks(f0, f1, w, h, K, radius=7, levels=4, iters=10, check=False):
@@ -249,6 +269,8 @@ def main(argv=None, writer=None):
     np.random.seed(0)
     if args.flow_full_size and not args.resize:
         raise SystemExit("--flow-full-size needs --resize: there is no other size to come back from")
+    if args.save_residual_flow and not args.global_motion:
+        raise SystemExit("--save-residual-flow needs --global-motion: there is no model to remove")
     full = None
     if args.resize or args.normalize_pair:   # (off by default: every other run reads its frames as before)
         (f1, w, h), (f2, w, h) = prepared_frames(args, args.resize)
@@ -391,6 +413,16 @@ def main(argv=None, writer=None):
         if args.save_tracks:
             print("saving tracks...")
             emit(_write_lines, track_rows(pts, disp, status, err), args.save_tracks)
+
+    if args.global_motion:
+        # (the mask is of the solved flow at the size of the solve: it serves a flow of that size)
+        gm_mask = cross_check(*solved)[0] if args.save_consistency and (sw, sh) == (w, h) else None
+        gm, gm_in, gm_usable, ru, rv = global_motion(w, h, u, v, args.global_motion, gm_mask)
+        print(f" - global motion ({args.global_motion}): " + " ".join(repr(float(x)) for x in gm.ravel()) +
+              " / inlier share: " + str(gm_in / max(gm_usable, 1)))
+        if args.save_residual_flow:
+            print("saving residual flo file...")
+            emit(utils.saveFlo, w, h, ru, rv, args.save_residual_flow)
 
     if args.save_benchmark:
         with open(args.save_benchmark, "w") as f:
