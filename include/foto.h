@@ -1387,6 +1387,77 @@ int foto_motion_field_dev(const double* models, int count, int w, int h, void* o
 int foto_motion_residual_dev(const foto_flow* fl, const double* models, int count, int w, int h, void* out,
                              void* stream);
 
+/* ------------------------------------------------------------------ entropic transport
+ * The static counterpart of the BB solver: entropic optimal transport between two frames on the
+ * pixel grid (Cuturi 2013; Solomon et al. 2015, "Convolutional Wasserstein distances") with the
+ * cost c(x, y) = |x - y|^2 / 2.  The Gibbs kernel exp(-c / eps) is a separable Gaussian of variance
+ * eps px^2, truncated here to the (2 R + 1)^2 box |dx|, |dy| <= R; one Sinkhorn half-iteration is
+ * one separable convolution and one division per pixel.  The plan's barycentric projection is a
+ * flow, its cost a W2.  No reference counterpart; tests/sinkhorn_ref.py restates the arithmetic
+ * below in numpy and the device equals it bit for bit.  Additive.  Everything is float64 on the
+ * device.  Every *_dev entry obeys the stream contract of the device-buffer section; argument
+ * checks that need no device come before any HIP call, device pointers are checked for the
+ * context's device before anything is enqueued.  No entry but foto_sinkhorn_solve waits for the
+ * device: every count is fixed, there is no stop test.
+ *
+ * Frames.  mu (frame 0) and nu (frame 1) are h x w; an input pixel that is negative or not finite
+ * counts as 0 and is counted in `bad`.  The solver equalises nothing: the masses are the caller's
+ * (foto_prep_normalize_pair_dev) and the record reports both.
+ * Tables.  A HOST float64 [3][R + 1], d = 0 .. R: k[d] = exp(-d d / (2 eps)), k1[d] = d k[d],
+ * k2[d] = (0.5 (d d)) k[d] (foto.sinkhorn.tables makes it with numpy; the device never evaluates
+ * exp).  The entries for negative d are k[|d|], -k1[|d|], k2[|d|].
+ * Convolution conv(p, q, z) with row table p and column table q:
+ *   t(j, i) = sum_{d = -R .. R} p[d] z(j, i + d),   s(j, i) = sum_{d = -R .. R} q[d] t(j + d, i),
+ * each sum sequential in ascending d from 0.0, the product rounded before the add; a tap outside
+ * the frame is 0.0.  div(m, s) = m / s where m > 0 and s > 0, else 0.
+ * Iterations.  From a = 0, b = 1, one iteration is a = div(mu, conv(k, k, b)), then b = div(nu,
+ * conv(k, k, a)).
+ * Flow, frame 0 -> frame 1 (direction 0).  With s = conv(k, k, b): u = conv(k1, k, b) / s, v =
+ * conv(k, k1, b) / s where mu > 0 and s > 0 (valid = 1); elsewhere u = v = 0 and valid = 0.  m = 0
+ * everywhere.  Direction 1 (frame 1 -> frame 0) is the same with a, nu in place of b, mu.
+ * The record, float64[8]: sum mu, sum nu, the marginal error sum |a s - mu|, the sharp cost sum a
+ * (conv(k2, k, b) + conv(k, k2, b)), bad, unreachable (pixels with mu > 0 and s = 0), iterations
+ * done, 0.  The sums have one order fixed by w h (they keep their bits from call to call), which
+ * the tests do not rely on beyond the bound of any order, w h 2^-53 sum |terms|.
+ *
+ * FOTO_ERR_ARG (nothing made, nothing enqueued): a null pointer (valid_or_null excepted), w or h <
+ * 1 or w h >= 2^31, radius outside 0 .. FOTO_SINKHORN_MAX_RADIUS, eps not finite and > 0, n < 0, a
+ * direction outside {0, 1}, anything foto_image_check or the export rules reject, a pointer that is
+ * not device memory of the context's device.  FOTO_ERR_STATE: iterate, flow, info or scalings
+ * before any frames.                                                                             */
+#define FOTO_SINKHORN_MAX_RADIUS 32
+#define FOTO_SINKHORN_TILE_W 64   /* the fused kernel's tile: the tests' frame sizes derive from it */
+#define FOTO_SINKHORN_TILE_H 32
+typedef struct {
+    int radius;                /* R, 0 .. FOTO_SINKHORN_MAX_RADIUS                                 */
+    int per_launch_reserved;   /* 0                                                               */
+    double eps;                /* the kernel's variance in px^2, finite and > 0                   */
+} foto_sinkhorn_opts;
+/* eps 2, radius 16 */
+int foto_sinkhorn_opts_default(foto_sinkhorn_opts* o);
+typedef struct foto_sinkhorn foto_sinkhorn;
+/* opts NULL: the defaults.  tables: the host [3][radius + 1] above, copied.  FOTO_SK_FUSED is read
+ * here, once.                                                              */
+int foto_sinkhorn_create(int w, int h, const foto_sinkhorn_opts* opts, const double* tables, foto_sinkhorn** out);
+void foto_sinkhorn_destroy(foto_sinkhorn* c);
+/* The two frames; a = 0, b = 1 and the iteration count 0 again. */
+int foto_sinkhorn_set_frames_dev(foto_sinkhorn* c, const foto_image* f0, const foto_image* f1, void* stream);
+/* n more iterations (n = 0: nothing), four launches each (two with FOTO_SK_FUSED=1). */
+int foto_sinkhorn_iterate_dev(foto_sinkhorn* c, int n, void* stream);
+/* out: a flow record as foto_flow describes it (dtype FOTO_F32 | FOTO_F64, layout 0 planar u, v, m
+ * or 1 interleaved (u, v)); valid_or_null: uint8[h][w].                                          */
+int foto_sinkhorn_flow_dev(foto_sinkhorn* c, int direction, void* out, int dtype, int layout,
+                           unsigned char* valid_or_null, void* stream);
+/* info8: DEVICE float64[8], the record. */
+int foto_sinkhorn_info_dev(foto_sinkhorn* c, double* info8, void* stream);
+/* a_out, b_out: DEVICE float64[h][w]. */
+int foto_sinkhorn_scalings_dev(foto_sinkhorn* c, double* a_out, double* b_out, void* stream);
+/* One shot: the frames set, n iterations, the forward flow.  Host arrays of w h float64 (waits for
+ * the result), or device frames and a device flow record (does not). */
+int foto_sinkhorn_solve(foto_sinkhorn* c, const double* f0, const double* f1, int n, double* u, double* v, double* m);
+int foto_sinkhorn_solve_dev(foto_sinkhorn* c, const foto_image* f0, const foto_image* f1, int n, void* out, int dtype,
+                            int layout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

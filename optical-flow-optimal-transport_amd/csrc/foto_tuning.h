@@ -48,6 +48,9 @@ struct Tuning {
     bool gn_fold = true;        // FOTO_GN_FOLD=0: k_gnp_upd not folded into the level-0 down leg
     bool mg_ltail = true;       // FOTO_MG_LTAIL=0: the three level kernels instead of k_mg_ltail
     int gn_host_threads = 4;    // FOTO_GN_HOST_THREADS: host copy workers, clamped to 0..16
+
+    // ---- entropic transport (foto_sinkhorn.hip)
+    bool sk_fused = false;      // FOTO_SK_FUSED=1: a half-iteration as one LDS-tiled launch, not a row + a column / divide kernel
 };
 
 // the one place that reads the environment: the value of `name` as an integer, dflt when unset
@@ -88,6 +91,7 @@ inline Tuning tuning_from_env() {
     t.mg_ltail = env_int("FOTO_MG_LTAIL", 1) != 0;
     t.gn_host_threads = (int)env_int("FOTO_GN_HOST_THREADS", 4);
     t.gn_host_threads = t.gn_host_threads < 0 ? 0 : t.gn_host_threads > 16 ? 16 : t.gn_host_threads;
+    t.sk_fused = env_int("FOTO_SK_FUSED", 0) != 0;
     return t;
 }
 

@@ -278,6 +278,19 @@ class MotionOpts(ctypes.Structure):
     ]
 
 
+# (include/foto.h, entropic transport)
+FOTO_SINKHORN_MAX_RADIUS, FOTO_SINKHORN_TILE_W, FOTO_SINKHORN_TILE_H = 32, 64, 32
+
+
+class SinkhornOpts(ctypes.Structure):
+    """foto_sinkhorn_opts (include/foto.h): the window radius and the kernel's variance."""
+    _fields_ = [
+        ("radius", ctypes.c_int),
+        ("per_launch_reserved", ctypes.c_int),
+        ("eps", ctypes.c_double),
+    ]
+
+
 ITER_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int)
 
 _D = ctypes.POINTER(ctypes.c_double)
@@ -453,6 +466,17 @@ SIGNATURES = {
                                       _P, _P, _P, _P]),
     "foto_motion_field_dev": (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
     "foto_motion_residual_dev": (_I, [ctypes.POINTER(Flow), _P, _I, _I, _I, _P, _P]),
+    # entropic transport: convolutional Sinkhorn, its flow and its cost
+    "foto_sinkhorn_opts_default": (_I, [ctypes.POINTER(SinkhornOpts)]),
+    "foto_sinkhorn_create": (_I, [_I, _I, ctypes.POINTER(SinkhornOpts), _D, ctypes.POINTER(_P)]),
+    "foto_sinkhorn_destroy": (None, [_P]),
+    "foto_sinkhorn_set_frames_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _P]),
+    "foto_sinkhorn_iterate_dev": (_I, [_P, _I, _P]),
+    "foto_sinkhorn_flow_dev": (_I, [_P, _I, _P, _I, _I, _P, _P]),
+    "foto_sinkhorn_info_dev": (_I, [_P, _P, _P]),
+    "foto_sinkhorn_scalings_dev": (_I, [_P, _P, _P, _P]),
+    "foto_sinkhorn_solve": (_I, [_P, _D, _D, _I, _D, _D, _D]),
+    "foto_sinkhorn_solve_dev": (_I, [_P, ctypes.POINTER(Image), ctypes.POINTER(Image), _I, _P, _I, _I, _P]),
 }
 
 _lib = None

@@ -599,6 +599,20 @@ def tvl1_flow(f0, f1, *, dtype="float32", layout="planar", out=None, stream=None
     return p.solve_device(a, b, out=out, dtype=dtype, layout=layout, stream=stream_handle(stream, f0, f1))[0]
 
 
+def sinkhorn_flow(f0, f1, *, eps=2.0, radius=16, iters=100, dtype="float32", layout="planar", out=None, stream=None):
+    """Entropic optimal transport between two device frames as a flow (the solver from
+    foto.sinkhorn's cache): ``iters`` Sinkhorn iterations with the Gaussian kernel of variance
+    ``eps`` px^2 in a window of ``radius``, then the plan's barycentric projection, frame 0 -> frame
+    1; returns the DeviceArray (or ``out``) holding u, v, m (m = 0): a flow buffer foto.chain,
+    foto.filter, foto.render, foto.evaluate and foto.motion.fit_flow take as it is.  The masses are
+    the caller's (``prepare_pair`` equalises them)."""
+    from . import sinkhorn
+    a, b = _pair(f0, f1)
+    h, w = a.shape
+    p = sinkhorn.cached_sinkhorn(w, h, eps, radius)
+    return p.solve_device(a, b, iters, out=out, dtype=dtype, layout=layout, stream=stream_handle(stream, f0, f1))
+
+
 def lk_track(f0, f1, points_or_count, *, check=False, fb_tol=0.5, dtype="float32", stream=None, corner_opts=None,
              **opts):
     """Pyramidal Lucas-Kanade on device frames (the tracker from foto.sparse's cache; ``opts`` are

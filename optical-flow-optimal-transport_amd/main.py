@@ -51,6 +51,10 @@ def build_parser():
     p.add_argument("--tv-levels", type=int, default=4, help="TVL1: pyramid levels")
     p.add_argument("--tv-warps", type=int, default=5, help="TVL1: linearisations per pyramid level")
     p.add_argument("--tv-iters", type=int, default=30, help="TVL1: inner iterations per warp")
+    p.add_argument("--sk-eps", type=float, default=2.0,
+                   help="sinkhorn: the entropic regularisation, the variance of the Gaussian kernel in px^2")
+    p.add_argument("--sk-radius", type=int, default=16, help="sinkhorn: the kernel's window radius in px (0..32)")
+    p.add_argument("--sk-iters", type=int, default=100, help="sinkhorn: iterations (a fixed count, no stop test)")
     p.add_argument("--inbetweens", type=int, default=0,
                    help="FOTO: motion-compensated in-betweens of the two input frames at this many evenly spaced "
                         "interior times (0: none)")
@@ -341,10 +345,18 @@ def main(argv=None, writer=None):
             print(f"\t - {name}={tv['lam' if name == 'lambda' else name]}")
         solver = tvl1.cached_tvl1(w, h, **tv)
         u, v, m, _ = solver.solve(rho1, rho2)
+    elif args.algo == "sinkhorn":
+        from foto import sinkhorn
+        print(" - algorithm: sinkhorn")
+        print(f"\t - eps={args.sk_eps}")
+        print(f"\t - radius={args.sk_radius}")
+        print(f"\t - iters={args.sk_iters}")
+        solver = sinkhorn.cached_sinkhorn(w, h, args.sk_eps, args.sk_radius)
+        u, v, m = solver.solve(rho1, rho2, args.sk_iters)
     else:
         # reference: `assert("not implemented")` (always true), then NameError on `u` below
-        raise NotImplementedError(f"algorithm {args.algo!r} is not implemented (use --algo=foto, --algo=GN or "
-                                  "--algo=TVL1)")
+        raise NotImplementedError(f"algorithm {args.algo!r} is not implemented (use --algo=foto, --algo=GN, "
+                                  "--algo=TVL1 or --algo=sinkhorn)")
     timer = time.time() - start_time
 
     checked = []
@@ -356,6 +368,8 @@ def main(argv=None, writer=None):
                 bu, bv, _ = gn.assemble(rho2, rho1).process()
             elif args.algo == "TVL1":
                 bu, bv, _, _ = solver.solve(rho2, rho1)
+            elif args.algo == "sinkhorn":
+                bu, bv, _ = solver.solve(rho2, rho1, args.sk_iters)
             else:
                 bu, bv = backward[0]
             checked.append(consistency_mask(sw, sh, fu, fv, bu, bv))
