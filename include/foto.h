@@ -1387,6 +1387,118 @@ int foto_motion_field_dev(const double* models, int count, int w, int h, void* o
 int foto_motion_residual_dev(const foto_flow* fl, const double* models, int count, int w, int h, void* out,
                              void* stream);
 
+/* ------------------------------------------------------------------ feature matching
+ * Wide-baseline correspondences, the stage between foto_corners_dev and foto_motion_fit_dev that
+ * needs no small displacement: a 256-bit binary descriptor of the neighbourhood of each point
+ * (BRIEF, Calonder et al. 2010, test pairs G II; with an intensity-centroid orientation, Rublee et
+ * al. 2011), the nearest and second-nearest descriptor under the Hamming distance with the usual
+ * rejections (a distance bound, Lowe's ratio, a spatial gate), and the mutual check.  No reference
+ * counterpart; tests/match_ref.py restates the arithmetic below in numpy and the device equals it
+ * bit for bit.  Additive.  Frames are foto_image views, widened as (double)pixel / divisor like
+ * every *_dev entry; points are [M][2] = (x, y), x along w.  Every entry obeys the stream contract
+ * of the device-buffer section; argument checks that need no device come before any HIP call,
+ * every device pointer is checked (for the CURRENT device) before anything is enqueued, and an
+ * argument error leaves the outputs untouched.  No entry waits for the device.  (Tables that
+ * differ from those of the previous call are uploaded first, which may wait for that previous
+ * call's work; a scratch that has to grow waits likewise.)
+ *
+ * Tables (HOST, copied by the call; the device draws no random number and evaluates no sin, cos
+ * or atan2).  pattern: int8 [K][256][4] = (ax, ay, bx, by), the 256 test pairs of each of the K =
+ * `orientations` bins, every end inside the disc ax ax + ay ay <= patch patch (foto.match.pattern
+ * draws bin 0 and rotates it into the others).  directions: float64 [K][2] = (C[k], S[k]) = (cos,
+ * sin)(2 pi k / K) (foto.match.directions).
+ *
+ * Descriptors.  The smoothed plane B is the box sum of the widened frame F over (2 blur + 1)^2
+ * pixels, F counting as +0.0 outside the frame, not divided: H[j][i] = sum over dx = -blur .. blur
+ * of F[j][i + dx], in increasing dx from the first term, then B[j][i] = sum over dy = -blur .. blur
+ * of H[j + dy][i], in increasing dy from the first term (the corner detector's box sums).  blur = 0:
+ * B = F.  The keypoint pixel of a point (x, y) is (i, j) = (floor(x + 0.5), floor(y + 0.5)), in
+ * double.  state: FOTO_MATCH_NONFINITE | FOTO_MATCH_OUT for a NaN or Inf coordinate; FOTO_MATCH_OUT
+ * unless patch <= i <= w - 1 - patch and patch <= j <= h - 1 - patch; in either case the
+ * descriptor is four zero words and bin = -1, and nothing is read for the point.  Otherwise state
+ * = 0 and:
+ *   orientation (K > 1): m10 = sum ax F[j + ay][i + ax], m01 = sum ay F[j + ay][i + ax] over the
+ *   elements e = (ay + patch) (2 patch + 1) + (ax + patch), e < n = (2 patch + 1)^2, a term being
+ *   +0.0 where ax ax + ay ay > patch patch; lane p of 64 adds its slots e = p, p + 64, p + 128, ..
+ *   (ceil(n / 64) of them, +0.0 for e >= n) in increasing e from the first term, and the 64 partials
+ *   go through the tree a[p] += a[p + o], p < o, for o = 32, 16, .., 1.  bin = the k that maximises
+ *   m10 C[k] + m01 S[k] (two products, one sum, each rounded), the lowest such k: bin = 0, then k
+ *   = 1 .. K - 1 replaces it when its value is > the value held (false for a NaN: a NaN moment
+ *   gives bin 0).  K = 1: bin = 0 and no moment is computed.
+ *   bits: for t = 0 .. 255 with (ax, ay, bx, by) = pattern[bin][t]: bit t = B[j + ay][i + ax] < B[j +
+ *   by][i + bx] (false for a NaN), bit t % 64 of word t / 64.
+ * desc: uint64[M][4]; state: uint8[M]; bin_or_null: int32[M].
+ * FOTO_ERR_ARG: a null pointer (bin excepted), w or h < 2 patch + 1 or w h >= 2^31, anything
+ * foto_image_check rejects, blur outside 0 .. FOTO_MATCH_MAX_BLUR, patch outside 2 ..
+ * FOTO_MATCH_MAX_PATCH, orientations outside 1 .. FOTO_MATCH_MAX_ORIENT, a pattern entry outside
+ * the disc of `patch`, M < 1 or > 2^31 - 1, a dtype outside {F32, F64}, a misaligned pointer; then a
+ * pointer that is not device memory of the current device, an output that overlaps an input or
+ * another output.
+ *
+ * Matching.  Train entry j < N1 is a CANDIDATE of query i < N0 when state1[j] == 0 and either
+ * max_disp == 0 or both |x1_j - x0_i| <= max_disp and |y1_j - y0_i| <= max_disp, on coordinates
+ * widened to double (false for a NaN).  d(i, j) = the number of set bits of desc0[i] XOR desc1[j]
+ * over the four words.  The best candidate j1 has the smallest key (d, j) -- ties go to the lower j
+ * -- and d1 = d(i, j1); d2 is the smallest d over the other candidates; 257 stands for "none" in
+ * either place.  An order of the reduction does not enter: the minimum of an ordered integer key
+ * has none.  For a query with state0[i] != 0: status = state0[i], idx = -1, dist = (257, 257).
+ * Otherwise dist = (d1, d2), idx = j1, status = 0, and
+ *   FOTO_MATCH_NONE is set, and idx = -1, when there is no candidate or d1 > max_dist (dist keeps
+ *   what was found);
+ *   FOTO_MATCH_AMBIGUOUS is set unless ratio == 0 or d1 256 < ratio d2 (integers; d = 257 where
+ *   there is none, so a query without any candidate carries both bits).
+ * disp (optional): pts1[idx] - pts0[i] per component, in double, narrowed; NaN where idx < 0.
+ * idx: int32[N0]; dist: int32[N0][2]; status: uint8[N0]; disp_or_null: [N0][2] of disp_dtype.
+ * FOTO_ERR_ARG: a null pointer (disp excepted), N0 or N1 < 1 or > 2^31 - 1, max_disp negative, NaN
+ * or infinite, max_dist outside 0 .. 256, ratio outside 0 .. 256, a dtype outside {F32, F64}, a
+ * misaligned pointer (desc0, desc1: 16 bytes, one vector load per half descriptor; a pair array: a
+ * pair); then non-device memory, an output that overlaps an input or another output.
+ *
+ * The mutual check.  foto_match_cross_dev ORs FOTO_MATCH_NOT_MUTUAL into status[i] where idx01[i]
+ * >= 0 and idx10[idx01[i]] != i (an idx01[i] >= N1 counts as not mutual and reads nothing); like
+ * LK's INCONSISTENT it overwrites nothing else.  Two foto_match_dev calls (0 -> 1, 1 -> 0) and this
+ * one, on one stream, are the whole check with nothing downloaded.  The status byte is what
+ * foto_motion_fit_dev takes: non-zero = unusable.                                                 */
+#define FOTO_MATCH_MAX_PATCH 31
+#define FOTO_MATCH_MAX_ORIENT 32
+#define FOTO_MATCH_MAX_BLUR 7
+#define FOTO_MATCH_NONE 1         /* no candidate, or the best one farther than max_dist           */
+#define FOTO_MATCH_OUT 2          /* the patch leaves the frame (FOTO_LK_OUT's value)              */
+#define FOTO_MATCH_NONFINITE 4    /* a NaN or Inf coordinate (FOTO_LK_NONFINITE's value)           */
+#define FOTO_MATCH_NOT_MUTUAL 8   /* the best match's best match is another query                  */
+#define FOTO_MATCH_AMBIGUOUS 16   /* the second best is too close (Lowe's ratio)                   */
+#define FOTO_MATCH_TILE 256       /* train descriptors per LDS tile: the tests' sizes derive from   */
+#define FOTO_MATCH_QUERIES 512    /* queries per block; and from the blocks a launch aims at        */
+#define FOTO_MATCH_BLOCKS 1024
+typedef struct {
+    int blur;           /* the box radius of the smoothed plane, 0 .. FOTO_MATCH_MAX_BLUR          */
+    int patch;          /* the disc's radius, 2 .. FOTO_MATCH_MAX_PATCH                            */
+    int orientations;   /* K, 1 .. FOTO_MATCH_MAX_ORIENT                                           */
+    int reserved;       /* 0                                                                       */
+} foto_describe_opts;
+/* blur 2, patch 15, orientations 1 */
+int foto_describe_opts_default(foto_describe_opts* o);
+typedef struct {
+    double max_disp;    /* the spatial gate in pixels, finite and >= 0; 0: no gate                 */
+    int max_dist;       /* 0 .. 256                                                                */
+    int ratio;          /* 0 .. 256, in 1 / 256; 0: no ratio test                                  */
+    int reserved[2];    /* 0                                                                       */
+} foto_match_opts;
+/* max_disp 0, max_dist 64, ratio 205 (Lowe's 0.8) */
+int foto_match_opts_default(foto_match_opts* o);
+/* opts NULL: the defaults.  pattern, directions: the HOST tables above for opts->orientations. */
+int foto_describe_dev(const foto_image* frame, int w, int h, const void* pts, int pts_dtype, int64_t M,
+                      const foto_describe_opts* opts, const int8_t* pattern, const double* directions,
+                      uint64_t* desc, unsigned char* state, int32_t* bin_or_null, void* stream);
+/* opts NULL: the defaults.  The train set is split over blocks so that about FOTO_MATCH_BLOCKS
+ * blocks run whatever N0 is; the partial minima are merged in a second launch.                   */
+int foto_match_dev(const uint64_t* desc0, const unsigned char* state0, const void* pts0, int pts0_dtype, int64_t N0,
+                   const uint64_t* desc1, const unsigned char* state1, const void* pts1, int pts1_dtype, int64_t N1,
+                   const foto_match_opts* opts, int32_t* idx, int32_t* dist, unsigned char* status,
+                   void* disp_or_null, int disp_dtype, void* stream);
+int foto_match_cross_dev(const int32_t* idx01, int64_t N0, const int32_t* idx10, int64_t N1, unsigned char* status,
+                         void* stream);
+
 /* ------------------------------------------------------------------ entropic transport
  * The static counterpart of the BB solver: entropic optimal transport between two frames on the
  * pixel grid (Cuturi 2013; Solomon et al. 2015, "Convolutional Wasserstein distances") with the

@@ -278,6 +278,32 @@ class MotionOpts(ctypes.Structure):
     ]
 
 
+# (include/foto.h, feature matching)
+FOTO_MATCH_MAX_PATCH, FOTO_MATCH_MAX_ORIENT, FOTO_MATCH_MAX_BLUR = 31, 32, 7
+FOTO_MATCH_NONE, FOTO_MATCH_OUT, FOTO_MATCH_NONFINITE, FOTO_MATCH_NOT_MUTUAL, FOTO_MATCH_AMBIGUOUS = 1, 2, 4, 8, 16
+FOTO_MATCH_TILE, FOTO_MATCH_QUERIES, FOTO_MATCH_BLOCKS = 256, 512, 1024   # the matcher's shape: the tests' sizes
+
+
+class DescribeOpts(ctypes.Structure):
+    """foto_describe_opts (include/foto.h): the box radius, the disc's radius and the orientation bins."""
+    _fields_ = [
+        ("blur", ctypes.c_int),
+        ("patch", ctypes.c_int),
+        ("orientations", ctypes.c_int),
+        ("reserved", ctypes.c_int),
+    ]
+
+
+class MatchOpts(ctypes.Structure):
+    """foto_match_opts (include/foto.h): the spatial gate, the distance bound and Lowe's ratio in 1 / 256."""
+    _fields_ = [
+        ("max_disp", ctypes.c_double),
+        ("max_dist", ctypes.c_int),
+        ("ratio", ctypes.c_int),
+        ("reserved", ctypes.c_int * 2),
+    ]
+
+
 # (include/foto.h, entropic transport)
 FOTO_SINKHORN_MAX_RADIUS, FOTO_SINKHORN_TILE_W, FOTO_SINKHORN_TILE_H = 32, 64, 32
 
@@ -466,6 +492,14 @@ SIGNATURES = {
                                       _P, _P, _P, _P]),
     "foto_motion_field_dev": (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
     "foto_motion_residual_dev": (_I, [ctypes.POINTER(Flow), _P, _I, _I, _I, _P, _P]),
+    # feature matching: binary descriptors at points, the Hamming matcher, the mutual check
+    "foto_describe_opts_default": (_I, [ctypes.POINTER(DescribeOpts)]),
+    "foto_match_opts_default": (_I, [ctypes.POINTER(MatchOpts)]),
+    "foto_describe_dev": (_I, [ctypes.POINTER(Image), _I, _I, _P, _I, ctypes.c_int64, ctypes.POINTER(DescribeOpts), _P, _P,
+                               _P, _P, _P, _P]),
+    "foto_match_dev": (_I, [_P, _P, _P, _I, ctypes.c_int64, _P, _P, _P, _I, ctypes.c_int64, ctypes.POINTER(MatchOpts),
+                            _P, _P, _P, _P, _I, _P]),
+    "foto_match_cross_dev": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P]),
     # entropic transport: convolutional Sinkhorn, its flow and its cost
     "foto_sinkhorn_opts_default": (_I, [ctypes.POINTER(SinkhornOpts)]),
     "foto_sinkhorn_create": (_I, [_I, _I, ctypes.POINTER(SinkhornOpts), _D, ctypes.POINTER(_P)]),

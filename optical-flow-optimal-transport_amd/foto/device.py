@@ -54,11 +54,14 @@ def runtime_check():
     return found
 
 
+_INDEX_DTYPES = ("<i4", "<u8")   # foto.match's indices, distances and descriptor words: no frame, no flow
+
+
 def _typestr(dtype):
     dt = np.dtype(dtype)
     ts = dt.str if dt.itemsize > 1 else "|" + dt.str[1:]
-    if ts not in _DTYPES:
-        raise ValueError(f"dtype {dt}: device arrays hold uint8, float32 or float64")
+    if ts not in _DTYPES and ts not in _INDEX_DTYPES:
+        raise ValueError(f"dtype {dt}: device arrays hold uint8, float32 or float64 (and int32 / uint64 tables)")
     return ts
 
 
@@ -651,6 +654,56 @@ def global_motion(f0, f1, model="affine", max_corners=1024, *, threshold=1.0, ro
     pts, _ = sparse.corners(a, int(max_corners), dtype=dtype, stream=st, wait=False, **(corner_opts or {}))
     p = sparse.cached_lk(w, h, **opts).set_frames(a, b, stream=st)
     disp, status, _, _ = p.track(pts, check=True, fb_tol=fb_tol, dtype=dtype, stream=st)
+    fit = motion.fit(pts, disp, w, h, model, status=status, threshold=threshold, rounds=rounds, samples=samples,
+                     min_inliers=min_inliers, stream=st)
+    return fit, pts, disp, status
+
+
+_DESCRIBE_KEYS, _MATCH_KEYS = ("blur", "patch", "orientations", "seed", "table"), ("max_disp", "max_dist", "ratio")
+
+
+def match_frames(f0, f1, max_corners=1024, *, check=True, corner_opts=None, dtype="float32", stream=None, **opts):
+    """Wide-baseline correspondences between two device frames (foto.match): the ``max_corners``
+    strongest Shi-Tomasi corners of each frame (``corner_opts``: foto.sparse.CORNER_DEFAULTS' keys,
+    the margin raised to at least the patch radius), their binary descriptors, the nearest frame-1
+    corner of every frame-0 corner under the Hamming distance and, with ``check``, the mutual
+    check.  ``opts``: foto.match.describe's blur, patch, orientations, seed, table and
+    foto.match.match's max_disp, max_dist, ratio.  All on one stream and with nothing downloaded
+    (the corner counts stay on the device: rows beyond them are NaN, which ``describe`` marks and the
+    matcher leaves out).  Returns (points (M, 2), disp (M, 2), status (M,), idx (M,), dist (M, 2)):
+    what lk_track's callers and foto.motion.fit take as they are."""
+    from . import match as MT
+    from . import sparse
+    a, b = _pair(f0, f1)
+    st = stream_handle(stream, f0, f1)
+    unknown = set(opts) - set(_DESCRIBE_KEYS) - set(_MATCH_KEYS)
+    if unknown:
+        raise TypeError(f"matching options are {sorted(_DESCRIBE_KEYS + _MATCH_KEYS)}; got {sorted(unknown)}")
+    d_opts = {k: opts[k] for k in _DESCRIBE_KEYS if k in opts}
+    m_opts = {k: opts[k] for k in _MATCH_KEYS if k in opts}
+    co = dict(sparse.CORNER_DEFAULTS, **(corner_opts or {}))
+    co["margin"] = max(int(co["margin"]), int(d_opts.get("patch", MT.DESCRIBE_DEFAULTS["patch"])))
+    p0, _ = sparse.corners(a, int(max_corners), dtype=dtype, stream=st, wait=False, **co)
+    p1, _ = sparse.corners(b, int(max_corners), dtype=dtype, stream=st, wait=False, **co)
+    d0, s0 = MT.describe(a, p0, stream=st, **d_opts)
+    d1, s1 = MT.describe(b, p1, stream=st, **d_opts)
+    idx, dist, status, disp = MT.match(d0, s0, p0, d1, s1, p1, dtype=dtype, stream=st, **m_opts)
+    if check:
+        idx10 = MT.match(d1, s1, p1, d0, s0, p0, dtype=dtype, stream=st, **m_opts)[0]
+        MT.cross(idx, idx10, status, stream=st)
+    return p0, disp, status, idx, dist
+
+
+def match_motion(f0, f1, model="affine", max_corners=1024, *, threshold=1.0, rounds=3, samples=None, min_inliers=0,
+                 check=True, dtype="float32", stream=None, corner_opts=None, **opts):
+    """global_motion with ``match_frames`` in the tracker's place: the global motion between two
+    device frames that may be a large pan or a roll apart.  Returns (fit, points, disp, status)."""
+    from . import motion
+    a, b = _pair(f0, f1)
+    h, w = a.shape
+    st = stream_handle(stream, f0, f1)
+    pts, disp, status, _, _ = match_frames(a, b, max_corners, check=check, corner_opts=corner_opts, dtype=dtype,
+                                           stream=st, **opts)
     fit = motion.fit(pts, disp, w, h, model, status=status, threshold=threshold, rounds=rounds, samples=samples,
                      min_inliers=min_inliers, stream=st)
     return fit, pts, disp, status

@@ -98,8 +98,19 @@ def build_parser():
     p.add_argument("--lk-check", action="store_true",
                    help="LK: the forward-backward check (status bit 8: the round trip misses the corner by more than "
                         "half a pixel)")
+    p.add_argument("--match", type=int, default=0, metavar="K",
+                   help="instead of --lk: match the K strongest corners of frame 0 to those of frame 1 by binary "
+                        "descriptors (foto.match: no limit on the displacement; 0: none); with --global-motion also "
+                        "fits the model to the matches")
+    p.add_argument("--match-orientations", type=int, default=1, metavar="N",
+                   help="match: orientation bins of the descriptor (1: upright; 32 follows a roll of the camera)")
+    p.add_argument("--match-ratio", type=float, default=0.8, help="match: Lowe's ratio (0: no ratio test)")
+    p.add_argument("--match-max-disp", type=float, default=0.0, metavar="PX",
+                   help="match: only corners within PX pixels in x and in y are candidates (0: no gate)")
+    p.add_argument("--match-patch", type=int, default=15, metavar="R", help="match: the descriptor's radius (2..31)")
     p.add_argument("--save-tracks", default=None, metavar="FILE",
-                   help="with --lk: one text row per corner, `x y dx dy status err`")
+                   help="with --lk or --match: one text row per corner, `x y dx dy status err` (--match: err is the "
+                        "best Hamming distance)")
     p.add_argument("--global-motion", default=None, choices=("translation", "similarity", "affine", "homography"),
                    metavar="MODEL", help="fit the solved flow with one parametric motion (translation, similarity, "
                    "affine, homography; foto.motion.fit_flow on every fourth pixel, --save-consistency's mask when "
@@ -130,6 +141,25 @@ def lk_tracks(f0, f1, w, h, K, radius=7, levels=4, iters=10, check=False):
     a, b = (D.DeviceArray.from_numpy(np.asarray(f, dtype=np.float64).reshape(h, w)) for f in (f0, f1))
     res = D.lk_track(a, b, int(K), check=check, dtype="float64", radius=radius, levels=levels, iters=iters)
     return tuple(x.to_numpy() for x in res[:4])
+
+
+def match_tracks(f0, f1, w, h, K, model=None, orientations=1, ratio=0.8, max_disp=0.0, patch=15):
+    """(points, disp, status, best distance) of --match K as numpy arrays, the rows of frame 0's
+    corners: foto.device.match_frames on the two frames, mutual check included; with ``model`` the
+    matches are fitted too (foto.motion.fit): (matrix (3, 3), inliers, usable matches) after them."""
+    from foto import device as D
+    from foto import motion
+    a, b = (D.DeviceArray.from_numpy(np.asarray(f, dtype=np.float64).reshape(h, w)) for f in (f0, f1))
+    pts, disp, status, _, dist = D.match_frames(a, b, int(K), dtype="float64", orientations=orientations,
+                                                ratio=ratio if ratio > 0 else None, max_disp=max_disp, patch=patch)
+    fit = motion.fit(pts, disp, w, h, model, status=status) if model else None
+    p = pts.to_numpy()
+    rows = np.isfinite(p).all(axis=1)   # (the rows beyond the corner count are NaN)
+    res = (p[rows], disp.to_numpy()[rows], status.to_numpy()[rows], dist.to_numpy()[rows, 0].astype(np.float64))
+    if fit is not None:
+        inliers, usable, _, _ = fit.counts()
+        res += (fit.matrix(), inliers, usable)
+    return res
 
 
 def flows_at(points, w, h, *flows):
@@ -275,6 +305,8 @@ def main(argv=None, writer=None):
         raise SystemExit("--flow-full-size needs --resize: there is no other size to come back from")
     if args.save_residual_flow and not args.global_motion:
         raise SystemExit("--save-residual-flow needs --global-motion: there is no model to remove")
+    if args.lk > 0 and args.match > 0:
+        raise SystemExit("--lk and --match are two ways to the same tracks: choose one")
     full = None
     if args.resize or args.normalize_pair:   # (off by default: every other run reads its frames as before)
         (f1, w, h), (f2, w, h) = prepared_frames(args, args.resize)
@@ -424,6 +456,19 @@ def main(argv=None, writer=None):
             if known.any():
                 print(" - LK EE-mean at the corners: " + str(float(np.hypot(*(disp - gt)[known].T).mean())))
                 print(f" - {args.algo} EE-mean at the corners: " + str(float(np.hypot(*(dense - gt)[known].T).mean())))
+        if args.save_tracks:
+            print("saving tracks...")
+            emit(_write_lines, track_rows(pts, disp, status, err), args.save_tracks)
+
+    if args.match > 0:
+        res = match_tracks(f1, f2, w, h, args.match, args.global_motion, args.match_orientations, args.match_ratio,
+                           args.match_max_disp, args.match_patch)
+        pts, disp, status, err = res[:4]
+        print(f" - match: {int(np.count_nonzero(status == 0))} of {len(pts)} corners matched (patch "
+              f"{args.match_patch}, {args.match_orientations} orientations, ratio {args.match_ratio})")
+        if args.global_motion:
+            print(f" - match motion ({args.global_motion}): " + " ".join(repr(float(x)) for x in res[4].ravel()) +
+                  " / inlier share: " + str(res[5] / max(res[6], 1)))
         if args.save_tracks:
             print("saving tracks...")
             emit(_write_lines, track_rows(pts, disp, status, err), args.save_tracks)
